@@ -12,6 +12,8 @@ reverse-mode adjoint step (Grad.transfer_grad: contact re-detection, un-projecte
 kernels).  The timed region runs K forward steps onto the tape and then the K adjoint steps of the same rollout, all state
 resident in HBM.  value = cloth triangles x K x n_gpus / wall seconds (max over ranks).  Ranks run independent scene rollouts
 (trajectory-optimisation batch): no data-path collective, "scaling": "weak".
+--dump-outputs DIR writes what the timed rollout computed (dump_outputs) as .npy files; the inputs depend on the arguments only, so
+two builds run with the same arguments can be compared output for output.
 
 The JSON line also carries
   roofline      -- the kernel class of the sparse direct solve that takes the most time per Newton iteration (named in the object):
@@ -542,6 +544,34 @@ def roofline(ctx, scene, elapsed, K, stats, args):
     return rf, step
 
 
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, grad, K):
+    """--dump-outputs: what the timed rollout handed its caller, as DIR/<name>.npy in float64 -- the state after the last forward step
+    (the tape's x_K: the reverse sweep leaves the scene itself at x_1), the parameter-side gradients of the reverse sweep's last step
+    (pos_grad / angleref_grad of tape step 0) and the gripper gradients of the K steps.  An array larger than its share of the 64 MB
+    budget is replaced by a fixed sample of its leading-axis rows (default_rng(0), sorted), the same for every run with the same arguments."""
+    import numpy as np
+    arrays = {
+        "pos_final": grad.pos_buffer.t[K],
+        "pos_grad_0": grad.pos_grad.t[0],
+        "angleref_grad_0": grad.angleref_grad.t[0].reshape(-1, 3),
+        "gripper_grad": grad.gripper_grad.t[1:K + 1],
+    }
+    share = (DUMP_BUDGET_BYTES - 4096 * len(arrays)) // len(arrays)    # room for the .npy headers
+    os.makedirs(out_dir, exist_ok=True)
+    written = {}
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy().astype(np.float64, copy=False)
+        if a.nbytes > share:
+            rows = max(1, share // max(1, a[0].nbytes))
+            a = a[np.sort(np.random.default_rng(0).choice(a.shape[0], size=rows, replace=False))]
+        np.save(os.path.join(out_dir, f"{name}.npy"), np.ascontiguousarray(a))
+        written[name] = list(a.shape)
+    return written
+
+
 def timed_region(batch, run, sync=None):
     """The timed region of the contract: barrier + device synchronisation on BOTH sides of `run()` (K steps of this rank's rollout), wall seconds = the MAX over
     the ranks.  Returns (what run returned, seconds).  Rank logic only -- tests/test_host_logic.py drives it with two gloo ranks and a stand-in rollout."""
@@ -592,6 +622,8 @@ def main():
     ap.add_argument("--cpu-grid", type=int, default=71, help="cloth grid of the complete oracle steps of cpu_baseline")
     ap.add_argument("--cpu-steps", type=int, default=2)
     ap.add_argument("--cpu-threads", type=int, default=16)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed rollout computed (rank 0) as DIR/<name>.npy in float64, at most 64 MB in all")
     args = ap.parse_args()
     if args.workload == "cfg3" and args.grid == 224:
         args.grid = 200
@@ -635,6 +667,7 @@ def main():
     stats, elapsed = timed_region(batch, lambda: run_rollout(scene, grad, K, args), torch.cuda.synchronize)
     info1 = ctx.direct_info()
     stats["factorizations_total"] = info1["factorizations"] - info0["factorizations"]
+    dumped = dump_outputs(args.dump_outputs, grad, K) if args.dump_outputs and rank == 0 else None
 
     T = scene.cloths[0].NF
     n_solves_fwd = max(stats["newton"], 1)
@@ -669,6 +702,8 @@ def main():
                    "max_rel_residual_fwd": stats["max_res_fwd"], "max_rel_residual_adjoint": stats["max_res_adj"], "max_backward_error_adjoint": stats["max_be_adj"],
                    "adjoint_solve_methods": {str(k): v for k, v in stats["methods"].items()}},
     })
+    if dumped is not None:
+        out["dumped_outputs"] = {"dir": args.dump_outputs, "shapes": dumped}
     rf, step = roofline(ctx, scene, elapsed, K, stats, args)
     if rf is not None:
         rf["whole_step"] = step   # SURVEY section 8d's bytes model and the factorisation-flops figure of the WHOLE step, inside the object the driver keeps
