@@ -102,7 +102,7 @@ int tsl_ctx_create(const tsl_scene_desc* desc, tsl_ctx** out);
 void tsl_ctx_destroy(tsl_ctx* ctx);
 int tsl_set_stream(tsl_ctx* ctx, void* hip_stream);
 
-/* 0-d field writes of the reference and the engine's own switches (39 keys + three patterns; an unknown key is an error).
+/* 0-d field writes of the reference and the engine's own switches (40 keys + three patterns; an unknown key is an error).
  *  Scene (trajopt_folding.py:50,66; Scene_folding.py:30-31; geometry.py:8-19; geometry_self.py:166-230):
  *   "cloth<i>.Kb|Kl|Ka|k_angle", "elastic<i>.mu|lam|alpha", "mu_cloth_elastic", "mu_cloth_cloth", "k_contact", "eps_contact", "eps_v", "damping",
  *   "newton_cap", "plastic", "contact" (0: no detection in tsl_step), "grid_h", "grid_extent" (broad-phase cell and box), "self_contact<body>"
@@ -125,7 +125,10 @@ int tsl_set_stream(tsl_ctx* ctx, void* hip_stream);
  *   factorisation are cleared on a side stream after each solve of a time step, 64 plans of earlier constraint sets are kept.)
  *   "mg" (-1 auto / 0 / 1), "mg_coarse_exact", "mg_dense_nodes" (largest multigrid level solved exactly; -1 = chosen per time step), "body_inv"
  *   (dense inverses of the small FEM-body blocks), "gmres_m" (GMRES restart length), "tet_warm" (1: the eigen-clamp of the element blocks starts from
- *   the eigenvectors of the element's previous assembly).
+ *   the eigenvectors of the element's previous assembly), "spd_literal" (0 default: the forward projections of the cloth spring blocks, the contact normal
+ *   blocks and the tactile element blocks are a converged Jacobi eigen-clamp; 1: the reference's own projector, SPD_Projector of linalg.py:15-148 --
+ *   Householder, at most K = 10 (3 x 3) / 20 (9 x 9) shifted-QR sweeps, rebuild from the positive diagonal -- with the reference's arithmetic: the
+ *   same bits as its x86-64 restatement in oracle/tslo_linalg.h for the same block.  The preconditioner-only assembly and the adjoint are not affected).
  *   (Element gradients / blocks and contact rows go to staging slots and records and are summed by gather kernels in a fixed order, constraint lists are
  *   compacted by scan, energies and dot products joined from per-workgroup partials: no f64 atomics on the step and adjoint path, two runs give the same
  *   bits.  There is no switch: the scattered-atomics assembly of rounds 1-3 and its "deterministic" key are gone.)
@@ -200,7 +203,8 @@ int tsl_proj_import(tsl_ctx* ctx, const int32_t* proj_flag_host, const int32_t* 
 /* BaseScene.border_flag (tot_NV; BaseScene.py:104, restored by Scene_balancing.load_all :213-222, read by project_pair geometry.py:194-201) */
 int tsl_set_border(tsl_ctx* ctx, const int32_t* border_flag_host);
 
-/* Batched SPD projections (linalg.py:5-12 and :15-148) on device arrays of D x D blocks, D in {2,3,9}. */
+/* Batched SPD projections (linalg.py:5-12 and :15-148) on device arrays of D x D blocks, D in {2,3,9}; D = 3 and 9 follow "spd_literal"
+ * (the device functions of the assembly, K = 10 / 20). */
 int tsl_spd_project(tsl_ctx* ctx, double* blocks_dev, int32_t n_blocks, int32_t D);
 
 /* Timing of the dominant kernel for bench.py's roofline object: HIP-event time (ms) accumulated over the

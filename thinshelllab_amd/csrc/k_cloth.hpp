@@ -210,7 +210,8 @@ __global__ void k_cloth_quirk(ClothArgs A, int n_cloth, const double* __restrict
 // of blocks, accumulated in registers and flushed once.
 // CLAMP_ALL: the whole 9x9 face block (springs + un-projected area and bending parts) is projected as well -- used only to
 // build an SPD preconditioner when the reference's partially projected Hessian turns out indefinite.
-template <bool CLAMP_ALL>
+// LIT ("spd_literal" = 1, spd 1 only): the spring blocks are projected by the reference's own projector (spd_literal3, K = 10) instead of the eigen-clamp.
+template <bool CLAMP_ALL, bool LIT = false>
 __global__ void __launch_bounds__(128)
 k_cloth_hess_face(ClothArgs A, const double* __restrict__ pos, const double* __restrict__ ref_angle, const double* __restrict__ Q, int spd, double* __restrict__ rec) {
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
@@ -243,7 +244,10 @@ k_cloth_hess_face(ClothArgs A, const double* __restrict__ pos, const double* __r
         const double G = (j == k) ? (1.0 - dd[j] * dd[j]) / len : dd[j] * dd[k] / len;
         K[j * 3 + k] = dl * G + dl2 * dd[j] * dd[k];
       }
-    if (spd) spd_clamp<3>(K);
+    if (spd) {
+      if constexpr (LIT) spd_literal3<10>(K);
+      else spd_clamp<3>(K);
+    }
 #pragma unroll
     for (int j = 0; j < 3; j++)
 #pragma unroll

@@ -361,6 +361,8 @@ __global__ void k_contact_energy(int nc, ContactArgs A, const double* __restrict
 // a time and 16 lanes in lock step: 125-185 us; gone.)
 TSL_DEV d3 c_unit(int a) { return d3(a == 0 ? 1.0 : 0.0, a == 1 ? 1.0 : 0.0, a == 2 ? 1.0 : 0.0); }
 TSL_DEV double c_comp(const d3& v, int a) { return a == 0 ? v.x : (a == 1 ? v.y : v.z); }
+// LIT ("spd_literal" = 1, spd 1 only): the normal block is projected by the reference's own projector (spd_literal9_coop, K = 20; a third LDS array for T).
+template <bool LIT = false>
 __global__ void __launch_bounds__(256)
 k_contact_assemble_coop(int nc, ContactArgs A, const double* __restrict__ pos, int spd, double* __restrict__ Hfull, double* __restrict__ cg) {
   const int l = threadIdx.x & 15;
@@ -411,7 +413,20 @@ k_contact_assemble_coop(int nc, ContactArgs A, const double* __restrict__ pos, i
     }
     g9 = G9j * pe_pd;
   }
-  if (spd) {
+  if constexpr (LIT) {
+    __shared__ double sA[16][81], sQ[16][81], sT[16][81];
+    const int g = threadIdx.x >> 4;
+    if (l < 9) {
+#pragma unroll
+      for (int k = 0; k < 9; k++) sA[g][l * 9 + k] = h[k];
+    }
+    spd_grp_sync();
+    spd_literal9_coop(sA[g], sT[g], sQ[g], l, active);
+    if (l < 9) {
+#pragma unroll
+      for (int k = 0; k < 9; k++) h[k] = sA[g][l * 9 + k];
+    }
+  } else if (spd) {   // (LIT is instantiated for spd 1 only)
     __shared__ double sA[16][81], sV[16][81];
     const int g = threadIdx.x >> 4;
     if (l < 9) {
@@ -699,6 +714,30 @@ __global__ void k_spd_batch(double* blocks, int n, int D) {
     blocks[4 * (size_t)i] = a; blocks[4 * (size_t)i + 1] = b; blocks[4 * (size_t)i + 2] = b; blocks[4 * (size_t)i + 3] = d;
   }
 }
+// the same with "spd_literal" = 1: the reference's projector through the device functions of the assembly -- D = 3 one lane per block (spd_literal3, K = 10),
+// D = 9 sixteen lanes per block (spd_literal9_coop, K = 20; 256-thread workgroups)
+__global__ void __launch_bounds__(256) k_spd_batch_literal(double* blocks, int n, int D) {
+  if (D == 3) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    double A[9];
+#pragma unroll
+    for (int k = 0; k < 9; k++) A[k] = blocks[9 * (size_t)i + k];
+    spd_literal3<10>(A);
+#pragma unroll
+    for (int k = 0; k < 9; k++) blocks[9 * (size_t)i + k] = A[k];
+    return;
+  }
+  __shared__ double sA[16][81], sQ[16][81], sT[16][81];
+  const int l = threadIdx.x & 15, g = threadIdx.x >> 4;
+  const int i = (int)((blockIdx.x * (size_t)blockDim.x + threadIdx.x) >> 4);
+  const bool valid = i < n;
+  const size_t b0 = 81 * (size_t)(valid ? i : 0);   // (groups beyond the list project a copy of block 0 and store nothing)
+  for (int q = l; q < 81; q += 16) sA[g][q] = blocks[b0 + q];
+  spd_grp_sync();
+  spd_literal9_coop(sA[g], sT[g], sQ[g], l, valid);
+  if (valid) for (int q = l; q < 81; q += 16) blocks[b0 + q] = sA[g][q];
+}
 
 // ------------------------------------------------------------------------------------------------ host side
 static inline int cnblk(long n, int b) { return (int)((n + b - 1) / b); }
@@ -906,7 +945,8 @@ static int contact_assemble(tsl_ctx* c, const double* pos, int spd, double* grad
   A.k_contact = c->k_contact; A.eps_contact = c->eps_contact; A.eps_vh = c->eps_v * c->dt;
   if (grad && c->c_G.n < 12 * (size_t)c->max_n_constraints) { if (c->c_G.alloc(12 * (size_t)c->max_n_constraints)) return -1; }
   double* cg = grad ? c->c_G.p : (double*)nullptr;   // per-constraint gradients, summed per vertex by k_contact_row_gather
-  hipLaunchKernelGGL(k_contact_assemble_coop, dim3(cnblk((long)c->nc * 16, 256)), dim3(256), 0, s, c->nc, A, pos, spd, c->c_Hfull.p, cg);
+  if (c->spd_literal && spd == 1) hipLaunchKernelGGL(k_contact_assemble_coop<true>, dim3(cnblk((long)c->nc * 16, 256)), dim3(256), 0, s, c->nc, A, pos, spd, c->c_Hfull.p, cg);
+  else hipLaunchKernelGGL(k_contact_assemble_coop<false>, dim3(cnblk((long)c->nc * 16, 256)), dim3(256), 0, s, c->nc, A, pos, spd, c->c_Hfull.p, cg);
   hipLaunchKernelGGL(k_contact_mask, dim3(cnblk((long)c->nc * 144, 256)), dim3(256), 0, s, c->nc, c->c_idx.p, c->frozen.p, c->c_Hfull.p, c->c_H.p);
   // the diagonal 3 x 3 blocks of the contact terms feed the block-Jacobi inverse and the hierarchy's Galerkin diagonal only: a solve that goes to the
   // factorisation never reads them (45 us on the longest chain of an assembly); block_jacobi_refresh forms them when the hierarchy runs after all

@@ -194,6 +194,9 @@ TSL_DEV m3 tet_dH(const ElasticDev& e, const m3& F, const m3& Fi, const m3& FiT,
 // (b / 4, b % 4) of the element record that k_cloth_gather sums into the matrix.  (Rounds 1-5: one lane per element with the block and the basis in
 // private arrays -- 512 registers, 1414 spilled, 130-170 us for the 5.8k elements of cfg4, the longest kernel of an assembly.)  kind 0 = 9 x 9 over vertices 0..2 with optional SPD projection, vertex 3 = minus row / column sums
 // (model_elastic_tactile.py:88-124); kind 1 = direct 12 x 12 (model_elastic_offset.py:101-167, no projection).
+// LIT ("spd_literal" = 1, spd 1 only): the kind-0 blocks are projected by the reference's own projector (spd_literal9_coop, K = 20) as formed -- no
+// symmetrisation, no warm basis (Vws is not read or written).
+template <bool LIT = false>
 __global__ void __launch_bounds__(256)
 k_tet_hess_coop(TetArgs A, const double* __restrict__ pos, int spd, double* __restrict__ Vws, int warm, double* __restrict__ rec) {
   __shared__ double sA[16][81], sV[16][81], sT[16][81];
@@ -227,8 +230,10 @@ k_tet_hess_coop(TetArgs A, const double* __restrict__ pos, int spd, double* __re
       for (int j = 0; j < 3; j++) sa[l * 9 + i * 3 + j] = dH.m[j * 3 + i];
   }
   spd_grp_sync();
-  const bool clamp = (e.kind == 0 && spd) || spd == 2;   // spd 2: preconditioner-only assembly, every element block projected
-  if (__any(clamp)) {
+  const bool clamp = (e.kind == 0 && spd) || (!LIT && spd == 2);   // spd 2: preconditioner-only assembly, every element block projected (LIT: spd 1 only)
+  if constexpr (LIT) {
+    if (__any(clamp)) spd_literal9_coop(sa, st, sv, l, clamp);
+  } else if (__any(clamp)) {
     // symmetrise (spd_clamp_warm does so before the basis change)
     if (l < 9 && clamp) {
       for (int k = l + 1; k < 9; k++) { const double s2 = 0.5 * (sa[l * 9 + k] + sa[k * 9 + l]); sa[l * 9 + k] = s2; sa[k * 9 + l] = s2; }

@@ -215,6 +215,7 @@ struct tsl_ctx {
   double dt = 5e-3, k_contact = 1000, eps_contact = 1e-3, eps_v = 0.01, damping = 1.0, mu_cloth_elastic = 1.0, mu_cloth_cloth = 1.0;
   int max_n_constraints = 10000;
   int newton_cap = 1000, plastic = 0, contact_enable = 1;
+  int spd_literal = 0;   // 1: the forward projections of the spring, contact-normal and element blocks run the reference's Householder + QR projector (spd_literal3 / spd_literal9_coop)
   double cg_tol = 1e-10;
   int cg_maxit = 200000, cg_check = 32;
   double grid_h = 0.003;

@@ -323,6 +323,259 @@ TSL_DEV void spd_clamp9_cold(double* __restrict__ sa, double* __restrict__ sv, i
   spd_clamp9_par(sa, sv, l, on);
 }
 
+// ---- the reference's own projector (context key "spd_literal" = 1): SPD_Projector, engine/linalg.py:15-148 ----------------------------------------------------------
+// Householder tridiagonalisation (a column whose sub-diagonal norm is below 1e-6 is skipped), at most K Wilkinson-shifted QR sweeps on the tridiagonal (absolute
+// 1e-5 guards: the sweeps stop when every sub-diagonal entry is at most 1e-5, the active block ends behind the last larger one), then A <- sum over the diagonal
+// entries v_i > 0 of v_i q_i q_i^T.  Not always converged (K = 10 for the 3 x 3 spring blocks, 20 for the 9 x 9 contact and element blocks), and it reads the LOWER
+// triangle of A only: the input is not symmetrised.  Every sum runs sequentially in the reference's order and nothing is contracted into an FMA, so that the result
+// has the bits of the x86-64 build of the reference's arithmetic (the oracle of the tests): division and sqrt are correctly rounded on both.
+//
+// The QR sweeps on the tridiagonal (dg: diagonal, sb: sub-diagonal A(i+1, i), sp: super-diagonal A(i, i+1)) and the rotations of R rows of Q (q: R x N, row major):
+// everything in registers with compile-time indices (the active size m only guards the unrolled steps).
+template <int N, int K, int R>
+TSL_DEV void spd_lit_qr(double* dg, double* sb, double* sp, double* q) {
+#pragma clang fp contract(off)
+  for (int sw = 0; sw < K; sw++) {
+    int m = 0;
+#pragma unroll
+    for (int i = 0; i < N - 1; i++)
+      if (fabs(sb[i]) > 1e-5) m = i + 2;
+    if (m == 0) break;
+    double a = 0.0, b = 0.0, c = 0.0;
+#pragma unroll
+    for (int t = 2; t <= N; t++)
+      if (m == t) { a = dg[t - 2]; b = sp[t - 2]; c = dg[t - 1]; }
+    double d = (a - c) / 2;
+    const double sd = d > 0 ? 1.0 : -1.0;
+    double mu = c;
+    if (fabs(b) > 1e-6) mu -= (sd * b * b) / (fabs(d) + sqrt(d * d + b * b));
+#pragma unroll
+    for (int i = 0; i < N; i++) dg[i] -= mu;
+    double sv[N - 1];
+#pragma unroll
+    for (int i = 0; i < N - 1; i++) {
+      sv[i] = 0.0;
+      if (i < m - 1) {
+        a = dg[i]; b = sp[i];
+        const double e = sb[i];
+        d = dg[i + 1];
+        double s = fabs(e) > 1e-5 ? fabs(e / sqrt(a * a + e * e)) : 0.0;
+        if (a * e < 0) s *= -1;
+        const double r = 1 - s * s;
+        c = sqrt(r < 0.0 ? 0.0 : r);
+        sv[i] = s;
+        dg[i] = a * c + e * s;
+        sp[i] = b * c + d * s;
+        dg[i + 1] = d * c - b * s;
+        if (i < N - 2) sp[i + 1] *= c;
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < N - 1; i++) {
+      if (i < m - 1) {
+        a = dg[i]; b = sp[i]; d = dg[i + 1];
+        const double s = sv[i];
+        const double r = 1 - s * s;
+        c = sqrt(r < 0.0 ? 0.0 : r);
+        dg[i] = a * c + b * s;
+        sb[i] = s * d;
+        dg[i + 1] = c * d;
+#pragma unroll
+        for (int w = 0; w < R; w++) {
+          const double qa = q[w * N + i], qb = q[w * N + i + 1];
+          q[w * N + i] = qa * c + qb * s;
+          q[w * N + i + 1] = -qa * s + qb * c;
+        }
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < N - 1; i++) sp[i] = sb[i];
+#pragma unroll
+    for (int i = 0; i < N; i++) dg[i] += mu;
+  }
+}
+
+// 3 x 3, one lane per block: A (row major), T and Q in registers, every loop unrolled.  K: the sweep limit (10 at the reference's spring blocks).
+template <int K>
+TSL_DEV void spd_literal3(double* A) {
+#pragma clang fp contract(off)
+  constexpr int n = 3;
+  double T[n * n], Q[n * n];
+#pragma unroll
+  for (int i = 0; i < n * n; i++) { T[i] = 0.0; Q[i] = (i % (n + 1) == 0) ? 1.0 : 0.0; }
+#pragma unroll
+  for (int i = 0; i < n - 2; i++) {
+    double b = 0.0;
+#pragma unroll
+    for (int j = i + 1; j < n; j++) b += A[j * n + i] * A[j * n + i];
+    b = sqrt(b);
+    if (b < 1e-6) {
+      T[i * n + i] = -1;
+#pragma unroll
+      for (int j = i + 1; j < n; j++) A[i * n + j] = 0;
+    } else {
+      T[i * n + i] = 1;
+      if (A[(i + 1) * n + i] < 0) b *= -1;
+      T[(i + 1) * n + i] = A[(i + 1) * n + i] + b;
+      double c = T[(i + 1) * n + i] * T[(i + 1) * n + i];
+#pragma unroll
+      for (int j = i + 2; j < n; j++) { T[j * n + i] = A[j * n + i]; c += A[j * n + i] * A[j * n + i]; }
+      c = sqrt(2 / c);
+#pragma unroll
+      for (int j = i + 1; j < n; j++) T[j * n + i] *= c;
+#pragma unroll
+      for (int j = i + 1; j < n; j++) {
+        double t = 0.0;
+#pragma unroll
+        for (int k = i + 1; k < j + 1; k++) t += A[j * n + k] * T[k * n + i];
+#pragma unroll
+        for (int k = j + 1; k < n; k++) t += A[k * n + j] * T[k * n + i];
+        T[i * n + j] = t;
+      }
+      double d = 0.0;
+#pragma unroll
+      for (int j = i + 1; j < n; j++) d += T[i * n + j] * T[j * n + i];
+      d *= 0.5;
+#pragma unroll
+      for (int j = i + 1; j < n; j++) { T[i * n + j] -= T[j * n + i] * d; A[i * n + j] = 0; A[j * n + i] = 0; }
+      A[(i + 1) * n + i] = -b; A[i * n + i + 1] = -b;
+#pragma unroll
+      for (int j = i + 1; j < n; j++)
+#pragma unroll
+        for (int k = i + 1; k < j + 1; k++) A[j * n + k] -= T[i * n + j] * T[k * n + i] + T[i * n + k] * T[j * n + i];
+#pragma unroll
+      for (int k = 0; k < n; k++) {
+        double s = 0.0;
+#pragma unroll
+        for (int j = i + 1; j < n; j++) s += Q[k * n + j] * T[j * n + i];
+#pragma unroll
+        for (int j = i + 1; j < n; j++) Q[k * n + j] -= s * T[j * n + i];
+      }
+    }
+  }
+  A[(n - 2) * n + n - 1] = A[(n - 1) * n + n - 2];
+  double dg[n], sb[n - 1], sp[n - 1];
+#pragma unroll
+  for (int i = 0; i < n; i++) dg[i] = A[i * n + i];
+#pragma unroll
+  for (int i = 0; i < n - 1; i++) { sb[i] = A[(i + 1) * n + i]; sp[i] = A[i * n + i + 1]; }
+  spd_lit_qr<n, K, n>(dg, sb, sp, Q);
+#pragma unroll
+  for (int i = 0; i < n * n; i++) A[i] = 0.0;
+#pragma unroll
+  for (int i = 0; i < n; i++) {
+    const double v = dg[i];
+    if (v > 0) {
+#pragma unroll
+      for (int j = 0; j < n; j++) {
+        const double v2 = v * Q[j * n + i];
+#pragma unroll
+        for (int k = 0; k < n; k++) A[j * n + k] += v2 * Q[k * n + i];
+      }
+    }
+  }
+}
+
+// 9 x 9, 16 lanes per block in LDS (the group conventions of spd_clamp9_par: `on` uniform within a group, every group of the wave joins every spd_grp_sync).
+// sa: the block (row major, lower triangle read), st, sq: 81 doubles of scratch each (T and Q).  K: the sweep limit (20 at the contact and element blocks).
+// Householder step i: lane j > i forms T(i, j) and updates row j of A, lane k < 9 row k of Q (independent outputs; the scalars b, c, d are formed
+// redundantly on every lane from the same LDS values, in the same order).  QR sweeps: the Givens chain on the tridiagonal runs redundantly on every lane
+// (registers, identical values), lane r < 9 applies the rotations to row r of Q.  Rebuild: lane j accumulates row j over i in order.  On return sa holds
+// the projected block (groups with `on`; the block of a group without is left as it was).
+TSL_DEV void spd_literal9_coop(double* __restrict__ sa, double* __restrict__ st, double* __restrict__ sq, int l, bool on) {
+#pragma clang fp contract(off)
+  constexpr int n = 9, K = 20;
+  const bool row = l < n, wr = row && on;   // (wr: lanes that may write the block)
+  if (row) {
+#pragma unroll
+    for (int k = 0; k < n; k++) sq[l * n + k] = (k == l) ? 1.0 : 0.0;
+  }
+  for (int i = 0; i < n - 2; i++) {
+    double b = 0.0;
+    for (int j = i + 1; j < n; j++) b += sa[j * n + i] * sa[j * n + i];
+    b = sqrt(b);
+    const bool skip = b < 1e-6;
+    double c = 0.0, ti1 = 0.0;
+    if (!skip) {
+      if (sa[(i + 1) * n + i] < 0) b *= -1;
+      ti1 = sa[(i + 1) * n + i] + b;
+      c = ti1 * ti1;
+      for (int j = i + 2; j < n; j++) c += sa[j * n + i] * sa[j * n + i];
+      c = sqrt(2 / c);
+    }
+    spd_grp_sync();
+    // the Householder vector T(j, i), j > i
+    if (row && l > i) {
+      if (!skip) st[l * n + i] = ((l == i + 1) ? ti1 : sa[l * n + i]) * c;
+      else if (wr) sa[i * n + l] = 0;
+    }
+    spd_grp_sync();
+    if (!skip) {
+      double tij = 0.0;
+      if (row && l > i) {   // T(i, j) = (A p)_j from the lower triangle
+        for (int k = i + 1; k < l + 1; k++) tij += sa[l * n + k] * st[k * n + i];
+        for (int k = l + 1; k < n; k++) tij += sa[k * n + l] * st[k * n + i];
+        st[i * n + l] = tij;
+      }
+      spd_grp_sync();
+      double d = 0.0;
+      for (int j = i + 1; j < n; j++) d += st[i * n + j] * st[j * n + i];
+      d *= 0.5;
+      spd_grp_sync();
+      if (row && l > i) st[i * n + l] = tij - st[l * n + i] * d;
+      if (wr && l > i) {
+        sa[i * n + l] = (l == i + 1) ? -b : 0.0;
+        sa[l * n + i] = (l == i + 1) ? -b : 0.0;
+      }
+      spd_grp_sync();
+      if (wr && l > i) {   // row l of the lower triangle: A(l, k) -= T(i, l) T(k, i) + T(i, k) T(l, i), k = i+1..l
+        const double til = st[i * n + l], tli = st[l * n + i];
+        for (int k = i + 1; k < l + 1; k++) sa[l * n + k] -= til * st[k * n + i] + st[i * n + k] * tli;
+      }
+      if (row) {   // row l of Q
+        double s = 0.0;
+        for (int j = i + 1; j < n; j++) s += sq[l * n + j] * st[j * n + i];
+        for (int j = i + 1; j < n; j++) sq[l * n + j] -= s * st[j * n + i];
+      }
+    }
+    spd_grp_sync();
+  }
+  double dg[n], sb[n - 1], sp[n - 1], qr[n];
+#pragma unroll
+  for (int i = 0; i < n; i++) dg[i] = sa[i * n + i];
+#pragma unroll
+  for (int i = 0; i < n - 2; i++) { sb[i] = sa[(i + 1) * n + i]; sp[i] = sa[i * n + i + 1]; }
+  sb[n - 2] = sa[(n - 1) * n + n - 2]; sp[n - 2] = sb[n - 2];   // A(n-2, n-1) = A(n-1, n-2)
+  const int lr = row ? l : 0;
+#pragma unroll
+  for (int k = 0; k < n; k++) qr[k] = sq[lr * n + k];
+  spd_lit_qr<n, K, 1>(dg, sb, sp, qr);
+  spd_grp_sync();
+  if (row) {
+#pragma unroll
+    for (int k = 0; k < n; k++) sq[l * n + k] = qr[k];
+  }
+  spd_grp_sync();
+  double outr[n];
+#pragma unroll
+  for (int k = 0; k < n; k++) outr[k] = 0.0;
+#pragma unroll
+  for (int i = 0; i < n; i++) {
+    const double v = dg[i];
+    if (v > 0) {
+      const double v2 = v * sq[lr * n + i];
+#pragma unroll
+      for (int k = 0; k < n; k++) outr[k] += v2 * sq[k * n + i];
+    }
+  }
+  spd_grp_sync();
+  if (row && on) {
+#pragma unroll
+    for (int k = 0; k < n; k++) sa[l * n + k] = outr[k];
+  }
+  spd_grp_sync();
+}
+
 // 2x2 symmetric PSD projection (engine/linalg.py:5-12, closed form of the ti.svd based rule)
 TSL_DEV void spd_clamp2(double& a, double& b, double& d) {
   double tr = a + d, df = a - d;

@@ -440,6 +440,10 @@ extern "C" int tsl_set_param(tsl_ctx* c, const char* key, double v) {
   else if (k == "cg_maxit") c->cg_maxit = (int)v;
   else if (k == "newton_cap") c->newton_cap = (int)v;
   else if (k == "plastic") c->plastic = (int)v;
+  else if (k == "spd_literal") {
+    if (v != 0.0 && v != 1.0) return tsl_fail("tsl_set_param: spd_literal must be 0 or 1 (got %g)", v);
+    c->spd_literal = (int)v;
+  }
   else if (k == "contact") c->contact_enable = (v != 0.0);
   else if (k == "grid_h") c->grid_h = v;
   else if (k == "grid_extent") c->grid_extent = v;
@@ -634,6 +638,7 @@ static int assemble_enqueue(tsl_ctx* c, const double* pos, const double* prev, c
     const int nq = (int)c->h_cloth.size() * 9;
     hipLaunchKernelGGL(k_cloth_quirk, dim3(nblk(nq, 64)), dim3(64), 0, s, CA, (int)c->h_cloth.size(), pos, ref, c->quirk.p);
     if (spd == 2) hipLaunchKernelGGL((k_cloth_hess_face<true>), dim3(nblk(c->n_cface, 128)), dim3(128), 0, s, CA, pos, ref, c->quirk.p, spd, c->cg_frec.p);
+    else if (c->spd_literal && spd == 1) hipLaunchKernelGGL((k_cloth_hess_face<false, true>), dim3(nblk(c->n_cface, 128)), dim3(128), 0, s, CA, pos, ref, c->quirk.p, spd, c->cg_frec.p);
     else hipLaunchKernelGGL((k_cloth_hess_face<false>), dim3(nblk(c->n_cface, 128)), dim3(128), 0, s, CA, pos, ref, c->quirk.p, spd, c->cg_frec.p);
   }
   if (c->n_hinge) hipLaunchKernelGGL(k_cloth_hess_hinge, dim3(nblk(c->n_hinge, 256)), dim3(256), 0, s, CA, pos, c->cg_hrec.p);
@@ -692,8 +697,11 @@ static int assemble_enqueue_early(tsl_ctx* c, const double* pos, const double* p
     if (grad) { hipLaunchKernelGGL(k_tet_grad, dim3(nblk(c->n_tet, 256)), dim3(256), 0, stt, TA, pos); HIP_OK(hipEventRecord(c->ev_g2, stt)); }   // tet gradients staged
     // eigen-clamp of the element blocks warm-started from the previous assembly's eigenvectors ("tet_warm", on by default);
     // every 16th clamped assembly starts from the identity again (orthogonality of the accumulated rotations)
-    double* vws = (c->tet_warm && spd != 0) ? c->tet_V.p : (double*)nullptr;   // (allocated and counted by assemble())
-    hipLaunchKernelGGL(k_tet_hess_coop, dim3(nblk(c->n_tet, 16)), dim3(256), 0, stt, TA, pos, spd, vws, vws ? tet_warm_flag : 0, c->cg_trec.p);
+    // ("spd_literal": the reference's projector on the blocks as formed, no basis)
+    const bool lit = c->spd_literal && spd == 1;
+    double* vws = (c->tet_warm && spd != 0 && !lit) ? c->tet_V.p : (double*)nullptr;   // (allocated and counted by assemble())
+    if (lit) hipLaunchKernelGGL(k_tet_hess_coop<true>, dim3(nblk(c->n_tet, 16)), dim3(256), 0, stt, TA, pos, spd, vws, 0, c->cg_trec.p);
+    else hipLaunchKernelGGL(k_tet_hess_coop<false>, dim3(nblk(c->n_tet, 16)), dim3(256), 0, stt, TA, pos, spd, vws, vws ? tet_warm_flag : 0, c->cg_trec.p);
   }
   HIP_OK(hipMemsetAsync(c->vals_full.p, 0, c->vals_full.n * sizeof(double), s));
   if (c->n_cface) hipLaunchKernelGGL(k_cloth_normals, dim3(nblk(c->n_cface, 256)), dim3(256), 0, s, c->n_cface, pos, c->cf_f2v.p, c->norm_dir.p);
@@ -707,6 +715,7 @@ static int assemble_enqueue_early(tsl_ctx* c, const double* pos, const double* p
     const int nq = (int)c->h_cloth.size() * 9;
     hipLaunchKernelGGL(k_cloth_quirk, dim3(nblk(nq, 64)), dim3(64), 0, s, CA, (int)c->h_cloth.size(), pos, ref, c->quirk.p);
     if (spd == 2) hipLaunchKernelGGL((k_cloth_hess_face<true>), dim3(nblk(c->n_cface, 128)), dim3(128), 0, s, CA, pos, ref, c->quirk.p, spd, c->cg_frec.p);
+    else if (c->spd_literal && spd == 1) hipLaunchKernelGGL((k_cloth_hess_face<false, true>), dim3(nblk(c->n_cface, 128)), dim3(128), 0, s, CA, pos, ref, c->quirk.p, spd, c->cg_frec.p);
     else hipLaunchKernelGGL((k_cloth_hess_face<false>), dim3(nblk(c->n_cface, 128)), dim3(128), 0, s, CA, pos, ref, c->quirk.p, spd, c->cg_frec.p);
   }
   // element stream, second part (behind the normals and the mass diagonal).  Round 6: the element blocks of the bodies take 55 us since they are formed by 16 lanes
@@ -773,7 +782,7 @@ static int assemble(tsl_ctx* c, const double* pos, const double* prev, const dou
     if (c->cg_hrec.alloc((size_t)std::max(c->n_hinge, 1) * 16) | c->cg_frec.alloc((size_t)c->n_cface * 81)) return tsl_fail("out of device memory (cloth element records)");
   }
   int warm = 0;
-  if (c->n_tet > 0 && c->tet_warm && spd != 0) {
+  if (c->n_tet > 0 && c->tet_warm && spd != 0 && !(c->spd_literal && spd == 1)) {   // (the literal projector keeps no basis)
     if (c->tet_V.n < (size_t)81 * c->n_tet) {
       if (c->tet_V.alloc((size_t)81 * c->n_tet)) return tsl_fail("out of device memory (tet eigenvectors)");
       HIP_OK(hipMemsetAsync(c->tet_V.p, 0, c->tet_V.n * sizeof(double), s));   // "no basis yet" for every element (spd_clamp_warm checks the norm)
@@ -2732,7 +2741,9 @@ extern "C" int tsl_direct_counters(tsl_ctx* c, double* out, int32_t n) {
 extern "C" int tsl_spd_project(tsl_ctx* c, double* blocks, int32_t n, int32_t D) {
   Scope scope(c);
   if (D != 2 && D != 3 && D != 9) return tsl_fail("tsl_spd_project: D must be 2, 3 or 9");
-  hipLaunchKernelGGL(k_spd_batch, dim3(nblk(n, 64)), dim3(64), 0, c->stream, blocks, n, D);
+  if (c->spd_literal && D == 3) hipLaunchKernelGGL(k_spd_batch_literal, dim3(nblk(n, 256)), dim3(256), 0, c->stream, blocks, n, D);
+  else if (c->spd_literal && D == 9) hipLaunchKernelGGL(k_spd_batch_literal, dim3(nblk((long)n * 16, 256)), dim3(256), 0, c->stream, blocks, n, D);
+  else hipLaunchKernelGGL(k_spd_batch, dim3(nblk(n, 64)), dim3(64), 0, c->stream, blocks, n, D);
   HIP_OK(hipStreamSynchronize(c->stream));
   return 0;
 }

@@ -51,6 +51,7 @@ class _SystemMatrix:
 class BaseScene:
     _newton_cap = 1000   # BaseScene.py:1342
     _plastic = 0         # base timestep_finish does not update ref angles (:1321-1325)
+    spd_literal = False  # True: the forward projections run the reference's own projector (linalg.py:15-148) instead of the converged eigen-clamp
 
     def __init__(self, cloth_size=0.1, dt=5e-3, enable_gripper=True, device="cuda:0"):
         # BaseScene.py:31-60
@@ -337,6 +338,7 @@ class BaseScene:
                 self._ctx.set_param("grid_extent", self.grid_extent)
             self._ctx.set_param("newton_cap", self._newton_cap)
             self._ctx.set_param("plastic", self._plastic)
+            self._ctx.set_param("spd_literal", int(bool(self.spd_literal)))
             self._ctx.set_ext_force(self._ext_force_array())
             self._dirty.clear()
         if self._dirty:
@@ -356,6 +358,13 @@ class BaseScene:
             self._ctx.set_param(key, value)
 
     # ------------------------------------------------------------------ frozen / external force
+    def set_spd_literal(self, on):
+        """Select the projector of the forward assembly: True the reference's Householder + QR sweeps (SPD_Projector, linalg.py:15-148), False
+        (default) the converged eigen-clamp.  Applies to a live engine context at once and to one created later."""
+        self.spd_literal = bool(on)
+        if self._ctx is not None:
+            self._ctx.set_param("spd_literal", int(self.spd_literal))
+
     def set_frozen_kernel(self):
         # BaseScene.py:1445-1463
         fr = self.frozen.t.view(-1, 3)
