@@ -359,7 +359,7 @@ static int group_create(tsl_ctx* const* ctxs, int n, tsl_group** out) {
   gd.merged = true; gd.enable = 1; gd.device = dev; gd.flow = d0.flow; gd.small_rounds = d0.small_rounds * n; gd.xcd_map = d0.xcd_map; gd.gemv_wide_below = d0.gemv_wide_below;
   gd.g32_below = d0.g32_below; gd.piv_tol = d0.piv_tol; gd.prezero = d0.prezero;
   gd.static_ready = true;
-  if (gd.bad.alloc(8 + 4 * DS_BADLOG)) return -1;
+  if (gd.bad.alloc(DS_BAD_INTS)) return -1;
   HIP_OK(hipFuncSetAttribute((const void*)k_ds_inv_small, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ds_small_lds(DS_SMALL)));
   HIP_OK(hipEventCreateWithFlags(&G->ev_g, hipEventDisableTiming));
   G->ev_m.assign(n, nullptr);

@@ -280,7 +280,7 @@ static int direct_static(tsl_ctx* c) {
     for (int k = 0; k < (int)c->h_rows[v].size(); k++) c2s[d.row_ptr[v] + k] = (int)(((long)c->h_slice_off[s] + 64L * k) * 9 + lane);
   }
   d.h_c2s = c2s;   // (SELL address of every CSR block: the plan uploads bake it into their level-ordered lists)
-  if (d.bad.alloc(8 + 4 * DS_BADLOG + 8)) return -1;   // (+ 8: the note of a dataflow launch that gave up, ds_flow_poll)
+  if (d.bad.alloc(DS_BAD_INTS)) return -1;
   HIP_OK(hipFuncSetAttribute((const void*)k_ds_inv_small, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ds_small_lds(DS_SMALL)));
   { hipDeviceProp_t prop;   // compute units of THIS device: rounds of the LDS kernel, remainder rule of the batches (was a constant 256)
     if (hipGetDeviceProperties(&prop, d.device) == hipSuccess && prop.multiProcessorCount > 0) d.plan.n_cu = prop.multiProcessorCount; else (void)hipGetLastError(); }

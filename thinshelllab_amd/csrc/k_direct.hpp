@@ -139,6 +139,8 @@ __global__ void __launch_bounds__(256) k_ds_assemble_contacts_level(int g0, int 
 // call it; the tile is complete in LDS on return (the function ends with a barrier).
 #define DS_PB 4
 #define DS_BADLOG 64
+#define DS_BAD_NOTE (8 + 4 * DS_BADLOG)   // bad[]: 8 counters, the pivot log (4 ints per entry), then the 8-int note of a dataflow launch that gave up (ds_flow_poll)
+#define DS_BAD_INTS (DS_BAD_NOTE + 8)
 #define DS_REDO 6   // bad[DS_REDO]: tiles of the last factorisation that went through the guarded form
 #define DS_CLS(f) ((f).pp > 512 ? 3 : ((f).pp > 128 ? 2 : 1))
 TSL_DEV double ds_rcp(double x) {
@@ -664,7 +666,7 @@ TSL_DEV void ds_flow_poll(const int* flag, int epoch, int* abort_w, int* s_dead)
     if (v == epoch) break;
     if (++spins >= DS_FLOW_SPINS) {
       if (atomicCAS(abort_w, 0, 1) == 0) {   // the first to give up leaves a note for the host's report: workgroups of this factorisation's dataflow launches that had started, this launch's grid, who waited for which flag
-        int* note = abort_w - DS_FLOW_ABORT + 8 + 4 * DS_BADLOG;
+        int* note = abort_w - DS_FLOW_ABORT + DS_BAD_NOTE;
         note[0] = __hip_atomic_load(abort_w - DS_FLOW_ABORT + DS_FLOW_ARRIVE, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); note[1] = (int)gridDim.x; note[2] = (int)blockIdx.x; note[3] = v; note[4] = epoch;
       }
       *s_dead = 1; return;
