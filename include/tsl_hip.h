@@ -102,11 +102,12 @@ int tsl_ctx_create(const tsl_scene_desc* desc, tsl_ctx** out);
 void tsl_ctx_destroy(tsl_ctx* ctx);
 int tsl_set_stream(tsl_ctx* ctx, void* hip_stream);
 
-/* 0-d field writes of the reference and the engine's own switches (40 keys + three patterns; an unknown key is an error).
+/* 0-d field writes of the reference and the engine's own switches (41 keys + three patterns; an unknown key is an error).
  *  Scene (trajopt_folding.py:50,66; Scene_folding.py:30-31; geometry.py:8-19; geometry_self.py:166-230):
  *   "cloth<i>.Kb|Kl|Ka|k_angle", "elastic<i>.mu|lam|alpha", "mu_cloth_elastic", "mu_cloth_cloth", "k_contact", "eps_contact", "eps_v", "damping",
  *   "newton_cap", "plastic", "contact" (0: no detection in tsl_step), "grid_h", "grid_extent" (broad-phase cell and box), "self_contact<body>"
- *   (0 / 1: the body's vertices are also projected onto its own triangles), "adj_clamp", "adj_clamp_angleref" (the clamping of analytic_grad_single:
+ *   (0 / 1: the body's vertices are also projected onto its own triangles), "contact_ee" (0 default: vertex-triangle contact only, as the reference;
+ *   1: edge-edge constraints between the surface edges of different bodies are appended behind the vertex-triangle ones, see tsl_contact_counts), "adj_clamp", "adj_clamp_angleref" (the clamping of analytic_grad_single:
  *   1000, on; of analytic_grad_system: 1, off), "adj_spd_pc" (adjoint solves of the iterative hierarchy preconditioned from the projected assembly).
  *  Linear solve (no reference counterpart: the reference calls cupyx spsolve):
  *   "cg_tol" (1e-10), "cg_maxit", "direct" (-1 auto: cloth grids of >= 1024 cells / 0 iterative hierarchy only / 1 always: multifrontal LU on the GPU),
@@ -162,6 +163,11 @@ int tsl_step(tsl_ctx* ctx, double* pos_dev, double* prev_pos_dev, double* vel_de
  * proj_flag / proj_dir persist inside the context between calls (geometry.py:210-219). */
 int tsl_contact_detect(tsl_ctx* ctx, const double* pos_dev, const double* prev_pos_dev, int32_t* nc_host);
 int tsl_contact_reset(tsl_ctx* ctx); /* BaseScene.reset: proj_flag.fill(0) (BaseScene.py:268) */
+/* {vertex-triangle, edge-edge} constraints of the last detection (their sum is tsl_step_stats.nc); the edge-edge ones ("contact_ee" = 1) are the
+ * slots [out2[0], out2[0] + out2[1]) of the list.  Such a slot has idx = (b0, b1, a0, a1): target edge (b0, b1), query edge (a0, a1) in the order that
+ * makes the signed line distance positive on the side the query edge was on at detection; w = (s, t, 0) with a(s) = (1 - s) x_a0 + s x_a1 and
+ * b(t) = (1 - t) x_b0 + t x_b1 the closest points at detection; friction acts on a(s) - b(t) - dx0. */
+int tsl_contact_counts(tsl_ctx* ctx, int32_t* out2_host);
 
 /* Cloth.update_ref_angle (model_fold_offset.py:176-185) for every cloth. */
 int tsl_update_ref_angle(tsl_ctx* ctx, const double* pos_dev, double* ref_angle_dev);
@@ -188,7 +194,8 @@ int tsl_elastic_force(tsl_ctx* ctx, const double* pos_dev, double* force_dev);
 int tsl_param_grad(tsl_ctx* ctx, const double* pos_dev, const double* ref_angle_dev, double* out_host);
 
 /* Scene_sliding.contact_energy_backprop_friction (Scene_sliding.py:139-176): contribution of the last tsl_adjoint_step to
- * d(loss)/d(mu_cloth_cloth), summed over the constraints of the pairs that use that parameter. pos = tape state x_s. */
+ * d(loss)/d(mu_cloth_cloth), summed over the constraints of the pairs that use that parameter. pos = tape state x_s.
+ * Fails (< 0) while edge-edge constraints ("contact_ee" = 1) of such pairs are present: their term is not implemented. */
 int tsl_friction_grad(tsl_ctx* ctx, const double* pos_dev, double* out_host);
 
 /* Introspection used by the parity tests (tests/ only): assembled matrix as BSR on the host. */

@@ -141,6 +141,12 @@ class TslContext:
         check(self.L.tsl_contact_detect(self.h, _ptr(pos), _ptr(prev_pos), C.byref(nc)), "tsl_contact_detect")
         return nc.value
 
+    def contact_counts(self):
+        """(vertex-triangle, edge-edge) constraints of the last detection; the edge-edge ones ("contact_ee" = 1) follow the others in the list"""
+        out = (C.c_int32 * 2)()
+        check(self.L.tsl_contact_counts(self.h, out), "tsl_contact_counts")
+        return int(out[0]), int(out[1])
+
     def contact_reset(self):
         check(self.L.tsl_contact_reset(self.h), "tsl_contact_reset")
 

@@ -362,7 +362,9 @@ __global__ void k_contact_energy(int nc, ContactArgs A, const double* __restrict
 TSL_DEV d3 c_unit(int a) { return d3(a == 0 ? 1.0 : 0.0, a == 1 ? 1.0 : 0.0, a == 2 ? 1.0 : 0.0); }
 TSL_DEV double c_comp(const d3& v, int a) { return a == 0 ? v.x : (a == 1 ? v.y : v.z); }
 // LIT ("spd_literal" = 1, spd 1 only): the normal block is projected by the reference's own projector (spd_literal9_coop, K = 20; a third LDS array for T).
-template <bool LIT = false>
+// EE: an edge-edge constraint (see k_ee_build): q = (x1 - x0, x3 - x2, x2 - x0), friction weights (-(1 - t), -t, 1 - s, s) over (x0..x3) with
+// (s, t) = (w[0], w[1]); the q-space normal block, its projection and the friction block are the same code, only the 9 -> 12 row map differs.
+template <bool LIT = false, bool EE = false>
 __global__ void __launch_bounds__(256)
 k_contact_assemble_coop(int nc, ContactArgs A, const double* __restrict__ pos, int spd, double* __restrict__ Hfull, double* __restrict__ cg) {
   const int l = threadIdx.x & 15;
@@ -372,7 +374,7 @@ k_contact_assemble_coop(int nc, ContactArgs A, const double* __restrict__ pos, i
   int id[4];
   for (int k = 0; k < 4; k++) id[k] = A.idx[4 * ci + k];
   const d3 x0 = ld3(pos, id[0]), xa = ld3(pos, id[1]), xb = ld3(pos, id[2]), xp = ld3(pos, id[3]);
-  const d3 a = xa - x0, b = xb - x0, p = xp - x0;
+  const d3 a = xa - x0, b = EE ? xp - xb : xb - x0, p = EE ? xb - x0 : xp - x0;
   const d3 cr = cross(a, b);
   const double D = dot(cr, p), C = norm(cr);
   const bool active = D / C < A.eps_contact;
@@ -440,10 +442,25 @@ k_contact_assemble_coop(int nc, ContactArgs A, const double* __restrict__ pos, i
     }
   }
   // 12 x 12 block: lane l < 9 -> row 3 + l; lanes 9..11 -> rows 0..2 of vertex 0 (minus the sums over the three other vertices)
+  // (EE: lane l < 12 -> row l, vertex u = l / 3; vertex u is sum_i M[u][i] q_i with M = (-1, 0, -1), (1, 0, 0), (0, -1, 1), (0, 1, 0))
   double out[12];
   double gout = 0.0;
-  const int axis = l < 9 ? l % 3 : l - 9;
-  {
+  const int axis = EE ? l % 3 : (l < 9 ? l % 3 : l - 9);
+  if constexpr (EE) {
+    const int u = l / 3;
+    const double m0 = u == 0 ? -1.0 : (u == 1 ? 1.0 : 0.0), m1 = u == 2 ? -1.0 : (u == 3 ? 1.0 : 0.0), m2 = u == 0 ? -1.0 : (u == 2 ? 1.0 : 0.0);
+    double r9[9];   // row (u, axis) of M^T H9 in q columns
+#pragma unroll
+    for (int k = 0; k < 9; k++) r9[k] = m0 * __shfl(h[k], axis, 16) + m1 * __shfl(h[k], 3 + axis, 16) + m2 * __shfl(h[k], 6 + axis, 16);
+    gout = m0 * __shfl(g9, axis, 16) + m1 * __shfl(g9, 3 + axis, 16) + m2 * __shfl(g9, 6 + axis, 16);
+#pragma unroll
+    for (int j2 = 0; j2 < 3; j2++) {
+      out[j2] = -r9[j2] - r9[6 + j2];
+      out[3 + j2] = r9[j2];
+      out[6 + j2] = r9[6 + j2] - r9[3 + j2];
+      out[9 + j2] = r9[3 + j2];
+    }
+  } else {
     double s0[9], sg = 0.0;   // sums over the rows l', l' % 3 == axis (for the vertex-0 rows)
 #pragma unroll
     for (int k = 0; k < 9; k++) {
@@ -473,16 +490,16 @@ k_contact_assemble_coop(int nc, ContactArgs A, const double* __restrict__ pos, i
     const double w[3] = {A.w[3 * ci], A.w[3 * ci + 1], A.w[3 * ci + 2]};
     const double kf = A.k[ci];
     const double* T = A.T + 6 * (size_t)ci;
-    const d3 x_c = x0 * w[0] + xa * w[1] + xb * w[2];
-    const d3 dx = xp - x_c - ld3(A.dx0, ci);
+    const d3 x_c = EE ? x0 * (1.0 - w[1]) + xa * w[1] : x0 * w[0] + xa * w[1] + xb * w[2];
+    const d3 dx = (EE ? xb * (1.0 - w[0]) + xp * w[0] : xp) - x_c - ld3(A.dx0, ci);
     const double u[2] = {T[0] * dx.x + T[1] * dx.y + T[2] * dx.z, T[3] * dx.x + T[4] * dx.y + T[5] * dx.z};
     const double r = sqrt(u[0] * u[0] + u[1] * u[1]);
     const double f1 = fr_f1(r, A.eps_vh), f2 = fr_f2(r, A.eps_vh);
     double ha = f1, hb = 0, hd = f1;
     if (r > 1e-9) { ha += f2 * u[0] * u[0] / r; hb += f2 * u[0] * u[1] / r; hd += f2 * u[1] * u[1] / r; }
     if (spd) spd_clamp2(ha, hb, hd);
-    const double w1[4] = {-w[0], -w[1], -w[2], 1.0};
-    const int i1 = l < 9 ? 1 + l / 3 : 0;
+    const double w1[4] = {EE ? w[1] - 1.0 : -w[0], -w[1], EE ? 1.0 - w[0] : -w[2], EE ? w[0] : 1.0};
+    const int i1 = EE ? l / 3 : (l < 9 ? 1 + l / 3 : 0);
     const double wi = i1 == 0 ? w1[0] : (i1 == 1 ? w1[1] : (i1 == 2 ? w1[2] : w1[3]));
     const double Ta = T[axis], Tb = T[3 + axis];
     gout += wi * kf * f1 * (u[0] * Ta + u[1] * Tb);
@@ -493,13 +510,12 @@ k_contact_assemble_coop(int nc, ContactArgs A, const double* __restrict__ pos, i
         out[i2 * 3 + j2] += wi * w1[i2] * kf * (Ta * (ha * T[j2] + hb * T[3 + j2]) + Tb * (hb * T[j2] + hd * T[3 + j2]));
   }
   if (!valid || l >= 12) return;
-  const int rowi = l < 9 ? 3 + l : l - 9;
+  const int rowi = EE ? l : (l < 9 ? 3 + l : l - 9);
   if (cg) cg[12 * (size_t)ci + rowi] = gout;   // (per-constraint gradients, summed per vertex by k_contact_row_gather)
   double* dst = Hfull + 144 * (size_t)ci + 12 * rowi;
 #pragma unroll
   for (int k = 0; k < 12; k++) dst[k] = out[k];
 }
-
 // masked copy of the per-constraint blocks (add_H frozen rule, BaseScene.py:399-405)
 // One thread per ENTRY (nc x 144): the one-thread-per-constraint version walked 144 dependent global accesses per lane and took
 // 96 us at 135 constraints on the contact stream of an assembly.
@@ -739,8 +755,288 @@ __global__ void __launch_bounds__(256) k_spd_batch_literal(double* blocks, int n
   if (valid) for (int q = l; q < 81; q += 16) blocks[b0 + q] = sA[g][q];
 }
 
+// ------------------------------------------------------------------------------------------------ edge-edge contact ("contact_ee" = 1)
+// The reference has vertex-triangle contact only (geometry.py:23-229).  Two surface edges whose lines pass closer than eps_contact, with the
+// closest points strictly inside both edges, get a 4-vertex constraint idx = (b0, b1, a0, a1): target edge (b0, b1), query edge (a0, a1).  In the
+// relative coordinates of the vertex-triangle term, q = (x1 - x0, x3 - x2, x2 - x0), d = (p1 x p2) . p / |p1 x p2| is the signed distance between
+// the two lines, so its gradient, Hessian and 9 x 9 clamp are the vertex-triangle ones (k_contact_assemble_coop<LIT, true>).  The query edge's vertex
+// order encodes the side it was on at detection (d > 0 there).  c_w = (s, t, 0): a(s) = (1 - s) x2 + s x3 on the query edge, b(t) = (1 - t) x0 + t x1
+// on the target edge; friction acts on a(s) - b(t) - dx0, weights (-(1 - t), -t, 1 - s, s).
+#define TSL_EE_SIN_MIN 1e-2   // pairs with sin(angle between the edges) below this are left out (near-parallel: the line distance is ill-conditioned)
+
+// midpoint cell of every edge of one target body + active box + bucket histogram + the body's longest edge (bits of a non-negative double: ordered as integers)
+__global__ void k_ee_grid_keys(GridArgs G, int e_start, int ne, const int* __restrict__ edges, const double* __restrict__ pos, int* __restrict__ key,
+                               int* __restrict__ range, int hshift, int* __restrict__ cnt, unsigned long long* __restrict__ lmax) {
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= ne) return;
+  const int e = e_start + t;
+  const d3 x0 = ld3(pos, edges[2 * e]), x1 = ld3(pos, edges[2 * e + 1]);
+  int id[3];
+  grid_idx3(G, 0.5 * (x0 + x1), id);
+  const int cell = (id[0] * G.n + id[1]) * G.n + id[2];
+  key[t] = cell;
+  atomicAdd(&cnt[grid_bucket(cell, hshift)], 1);
+  for (int a = 0; a < 3; a++) { atomicMin(&range[a], id[a]); atomicMax(&range[3 + a], id[a]); }
+  atomicMax(lmax, (unsigned long long)__double_as_longlong(norm(x1 - x0)));
+}
+
+// the qualifying test of a (query edge a, target edge b) pair: closest points of the two lines strictly inside both edges, not near-parallel,
+// distance below eps.  s on a, t on b; D = ((b1 - b0) x (a1 - a0)) . (a0 - b0) (its sign is the side of a).
+TSL_DEV bool ee_qualifies(const d3& a0, const d3& a1, const d3& b0, const d3& b1, double eps, double& s, double& t, double& D, double& C) {
+  const d3 d1 = a1 - a0, d2 = b1 - b0, r = a0 - b0;
+  const double aa = dot(d1, d1), ee = dot(d2, d2), ab = dot(d1, d2), c = dot(d1, r), f = dot(d2, r);
+  const d3 cr = cross(d2, d1);
+  const double cc = dot(cr, cr);
+  if (!(cc >= TSL_EE_SIN_MIN * TSL_EE_SIN_MIN * aa * ee) || !(cc > 0.0)) return false;
+  s = (ab * f - c * ee) / cc;
+  t = (aa * f - ab * c) / cc;
+  if (!(s > 0.0 && s < 1.0 && t > 0.0 && t < 1.0)) return false;
+  C = sqrt(cc);
+  D = dot(cr, r);
+  return fabs(D) / C < eps;
+}
+
+// Broad + narrow phase of one contact descriptor: query edge qlist[i] against the edges of one target body, hashed by midpoint cell (k_ee_grid_keys,
+// k_bucket_scatter, k_bucket_rank).  The query scans the cells that cover its box grown by eps + half the target's longest edge: every edge that can
+// qualify has its midpoint there, whatever the edge length against grid_h.  G lanes per query take a cell's candidates in chunks of G (as k_project_pair).
+// MODE 0: number of qualifying target edges per query -> qcnt; MODE 1: their ids at cand[qscan[i] ...] in scan order (k_ee_build sorts them).
+template <int G, int MODE>
+__global__ void __launch_bounds__(256)
+k_ee_query(GridArgs Gr, int nq, const int* __restrict__ qlist, int hshift, const int* __restrict__ bptr, const int* __restrict__ skey, const int* __restrict__ sval,
+           const int* __restrict__ range, const int* __restrict__ edges, const double* __restrict__ pos, const unsigned long long* __restrict__ lmax, double eps,
+           int* __restrict__ qcnt, const int* __restrict__ qscan, int* __restrict__ cand, int cand_cap) {
+  const int qi = (int)((blockIdx.x * (size_t)blockDim.x + threadIdx.x) / G);
+  const int g = threadIdx.x & (G - 1);
+  const bool live = qi < nq;
+  const int eq = live ? qlist[qi] : 0;
+  const int a0 = live ? edges[2 * eq] : 0, a1 = live ? edges[2 * eq + 1] : 0;
+  const d3 xa0 = live ? ld3(pos, a0) : d3(), xa1 = live ? ld3(pos, a1) : d3();
+  const double grow = eps + 0.5 * __longlong_as_double((long long)*lmax);
+  const d3 lo(fmin(xa0.x, xa1.x) - grow, fmin(xa0.y, xa1.y) - grow, fmin(xa0.z, xa1.z) - grow);
+  const d3 hi(fmax(xa0.x, xa1.x) + grow, fmax(xa0.y, xa1.y) + grow, fmax(xa0.z, xa1.z) + grow);
+  int q0[3], q1[3], r0[3], r1[3];
+  grid_idx3(Gr, lo, q0);
+  grid_idx3(Gr, hi, q1);
+  for (int a = 0; a < 3; a++) { r0[a] = max(q0[a], range[a]); r1[a] = min(q1[a], range[3 + a]) + 1; }
+  const int gbase = (threadIdx.x & 63) & ~(G - 1);
+  const unsigned long long gbits = G == 64 ? ~0ull : ((1ull << G) - 1);
+  const int base = (MODE == 1 && live) ? qscan[qi] : 0;
+  int cnt = 0;   // uniform in the group
+  if (live)
+    for (int gi = r0[0]; gi < r1[0]; gi++)
+      for (int gj = r0[1]; gj < r1[1]; gj++)
+        for (int gk = r0[2]; gk < r1[2]; gk++) {
+          const int cell = (gi * Gr.n + gj) * Gr.n + gk;
+          const int bk = grid_bucket(cell, hshift);
+          const int s0 = bptr[bk], s1 = bptr[bk + 1];
+          for (int sb = s0; sb < s1; sb += G) {
+            const int sidx = sb + g;
+            bool ok = false;
+            int et = 0;
+            if (sidx < s1 && skey[sidx] == cell) {
+              et = sval[sidx];
+              const int b0 = edges[2 * et], b1 = edges[2 * et + 1];
+              if (b0 != a0 && b0 != a1 && b1 != a0 && b1 != a1) {
+                double s, t, D, C;
+                ok = ee_qualifies(xa0, xa1, ld3(pos, b0), ld3(pos, b1), eps, s, t, D, C);
+              }
+            }
+            const unsigned long long m = (__ballot(ok) >> gbase) & gbits;
+            if (MODE == 1 && ok) {
+              const int k = cnt + __popcll(m & ((1ull << g) - 1));
+              if (base + k < cand_cap) cand[base + k] = et;
+            }
+            cnt += __popcll(m);
+          }
+        }
+  if (MODE == 0 && live && g == 0) qcnt[qi] = cnt;
+}
+
+// constraint records of one descriptor, one thread per query edge: its candidates in ascending target edge, written at nc_vf + qscan[i] + rank
+// (the list order: descriptor, query edge, target edge -- no atomics).  A query whose slots would pass max_nc writes nothing (the host reports the cap).
+__global__ void k_ee_build(int nq, int qoff, const int* __restrict__ qlist, const int* __restrict__ edges, const int* __restrict__ qscan, int* __restrict__ cand,
+                           const int* __restrict__ nc_vf, int max_nc, double mu, int kind, double k_contact, double eps_contact, const double* __restrict__ pos,
+                           const double* __restrict__ prev, int* __restrict__ c_idx, double* __restrict__ c_w, double* __restrict__ c_k, double* __restrict__ c_mu,
+                           double* __restrict__ c_dx0, double* __restrict__ c_T, double* __restrict__ c_n, int* __restrict__ c_kind) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= nq) return;
+  const int j0 = qscan[qoff + i], j1 = qscan[qoff + i + 1], nvf = *nc_vf;
+  if (j1 == j0 || nvf + j1 > max_nc) return;
+  for (int j = j0 + 1; j < j1; j++) {   // insertion sort: a query edge has a handful of candidates
+    const int v = cand[j];
+    int k = j - 1;
+    while (k >= j0 && cand[k] > v) { cand[k + 1] = cand[k]; k--; }
+    cand[k + 1] = v;
+  }
+  const int eq = qlist[i];
+  int a0 = edges[2 * eq], a1 = edges[2 * eq + 1];
+  for (int j = j0; j < j1; j++) {
+    const int et = cand[j];
+    const int b0 = edges[2 * et], b1 = edges[2 * et + 1];
+    const d3 xb0 = ld3(pos, b0), xb1 = ld3(pos, b1);
+    double s = 0, t = 0, D = 0, C = 1;
+    (void)ee_qualifies(ld3(pos, a0), ld3(pos, a1), xb0, xb1, eps_contact, s, t, D, C);
+    int q0 = a0, q1 = a1;
+    if (D < 0) { q0 = a1; q1 = a0; s = 1.0 - s; D = -D; }   // the query edge's side at detection: d > 0 there
+    const d3 n_c = cross(xb1 - xb0, ld3(pos, q1) - ld3(pos, q0)) / C;
+    const double gap = D / C;
+    const int c = nvf + j;
+    const double cforce = k_contact * (gap - eps_contact);
+    c_idx[4 * c] = b0; c_idx[4 * c + 1] = b1; c_idx[4 * c + 2] = q0; c_idx[4 * c + 3] = q1;
+    c_w[3 * c] = s; c_w[3 * c + 1] = t; c_w[3 * c + 2] = 0.0;
+    c_k[c] = -mu * cforce;
+    c_mu[c] = mu;
+    c_kind[c] = kind;
+    st3(c_dx0, c, (ld3(prev, q0) * (1.0 - s) + ld3(prev, q1) * s) - (ld3(prev, b0) * (1.0 - t) + ld3(prev, b1) * t));
+    d3 t1 = (fabs(n_c.x) < 0.5) ? d3(n_c.x, n_c.z, -n_c.y) : d3(n_c.y, -n_c.x, n_c.z);
+    const d3 t2 = cross(n_c, t1);
+    t1 = cross(n_c, t2);
+    c_T[6 * c] = t1.x; c_T[6 * c + 1] = t1.y; c_T[6 * c + 2] = t1.z; c_T[6 * c + 3] = t2.x; c_T[6 * c + 4] = t2.y; c_T[6 * c + 5] = t2.z;
+    st3(c_n, c, n_c);
+  }
+}
+
+// friction weights over (x0..x3) and the slip a(s) - b(t) - dx0 of an edge-edge slot
+TSL_DEV d3 ee_slip(const ContactArgs& A, int ci, const d3* x, double w1[4]) {
+  const double s = A.w[3 * ci], t = A.w[3 * ci + 1];
+  w1[0] = t - 1.0; w1[1] = -t; w1[2] = 1.0 - s; w1[3] = s;
+  return (x[2] * (1.0 - s) + x[3] * s) - (x[0] * (1.0 - t) + x[1] * t) - ld3(A.dx0, ci);
+}
+
+// k_contact_energy over edge-edge slots (A starts at slot nc_vf)
+__global__ void k_ee_energy(int nc, ContactArgs A, const double* __restrict__ pos, double* __restrict__ e_part) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  double e = 0;
+  if (i < nc) {
+    d3 x[4];
+    for (int k = 0; k < 4; k++) x[k] = ld3(pos, A.idx[4 * i + k]);
+    const d3 cr = cross(x[1] - x[0], x[3] - x[2]);
+    const double d = dot(cr, x[2] - x[0]) / norm(cr);
+    if (d < A.eps_contact) e += 0.5 * A.k_contact * (d - A.eps_contact) * (d - A.eps_contact);
+    double w1[4];
+    const d3 dx = ee_slip(A, i, x, w1);
+    const double* T = A.T + 6 * (size_t)i;
+    const double u0 = T[0] * dx.x + T[1] * dx.y + T[2] * dx.z, u1 = T[3] * dx.x + T[4] * dx.y + T[5] * dx.z;
+    e += A.k[i] * fr_f0(sqrt(u0 * u0 + u1 * u1), A.eps_vh);
+  }
+  e = wave_sum(e);
+  if ((threadIdx.x & 63) == 0) e_part[blockIdx.x] = e;
+}
+
+// k_contact_backprop over edge-edge slots (A and cg start at slot nc_vf): the same friction-lag adjoint with wp = -w1
+__global__ void k_ee_backprop(int nc, ContactArgs A, const double* __restrict__ pos, const double* __restrict__ z, double* __restrict__ cg) {
+  const int ci = blockIdx.x * blockDim.x + threadIdx.x;
+  if (ci >= nc) return;
+  int id[4];
+  d3 x[4];
+  for (int k = 0; k < 4; k++) { id[k] = A.idx[4 * ci + k]; x[k] = ld3(pos, id[k]); }
+  double w1[4];
+  const d3 dx = ee_slip(A, ci, x, w1);
+  const double kf = A.k[ci];
+  const double* T = A.T + 6 * (size_t)ci;
+  const double u[2] = {T[0] * dx.x + T[1] * dx.y + T[2] * dx.z, T[3] * dx.x + T[4] * dx.y + T[5] * dx.z};
+  const double r = sqrt(u[0] * u[0] + u[1] * u[1]);
+  const double f1 = fr_f1(r, A.eps_vh), f2 = fr_f2(r, A.eps_vh);
+  const double pressure = kf / A.mu[ci];
+  double g1[3];
+  for (int j = 0; j < 3; j++) g1[j] = kf * f1 * (u[0] * T[j] + u[1] * T[3 + j]);
+  const d3 n_c = ld3(A.n, ci);
+  double acc[12];
+  for (int k = 0; k < 12; k++) acc[k] = 0;
+  double zv[12];
+  for (int k = 0; k < 4; k++) for (int j = 0; j < 3; j++) zv[3 * k + j] = z[3 * (size_t)id[k] + j];
+  {
+    double s = 0;
+    for (int i1 = 0; i1 < 4; i1++)
+      for (int j1 = 0; j1 < 3; j1++) s += zv[3 * i1 + j1] * (-w1[i1] * g1[j1] / pressure);
+    const double nn[3] = {n_c.x, n_c.y, n_c.z};
+    for (int i2 = 0; i2 < 4; i2++)
+      for (int j2 = 0; j2 < 3; j2++) acc[3 * i2 + j2] += s * -w1[i2] * nn[j2] * A.k_contact;
+  }
+  {
+    double ha = f1, hb = 0, hd = f1;
+    if (r > 1e-9) { ha += f2 * u[0] * u[0] / r; hb += f2 * u[0] * u[1] / r; hd += f2 * u[1] * u[1] / r; }
+    double h1[9];
+    for (int a = 0; a < 3; a++)
+      for (int b = 0; b < 3; b++) h1[a * 3 + b] = kf * (T[a] * (ha * T[b] + hb * T[3 + b]) + T[3 + a] * (hb * T[b] + hd * T[3 + b]));
+    for (int i1 = 0; i1 < 4; i1++)
+      for (int i2 = 0; i2 < 4; i2++)
+        for (int j1 = 0; j1 < 3; j1++)
+          for (int j2 = 0; j2 < 3; j2++) acc[3 * i2 + j2] += zv[3 * i1 + j1] * w1[i1] * w1[i2] * h1[j1 * 3 + j2];
+  }
+  for (int k = 0; k < 12; k++) cg[12 * (size_t)ci + k] = acc[k];
+}
+
 // ------------------------------------------------------------------------------------------------ host side
 static inline int cnblk(long n, int b) { return (int)((n + b - 1) / b); }
+
+// edge-edge tables (host, once): the unique surface edges of every body in ascending (v0, v1), and per contact descriptor the query edges -- surface
+// edges with both vertices in [v_start, v_end) of every other body whose pair with b_idx no earlier descriptor took (BaseScene.contact_pairs lists both
+// directions; a range over several bodies is split by body), ascending (v0, v1).  No self pairs.
+static int ee_tables(tsl_ctx* c, const std::vector<int>& faces) {
+  const int NF = (int)(faces.size() / 3);
+  std::vector<int> ed;
+  c->h_ee_e0.assign(1, 0);
+  for (const auto& b : c->h_bodies) {
+    std::vector<std::pair<int, int>> es;
+    for (int f = std::max(b.f_start, 0); f < std::min(b.f_end, NF); f++)
+      for (int k = 0; k < 3; k++) {
+        const int u = faces[3 * f + k], v = faces[3 * f + (k + 1) % 3];
+        es.push_back({std::min(u, v), std::max(u, v)});
+      }
+    std::sort(es.begin(), es.end());
+    es.erase(std::unique(es.begin(), es.end()), es.end());
+    for (auto& e : es) { ed.push_back(e.first); ed.push_back(e.second); }
+    c->h_ee_e0.push_back((int)(ed.size() / 2));
+  }
+  c->ee_target.assign(c->h_bodies.size(), 0);
+  c->ee_desc.clear();
+  std::vector<int> ql;
+  std::vector<std::pair<int, int>> seen;
+  for (int pi = 0; pi < (int)c->h_pairs.size(); pi++) {
+    const tsl_contact_pair& pr = c->h_pairs[pi];
+    if (pr.b_idx < 0 || pr.b_idx >= (int)c->h_bodies.size()) continue;
+    std::vector<std::array<int, 3>> q;
+    for (int b = 0; b < (int)c->h_bodies.size(); b++) {   // every query body the range covers, for its first descriptor against b_idx only
+      if (b == pr.b_idx || c->h_bodies[b].v_end <= pr.v_start || c->h_bodies[b].v_start >= pr.v_end) continue;
+      const std::pair<int, int> key{std::min(b, pr.b_idx), std::max(b, pr.b_idx)};
+      if (std::find(seen.begin(), seen.end(), key) != seen.end()) continue;
+      seen.push_back(key);
+      for (int e = c->h_ee_e0[b]; e < c->h_ee_e0[b + 1]; e++)
+        if (ed[2 * e] >= pr.v_start && ed[2 * e] < pr.v_end && ed[2 * e + 1] >= pr.v_start && ed[2 * e + 1] < pr.v_end) q.push_back({ed[2 * e], ed[2 * e + 1], e});
+    }
+    std::sort(q.begin(), q.end());
+    if (q.empty() || c->h_ee_e0[pr.b_idx + 1] == c->h_ee_e0[pr.b_idx]) continue;
+    c->ee_desc.push_back({pi, pr.b_idx, (int)ql.size(), (int)q.size()});
+    c->ee_target[pr.b_idx] = 1;
+    for (auto& e : q) ql.push_back(e[2]);
+  }
+  c->ee_qtot = (long)ql.size();
+  if (c->ee_edges.upload(ed) | c->ee_qlist.upload(ql)) return -1;
+  return 0;
+}
+// the broad-phase buffers of the edge grids, at the first "contact_ee" = 1 (none are allocated while the mode is off)
+static int ee_prepare(tsl_ctx* c) {
+  if (c->ee_ready) return 0;
+  size_t tf = 0, tb = 0, tsn = 0;
+  c->ee_f0.clear(); c->ee_t0.clear(); c->ee_s0.clear();
+  for (size_t b = 0; b < c->h_bodies.size(); b++) {
+    const int ne = c->h_ee_e0[b + 1] - c->h_ee_e0[b];
+    int tsb = 64;
+    while (tsb < 2 * ne) tsb <<= 1;
+    c->ee_f0.push_back(tf); c->ee_t0.push_back(tb); c->ee_s0.push_back(tsn);
+    tf += (size_t)ne + 1; tb += (size_t)tsb + 2; tsn += (size_t)(tsb + 1) / SCAN_TILE + 2;
+  }
+  const size_t nb = std::max<size_t>(c->h_bodies.size(), 1);
+  int rc = 0;
+  rc |= c->ee_key.alloc(tf); rc |= c->ee_val.alloc(tf); rc |= c->ee_key2.alloc(tf); rc |= c->ee_val2.alloc(tf); rc |= c->ee_range.alloc(8 * nb);
+  rc |= c->ee_bcnt.alloc(tb); rc |= c->ee_bptr.alloc(tb); rc |= c->ee_bcur.alloc(tb); rc |= c->ee_bscan.alloc(tsn); rc |= c->ee_lmax.alloc(nb);
+  rc |= c->ee_qcnt.alloc((size_t)c->ee_qtot + 1); rc |= c->ee_qscan.alloc((size_t)c->ee_qtot + 1); rc |= c->ee_cand.alloc((size_t)c->max_n_constraints);
+  rc |= c->ee_scan_tmp.alloc((size_t)(c->ee_qtot + 1) / SCAN_TILE + 2); rc |= c->ee_nvf.alloc(2);
+  if (rc) return -1;
+  c->ee_ready = true;
+  return 0;
+}
 
 static int contact_alloc(tsl_ctx* c, const tsl_scene_desc* d) {
   int rc = 0;
@@ -788,6 +1084,7 @@ static int contact_alloc(tsl_ctx* c, const tsl_scene_desc* d) {
   // border_flag (BaseScene.py:82): all zero unless imported
   rc |= c->border.alloc(NV);
   if (rc) return -1;
+  if (ee_tables(c, faces)) return -1;
   c->proj_flag.zero(); c->proj_dir.zero(); c->proj_idx.zero(); c->proj_w.zero(); c->border.zero(); c->nc_dev.zero();
   c->nc = 0;
   return 0;
@@ -799,9 +1096,12 @@ extern "C" int tsl_contact_detect(tsl_ctx* c, const double* pos, const double* p
   Scope scope(c);
   hipStream_t s = c->stream;
   const int NV = c->NV;
-  c->nc = 0;
+  c->nc = 0; c->nc_ee = 0;
   c->bd_valid = false;
   c->ds.cons_checked = false;   // the factorisation plan compares the new constraint list with the one it was made for
+  const bool ee = c->contact_ee && !c->ee_desc.empty();
+  if (ee && ee_prepare(c)) return -1;
+  if (ee) HIP_OK(hipMemsetAsync(c->ee_nvf.p + 1, 0, sizeof(int), c->stream));   // [1]: largest oversized edge-midpoint bucket
   bool any_self = false;
   for (int v : c->self_contact) any_self |= v != 0;
   if ((c->n_body < 2 && !any_self) || c->NF == 0) { if (nc_host) *nc_host = 0; return 0; }   // a single body can still touch itself (geometry_self.py)
@@ -874,6 +1174,23 @@ extern "C" int tsl_contact_detect(tsl_ctx* c, const double* pos, const double* p
     }
 #undef TSL_PROJ_BY_SIZE
 #undef TSL_PROJ_LAUNCH
+    const int ne = c->h_ee_e0[b + 1] - c->h_ee_e0[b];
+    if (ee && c->ee_target[b] && ne > 0) {   // this body's edge grid (midpoints), on the same stream
+      int tse = 64, lge = 6;
+      while (tse < 2 * ne) { tse <<= 1; lge++; }
+      const int hse = 32 - lge;
+      int *e_key = c->ee_key.p + c->ee_f0[b], *e_val = c->ee_val.p + c->ee_f0[b], *e_key2 = c->ee_key2.p + c->ee_f0[b], *e_val2 = c->ee_val2.p + c->ee_f0[b];
+      int *e_cnt = c->ee_bcnt.p + c->ee_t0[b], *e_ptr = c->ee_bptr.p + c->ee_t0[b], *e_cur = c->ee_bcur.p + c->ee_t0[b], *e_range = c->ee_range.p + 8 * b;
+      hipLaunchKernelGGL(k_grid_range_init, dim3(1), dim3(64), 0, s, e_range, G.n);
+      HIP_OK(hipMemsetAsync(e_cnt, 0, ((size_t)tse + 1) * sizeof(int), s));
+      HIP_OK(hipMemsetAsync(e_cur, 0, (size_t)tse * sizeof(int), s));
+      HIP_OK(hipMemsetAsync(c->ee_lmax.p + b, 0, sizeof(unsigned long long), s));
+      hipLaunchKernelGGL(k_ee_grid_keys, dim3(cnblk(ne, 256)), dim3(256), 0, s, G, c->h_ee_e0[b], ne, (const int*)c->ee_edges.p, pos, e_key, e_range, hse, e_cnt, c->ee_lmax.p + b);
+      scan_exclusive(s, tse + 1, e_cnt, e_ptr, c->ee_bscan.p + c->ee_s0[b]);
+      hipLaunchKernelGGL(k_bucket_scatter, dim3(cnblk(ne, 256)), dim3(256), 0, s, ne, (const int*)e_key, hse, (const int*)e_ptr, e_cur, e_val);
+      hipLaunchKernelGGL(k_bucket_rank, dim3(cnblk(ne, 256)), dim3(256), 0, s, ne, c->h_ee_e0[b], (const int*)e_key, hse, (const int*)e_ptr, (const int*)e_val,
+                         e_key2, e_val2, c->ee_nvf.p + 1);
+    }
   }
   if (multi) {
     HIP_OK(hipEventRecord(c->ev_join, c->side)); HIP_OK(hipEventRecord(c->ev_join2, c->side2));
@@ -900,6 +1217,42 @@ extern "C" int tsl_contact_detect(tsl_ctx* c, const double* pos, const double* p
     }
     if (phase == 0 && Q > 0) scan_exclusive(s, (int)Q + 1, c->cq_flag.p, c->cq_scan.p, c->scan_tmp.p);
   }
+  // edge-edge constraints behind them: per descriptor the qualifying target edges of every query edge are counted, one exclusive scan, listed, then
+  // sorted and written per query edge at nc_vf + slot (fixed order: descriptor, query edge, target edge)
+  int n_ee = 0, big_edges = 0;
+  if (ee) {
+    const long QE = c->ee_qtot;
+    if (Q > 0) HIP_OK(hipMemcpyAsync(c->ee_nvf.p, c->cq_scan.p + Q, sizeof(int), hipMemcpyDeviceToDevice, s));
+    else HIP_OK(hipMemsetAsync(c->ee_nvf.p, 0, sizeof(int), s));
+    HIP_OK(hipMemsetAsync(c->ee_qcnt.p + QE, 0, sizeof(int), s));
+    for (int mode = 0; mode < 2; mode++) {
+      for (const auto& ed : c->ee_desc) {
+        const int b = ed.target, ne = c->h_ee_e0[b + 1] - c->h_ee_e0[b];
+        int tse = 64, lge = 6;
+        while (tse < 2 * ne) { tse <<= 1; lge++; }
+#define TSL_EE_LAUNCH(GW, MD)                                                                                                                                  \
+  hipLaunchKernelGGL((k_ee_query<GW, MD>), dim3(cnblk((long)ed.nq * GW, 256)), dim3(256), 0, s, G, ed.nq, (const int*)c->ee_qlist.p + ed.qoff, 32 - lge,             \
+                     (const int*)c->ee_bptr.p + c->ee_t0[b], (const int*)c->ee_key2.p + c->ee_f0[b], (const int*)c->ee_val2.p + c->ee_f0[b],                         \
+                     (const int*)c->ee_range.p + 8 * b, (const int*)c->ee_edges.p, pos, (const unsigned long long*)c->ee_lmax.p + b, c->eps_contact,                 \
+                     c->ee_qcnt.p + ed.qoff, (const int*)c->ee_qscan.p + ed.qoff, c->ee_cand.p, c->max_n_constraints)
+        // (lanes per query edge by the size of the target's edge set, as TSL_PROJ_BY_SIZE)
+        if (mode == 0) { if (ne >= 8192) TSL_EE_LAUNCH(64, 0); else if (ne >= 512) TSL_EE_LAUNCH(8, 0); else TSL_EE_LAUNCH(1, 0); }
+        else { if (ne >= 8192) TSL_EE_LAUNCH(64, 1); else if (ne >= 512) TSL_EE_LAUNCH(8, 1); else TSL_EE_LAUNCH(1, 1); }
+#undef TSL_EE_LAUNCH
+      }
+      if (mode == 0) scan_exclusive(s, (int)QE + 1, c->ee_qcnt.p, c->ee_qscan.p, c->ee_scan_tmp.p);
+    }
+    for (const auto& ed : c->ee_desc) {
+      const tsl_contact_pair& pr = c->h_pairs[ed.pair];
+      const double live = pr.mu_is_param == 2 ? c->mu_cloth_cloth : c->mu_cloth_elastic;
+      const double mu = pr.mu_is_param ? live * (pr.mu > 0 ? pr.mu : 1.0) : pr.mu;
+      hipLaunchKernelGGL(k_ee_build, dim3(cnblk(ed.nq, 128)), dim3(128), 0, s, ed.nq, ed.qoff, (const int*)c->ee_qlist.p + ed.qoff, (const int*)c->ee_edges.p,
+                         (const int*)c->ee_qscan.p, c->ee_cand.p, (const int*)c->ee_nvf.p, c->max_n_constraints, mu, pr.mu_is_param, c->k_contact, c->eps_contact, pos, prev,
+                         c->c_idx.p, c->c_w.p, c->c_k.p, c->c_mu.p, c->c_dx0.p, c->c_T.p, c->c_n.p, c->c_kind.p);
+    }
+    HIP_OK(hipMemcpyAsync(&n_ee, c->ee_qscan.p + QE, sizeof(int), hipMemcpyDeviceToHost, s));
+    HIP_OK(hipMemcpyAsync(&big_edges, c->ee_nvf.p + 1, sizeof(int), hipMemcpyDeviceToHost, s));
+  }
   int nc = 0, big_bucket = 0;
   if (Q > 0) HIP_OK(hipMemcpyAsync(&nc, c->cq_scan.p + Q, sizeof(int), hipMemcpyDeviceToHost, s));
   HIP_OK(hipMemcpyAsync(&big_bucket, c->nc_dev.p + 1, sizeof(int), hipMemcpyDeviceToHost, s));
@@ -910,12 +1263,23 @@ extern "C" int tsl_contact_detect(tsl_ctx* c, const double* pos, const double* p
     return tsl_fail("contact detection: %d triangles of one body fall into one broad-phase cell (more than %d are not ranked): the body lies outside grid_extent = %g m "
                     "(centroids are clamped into the boundary cells) or grid_h = %g m is far larger than its triangles", big_bucket, TSL_BUCKET_CAP, c->grid_extent, c->grid_h);
   }
+  if (big_edges > 0) {
+    c->nc = 0;
+    return tsl_fail("contact detection (contact_ee): %d surface-edge midpoints of one body fall into one broad-phase cell (more than %d are not ranked): the body lies "
+                    "outside grid_extent = %g m or grid_h = %g m is far larger than its edges", big_edges, TSL_BUCKET_CAP, c->grid_extent, c->grid_h);
+  }
+  if (ee && (long)nc + n_ee > c->max_n_constraints) {
+    c->nc = 0;
+    return tsl_fail("contact detection: %d vertex-triangle + %d edge-edge active constraints exceed max_n_constraints = %d (raise the scene's max_n_constraints)", nc, n_ee,
+                    c->max_n_constraints);
+  }
   if (nc > c->max_n_constraints) {
     // more constraints than the scene's cap (the reference would drop the surplus in atomic-append order): an error
     c->nc = 0;
     return tsl_fail("contact detection: %d active constraints exceed max_n_constraints = %d (raise the scene's max_n_constraints)", nc, c->max_n_constraints);
   }
-  c->nc = nc;
+  nc += n_ee;
+  c->nc = nc; c->nc_ee = n_ee;
   if (nc_host) *nc_host = c->nc;
   if (c->nc > 0) {
     const int n1 = NV + 1;
@@ -933,6 +1297,18 @@ extern "C" int tsl_contact_detect(tsl_ctx* c, const double* pos, const double* p
   return 0;
 }
 
+// the arguments of the edge-edge slots: every per-constraint array from slot nvf on
+static ContactArgs ee_args(ContactArgs A, int nvf) {
+  A.idx += 4 * (size_t)nvf; A.w += 3 * (size_t)nvf; A.n += 3 * (size_t)nvf; A.dx0 += 3 * (size_t)nvf; A.k += nvf; A.mu += nvf; A.T += 6 * (size_t)nvf;
+  return A;
+}
+
+extern "C" int tsl_contact_counts(tsl_ctx* c, int32_t* out2) {
+  if (!c || !out2) return tsl_fail("tsl_contact_counts: null argument");
+  out2[0] = c->nc - c->nc_ee; out2[1] = c->nc_ee;
+  return 0;
+}
+
 static bool direct_takes_solve(tsl_ctx* c);
 static void contact_diag_refresh(tsl_ctx* c, hipStream_t s) {
   hipLaunchKernelGGL(k_contact_diag, dim3(cnblk((long)c->NV * 64, 256)), dim3(256), 0, s, c->NV, (const int*)c->cr_ptr.p, (const int*)c->cr_ent.p, (const double*)c->c_H.p, c->c_diag.p);
@@ -945,8 +1321,18 @@ static int contact_assemble(tsl_ctx* c, const double* pos, int spd, double* grad
   A.k_contact = c->k_contact; A.eps_contact = c->eps_contact; A.eps_vh = c->eps_v * c->dt;
   if (grad && c->c_G.n < 12 * (size_t)c->max_n_constraints) { if (c->c_G.alloc(12 * (size_t)c->max_n_constraints)) return -1; }
   double* cg = grad ? c->c_G.p : (double*)nullptr;   // per-constraint gradients, summed per vertex by k_contact_row_gather
-  if (c->spd_literal && spd == 1) hipLaunchKernelGGL(k_contact_assemble_coop<true>, dim3(cnblk((long)c->nc * 16, 256)), dim3(256), 0, s, c->nc, A, pos, spd, c->c_Hfull.p, cg);
-  else hipLaunchKernelGGL(k_contact_assemble_coop<false>, dim3(cnblk((long)c->nc * 16, 256)), dim3(256), 0, s, c->nc, A, pos, spd, c->c_Hfull.p, cg);
+  const int nvf = c->nc - c->nc_ee;   // vertex-triangle slots [0, nvf), edge-edge slots [nvf, nc)
+  if (nvf > 0) {
+    if (c->spd_literal && spd == 1) hipLaunchKernelGGL(k_contact_assemble_coop<true>, dim3(cnblk((long)nvf * 16, 256)), dim3(256), 0, s, nvf, A, pos, spd, c->c_Hfull.p, cg);
+    else hipLaunchKernelGGL(k_contact_assemble_coop<false>, dim3(cnblk((long)nvf * 16, 256)), dim3(256), 0, s, nvf, A, pos, spd, c->c_Hfull.p, cg);
+  }
+  if (c->nc_ee > 0) {
+    const ContactArgs E = ee_args(A, nvf);
+    double* Hf = c->c_Hfull.p + 144 * (size_t)nvf;
+    double* cge = cg ? cg + 12 * (size_t)nvf : (double*)nullptr;
+    if (c->spd_literal && spd == 1) hipLaunchKernelGGL((k_contact_assemble_coop<true, true>), dim3(cnblk((long)c->nc_ee * 16, 256)), dim3(256), 0, s, c->nc_ee, E, pos, spd, Hf, cge);
+    else hipLaunchKernelGGL((k_contact_assemble_coop<false, true>), dim3(cnblk((long)c->nc_ee * 16, 256)), dim3(256), 0, s, c->nc_ee, E, pos, spd, Hf, cge);
+  }
   hipLaunchKernelGGL(k_contact_mask, dim3(cnblk((long)c->nc * 144, 256)), dim3(256), 0, s, c->nc, c->c_idx.p, c->frozen.p, c->c_Hfull.p, c->c_H.p);
   // the diagonal 3 x 3 blocks of the contact terms feed the block-Jacobi inverse and the hierarchy's Galerkin diagonal only: a solve that goes to the
   // factorisation never reads them (45 us on the longest chain of an assembly); block_jacobi_refresh forms them when the hierarchy runs after all

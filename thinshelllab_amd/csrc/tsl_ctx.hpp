@@ -360,6 +360,19 @@ struct tsl_ctx {
   DevBuf<int> grid_cnt, grid_ptr, grid_cur, scan_tmp;   // hash buckets of the broad phase (histogram, offsets, cursors) and the scratch of the scan
   int grid_buckets_max = 0;
   int max_body_faces = 0;
+  // ---- edge-edge contact ("contact_ee", k_contact.hpp): constraint slots [nc - nc_ee, nc) of the last detection
+  struct EeDesc { int pair, target, qoff, nq; };   // a descriptor of h_pairs that is the first one of its unordered body pair; its query edges qlist[qoff, qoff + nq)
+  int contact_ee = 0, nc_ee = 0;
+  std::vector<int> h_ee_e0;          // surface edges of body b: [h_ee_e0[b], h_ee_e0[b + 1]) of ee_edges, ascending (v0, v1)
+  std::vector<EeDesc> ee_desc;
+  std::vector<char> ee_target;       // per body: target of an edge-edge descriptor (its edge grid is built per detection)
+  long ee_qtot = 0;
+  bool ee_ready = false;             // grid buffers allocated (at the first "contact_ee" = 1)
+  DevBuf<int> ee_edges, ee_qlist;    // 2 x n_edges; query edges of all descriptors
+  DevBuf<int> ee_key, ee_val, ee_key2, ee_val2, ee_range, ee_bcnt, ee_bptr, ee_bcur, ee_bscan;   // per target body, regions as grid_* (offsets ee_f0 / ee_t0 / ee_s0)
+  std::vector<size_t> ee_f0, ee_t0, ee_s0;
+  DevBuf<unsigned long long> ee_lmax;   // per body: bits of its longest edge at the detection's positions
+  DevBuf<int> ee_qcnt, ee_qscan, ee_cand, ee_scan_tmp, ee_nvf;
 
   // ---- multigrid preconditioner
   std::vector<MgCloth*> mg;

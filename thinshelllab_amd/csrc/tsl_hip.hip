@@ -445,6 +445,11 @@ extern "C" int tsl_set_param(tsl_ctx* c, const char* key, double v) {
     c->spd_literal = (int)v;
   }
   else if (k == "contact") c->contact_enable = (v != 0.0);
+  else if (k == "contact_ee") {
+    if (v != 0.0 && v != 1.0) return tsl_fail("tsl_set_param: contact_ee must be 0 or 1 (got %g)", v);
+    c->contact_ee = (int)v;
+    if (c->contact_ee) TSL_TRY(ee_prepare(c));
+  }
   else if (k == "grid_h") c->grid_h = v;
   else if (k == "grid_extent") c->grid_extent = v;
   else if (k == "adj_spd_pc") c->adj_spd_pc = (int)v;
@@ -565,11 +570,13 @@ static int energy_async(tsl_ctx* c, const double* pos, const double* prev, const
   if (c->n_cface) hipLaunchKernelGGL(k_cloth_normals, dim3(nblk(c->n_cface, 256)), dim3(256), 0, s, c->n_cface, pos, c->cf_f2v.p, c->norm_dir.p);
   const int nmax = std::max(std::max(c->NV, c->n_cface), std::max(c->n_hinge, c->n_tet));
   // partials per workgroup, added in a fixed order (the line search decides on E < E0)
-  const int nb1 = nblk(nmax, 256), nb2 = c->nc > 0 ? nblk(c->nc, 64) : 0;
-  if (c->e_part.n < (size_t)nb1 + (size_t)nblk(c->max_n_constraints, 64)) { if (c->e_part.alloc((size_t)nb1 + (size_t)nblk(c->max_n_constraints, 64))) return -1; }
+  const int nvf = c->nc - c->nc_ee;   // vertex-triangle slots, then the edge-edge slots ("contact_ee")
+  const int nb1 = nblk(nmax, 256), nb2 = nvf > 0 ? nblk(nvf, 64) : 0, nb3 = c->nc_ee > 0 ? nblk(c->nc_ee, 64) : 0;
+  if (c->e_part.n < (size_t)nb1 + (size_t)nblk(c->max_n_constraints, 64) + 1) { if (c->e_part.alloc((size_t)nb1 + (size_t)nblk(c->max_n_constraints, 64) + 1)) return -1; }
   hipLaunchKernelGGL(k_energy, dim3(nb1), dim3(256), 0, s, vert_args(c), cloth_args(c), tet_args(c), pos, prev, vel, ref, c->e_part.p);
-  if (nb2 > 0) hipLaunchKernelGGL(k_contact_energy, dim3(nb2), dim3(64), 0, s, c->nc, contact_args(c), pos, c->e_part.p + nb1);
-  hipLaunchKernelGGL(k_energy_final, dim3(1), dim3(256), 0, s, nb1 + nb2, (const double*)c->e_part.p, &SC(c)->energy);
+  if (nb2 > 0) hipLaunchKernelGGL(k_contact_energy, dim3(nb2), dim3(64), 0, s, nvf, contact_args(c), pos, c->e_part.p + nb1);
+  if (nb3 > 0) hipLaunchKernelGGL(k_ee_energy, dim3(nb3), dim3(64), 0, s, c->nc_ee, ee_args(contact_args(c), nvf), pos, c->e_part.p + nb1 + nb2);
+  hipLaunchKernelGGL(k_energy_final, dim3(1), dim3(256), 0, s, nb1 + nb2 + nb3, (const double*)c->e_part.p, &SC(c)->energy);
   return 0;
 }
 static int energy_sync(tsl_ctx* c, const double* pos, const double* prev, const double* vel, const double* ref, double* E) {
@@ -2126,11 +2133,21 @@ extern "C" int tsl_elastic_force(tsl_ctx* c, const double* pos, double* force) {
 extern "C" int tsl_friction_grad(tsl_ctx* c, const double* pos, double* out_host) {
   Scope scope(c);
   hipStream_t s = c->stream;
+  if (c->nc_ee > 0) {   // edge-edge slots of the mu_cloth_cloth pairs: no gradient (restating the vertex-triangle term with the edge-edge weights disagreed with
+                        // differences in mu by orders of magnitude), so the call fails instead of returning a wrong number
+    std::vector<int> kind(c->nc_ee);
+    HIP_OK(hipMemcpyAsync(kind.data(), c->c_kind.p + (c->nc - c->nc_ee), kind.size() * sizeof(int), hipMemcpyDeviceToHost, s));
+    HIP_OK(hipStreamSynchronize(s));
+    for (int k : kind)
+      if (k == 2) return tsl_fail("tsl_friction_grad: %d edge-edge constraints (contact_ee = 1) use mu_cloth_cloth; their friction-coefficient gradient is not implemented", c->nc_ee);
+  }
   double* acc = &SC(c)->aux[0];
   HIP_OK(hipMemsetAsync(acc, 0, sizeof(double), s));
-  if (c->nc > 0)
-    hipLaunchKernelGGL(k_contact_friction_grad, dim3(nblk(c->nc, 64)), dim3(64), 0, s, c->nc, contact_args(c), c->c_kind.p, c->frozen.p, pos, c->pdir.p, c->mu_cloth_cloth, acc,
-                       nblk(c->nc, 64) <= 64 * 512 ? c->dot_part.p : (double*)nullptr, c->dot_ticket.p);
+  const int nvf = c->nc - c->nc_ee;   // vertex-triangle slots, then the edge-edge slots ("contact_ee")
+  if (nvf > 0)
+    hipLaunchKernelGGL(k_contact_friction_grad, dim3(nblk(nvf, 64)), dim3(64), 0, s, nvf, contact_args(c), c->c_kind.p, c->frozen.p, pos, c->pdir.p, c->mu_cloth_cloth, acc,
+                       nblk(nvf, 64) <= 64 * 512 ? c->dot_part.p : (double*)nullptr, c->dot_ticket.p);
+
   HIP_OK(hipMemcpyAsync(out_host, acc, sizeof(double), hipMemcpyDeviceToHost, s));
   HIP_OK(hipStreamSynchronize(s));
   return 0;
@@ -2246,7 +2263,7 @@ static int newton_step(const std::vector<StepMember>& m, GroupPool* pool, tsl_ct
     tsl_ctx* c = m[i].c;
     int nc = 0;
     if (c->contact_enable) TSL_TRY(tsl_contact_detect(c, m[i].pos, m[i].prev, &nc));
-    else { c->nc = 0; c->ds.cons_checked = false; }
+    else { c->nc = 0; c->nc_ee = 0; c->ds.cons_checked = false; }
     st[i].nc = nc;
   }
   const long gfact0 = g ? g->ds.n_factor : 0;
@@ -2866,7 +2883,7 @@ static int adjoint_pre(tsl_ctx* c, const AdjArgs& a, double** rhs) {
   // contacts re-detected at pos = prev_pos = x_{s-1} (copy_pos_only + calc_vn + f_contact + contact_analysis)
   int nc = 0;
   if (c->contact_enable) TSL_TRY(tsl_contact_detect(c, x_prev, x_prev, &nc));
-  else { c->nc = 0; c->ds.cons_checked = false; }
+  else { c->nc = 0; c->nc_ee = 0; c->ds.cons_checked = false; }
   ClothArgs CA = cloth_args(c);
   if (c->vg_stage.n < 3 * (size_t)std::max(c->vg_ns, 1)) { if (c->vg_stage.alloc(3 * (size_t)std::max(c->vg_ns, 1))) return tsl_fail("out of device memory (gradient staging)"); }
   // pos = x_s, ref_angle = ref_{s-1}: init_folding + ref_angle_backprop_a2ax
@@ -2932,7 +2949,9 @@ static int adjoint_post(tsl_ctx* c, const AdjArgs& a) {
   // contact_energy_backprop(step-1) ; ref_angle_backprop_x2a
   if (c->nc > 0) {
     if (c->c_G.n < 12 * (size_t)c->max_n_constraints) { if (c->c_G.alloc(12 * (size_t)c->max_n_constraints)) return -1; }
-    hipLaunchKernelGGL(k_contact_backprop, dim3(nblk(c->nc, 64)), dim3(64), 0, s, c->nc, contact_args(c), x_s, c->pdir.p, c->c_G.p);
+    const int nvf = c->nc - c->nc_ee;   // vertex-triangle slots, then the edge-edge slots ("contact_ee")
+    if (nvf > 0) hipLaunchKernelGGL(k_contact_backprop, dim3(nblk(nvf, 64)), dim3(64), 0, s, nvf, contact_args(c), x_s, c->pdir.p, c->c_G.p);
+    if (c->nc_ee > 0) hipLaunchKernelGGL(k_ee_backprop, dim3(nblk(c->nc_ee, 64)), dim3(64), 0, s, c->nc_ee, ee_args(contact_args(c), nvf), x_s, c->pdir.p, c->c_G.p + 12 * (size_t)nvf);
     hipLaunchKernelGGL(k_contact_row_gather, dim3(nblk((long)NV * 64, 256)), dim3(256), 0, s, NV, (const int*)c->rowpos.p, (const int*)c->cr_ptr.p, (const int*)c->cr_ent.p,
                        (const double*)c->c_G.p, pg_prev);
   }

@@ -52,6 +52,7 @@ class BaseScene:
     _newton_cap = 1000   # BaseScene.py:1342
     _plastic = 0         # base timestep_finish does not update ref angles (:1321-1325)
     spd_literal = False  # True: the forward projections run the reference's own projector (linalg.py:15-148) instead of the converged eigen-clamp
+    contact_ee = False   # True: edge-edge contact between the surface edges of different bodies next to the reference's vertex-triangle contact
 
     def __init__(self, cloth_size=0.1, dt=5e-3, enable_gripper=True, device="cuda:0"):
         # BaseScene.py:31-60
@@ -277,6 +278,9 @@ class BaseScene:
         the reference never calls these kernels (analytic_grad_single.py:231 is commented out), they complete the named surface."""
         import numpy as np
         c = self._ensure_ctx().constraints() if constraints is None else constraints
+        if constraints is None and self.contact_ee:   # the vertex-triangle slots only (the edge-edge ones follow them)
+            n_vf = self._ctx.contact_counts()[0]
+            c = {k: v[:n_vf] for k, v in c.items()}
         x = self.pos.to_numpy() if pos is None else pos
         idx, w = c["idx"], c["w"]
         T = c["T"].reshape(-1, 2, 3)
@@ -339,6 +343,8 @@ class BaseScene:
             self._ctx.set_param("newton_cap", self._newton_cap)
             self._ctx.set_param("plastic", self._plastic)
             self._ctx.set_param("spd_literal", int(bool(self.spd_literal)))
+            if self.contact_ee:
+                self._ctx.set_param("contact_ee", 1)
             self._ctx.set_ext_force(self._ext_force_array())
             self._dirty.clear()
         if self._dirty:
@@ -364,6 +370,13 @@ class BaseScene:
         self.spd_literal = bool(on)
         if self._ctx is not None:
             self._ctx.set_param("spd_literal", int(self.spd_literal))
+
+    def set_contact_ee(self, on):
+        """Edge-edge contact (no counterpart in the reference): True appends edge-edge constraints behind the vertex-triangle ones at every detection,
+        False (default) keeps vertex-triangle contact only.  Applies to a live engine context at once and to one created later."""
+        self.contact_ee = bool(on)
+        if self._ctx is not None:
+            self._ctx.set_param("contact_ee", int(self.contact_ee))
 
     def set_frozen_kernel(self):
         # BaseScene.py:1445-1463
