@@ -15,7 +15,8 @@ resident in HBM.  value = cloth triangles x K x n_gpus / wall seconds (max over 
 --dump-outputs DIR writes what the timed rollout computed (dump_outputs) as .npy files; the inputs depend on the arguments only, so
 two builds run with the same arguments can be compared output for output.
 
-The JSON line also carries
+A plain run sets up, warms up, times the K steps, dumps if asked and prints the line: the headline keys and `config` (the timed rollout's
+own convergence accounting).  With --full the line also carries the legs that take runs of their own:
   roofline      -- the kernel class of the sparse direct solve that takes the most time per Newton iteration (named in the object):
                    algorithmic flops (or bytes) per launch / average launch duration between one HIP-event pair around back-to-back
                    replays of that class's launches on the run's last plan, against the f64 matrix-core peak (or 8 TB/s);
@@ -613,7 +614,9 @@ def main():
     ap.add_argument("--grid", type=int, default=224, help="cloth grid N = M (224 -> 100,352 triangles)")
     ap.add_argument("--cloth-size", type=float, default=0.1 / 15 * 224, help="edge length of the square cloth in m (default keeps the reference dx = 0.1/15)")
     ap.add_argument("--cg-tol", type=float, default=1e-10)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="after the headline measurement, also the legs that take runs of their own: roofline (kernel-class "
+                                                         "replays) and cpu_baseline (oracle steps on the host; --no-cpu-baseline leaves it out)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave cpu_baseline out")
     ap.add_argument("--param", action="append", default=[], metavar="KEY=VALUE", help="extra tsl_set_param settings (solver experiments)")
     ap.add_argument("--scenes-per-gpu", type=int, default=0, help="after the single-scene measurement: the same workload as S independent scenes on this GPU stepped in lock step as one scene group "
                                                                      "(merged factorisations), reported as multi_scene next to the headline value")
@@ -704,10 +707,11 @@ def main():
     })
     if dumped is not None:
         out["dumped_outputs"] = {"dir": args.dump_outputs, "shapes": dumped}
-    rf, step = roofline(ctx, scene, elapsed, K, stats, args)
-    if rf is not None:
-        rf["whole_step"] = step   # SURVEY section 8d's bytes model and the factorisation-flops figure of the WHOLE step, inside the object the driver keeps
-        out["roofline"] = rf
+    if args.full:
+        rf, step = roofline(ctx, scene, elapsed, K, stats, args)
+        if rf is not None:
+            rf["whole_step"] = step   # SURVEY section 8d's bytes model and the factorisation-flops figure of the WHOLE step, inside the object the driver keeps
+            out["roofline"] = rf
     if args.scenes_per_gpu > 1 and rank == 0 and world == 1:
         # the multi-scene leg runs in a child process of its own (a fresh HIP context: this process keeps its scene, plans and arenas for the baseline leg below)
         try:
@@ -720,7 +724,7 @@ def main():
             out["multi_scene"] = json.loads(line[-1]) if line else {"scenes_per_gpu": args.scenes_per_gpu, "value": None, "error": (r.stderr or "no output")[-400:]}
         except Exception as e:   # noqa: BLE001 -- never fail the headline on the extra measurement
             out["multi_scene"] = {"scenes_per_gpu": args.scenes_per_gpu, "value": None, "error": repr(e)}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         try:
             out["cpu_baseline"] = cpu_baseline(args, scene, stats, K, rank)
         except Exception as e:  # the oracle is optional test infrastructure; never fail the GPU number on it

@@ -1,11 +1,11 @@
-"""Copies the rocprofv3 summaries that scripts/gpu_profile.sh left under gpurun_out/prof/ into profiles/ (tracked) and prints the
-headline numbers.  usage (repo root, after `gpurun -- 'bash scripts/gpu_profile.sh r02a'`):  python scripts/install_profiles.py r02a [workload]"""
+"""Copies the rocprofv3 summaries that scripts/gpu_profile.sh left under $PROF_OUT (default build/prof) into profiles/ (tracked) and prints the
+headline numbers.  usage (repo root, after `bash scripts/gpu_profile.sh r02a` on an MI355X):  python scripts/install_profiles.py r02a [workload]"""
 import csv, json, os, re, shutil, sys
 
 TAG = sys.argv[1] if len(sys.argv) > 1 else "r03a"
 WL = (sys.argv[2] if len(sys.argv) > 2 else "cfg4").replace("-", "_")
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-src = os.path.join(root, "gpurun_out", "prof") + os.sep
+src = os.path.join(root, os.environ.get("PROF_OUT", os.path.join("build", "prof"))) + os.sep
 dst = os.path.join(root, "profiles") + os.sep
 
 

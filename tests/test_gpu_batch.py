@@ -57,6 +57,24 @@ def test_bench_under_launcher_reports_world():
     assert r2.returncode != 0
 
 
+def test_bench_full_adds_roofline_and_cpu_baseline():
+    """a plain bench line stops after the timed steps; --full adds the legs that take runs of their own: the kernel-class replays
+    (roofline) and the oracle on the host (cpu_baseline: complete steps on a small cloth compared with the GPU, one Newton iteration at
+    the bench size)"""
+    args = [os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--grid", "48"]
+    lines = []
+    for k, extra in enumerate(([], ["--full", "--cpu-grid", "16", "--cpu-steps", "1"])):
+        r = _launch(args + extra, 29657 + 2 * k)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines.append(json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1]))
+    plain, full = lines
+    assert "roofline" not in plain and "cpu_baseline" not in plain and plain["value"] > 0
+    assert full["roofline"]["launches_per_factorization"] > 0 and full["roofline"]["whole_step"]["factorization_flops"] > 0
+    cb = full["cpu_baseline"]
+    assert cb["parity"]["ok"], cb["parity"]
+    assert cb["complete_steps_small_scene"]["value"] > 0 and cb["bench_size"]["value"] > 0, cb
+
+
 def test_trajopt_batch_cfg5_at_stated_size_one_rank(tmp_path):
     """BASELINE configs[4] at the size SURVEY section 8d states -- 8 scenes of the cfg3 class (folding, 200 x 100 cloth, 40,000 triangles
     each, trajectory seeds default_rng(1000 + scene)) -- on the one GPU the test box has: the 8 scenes run round-robin on rank 0,
