@@ -198,6 +198,24 @@ int tsl_param_grad(tsl_ctx* ctx, const double* pos_dev, const double* ref_angle_
  * Fails (< 0) while edge-edge constraints ("contact_ee" = 1) of such pairs are present: their term is not implemented. */
 int tsl_friction_grad(tsl_ctx* ctx, const double* pos_dev, double* out_host);
 
+/* d(loss)/d(theta) contributions of one reverse step for any of the material and contact scalars: out_host[j] = sum over the free dofs of
+ * p . d(force)/d(theta_j) (force = -F, F the gradient tsl_assemble forms: the sign of tsl_param_grad, whose kb is the sum of the "cloth<i>.Kb"
+ * values), theta_j = the value tsl_set_param(keys[j]) sets, every other key held fixed.
+ * Keys: "cloth<i>.Kl", "cloth<i>.Ka", "cloth<i>.Kb", "elastic<i>.mu", "elastic<i>.lam" (both material models, alpha fixed), "k_contact" (normal
+ * term of every vertex-triangle slot and the friction weights c_k = -mu k_contact (gap - eps) of the detection), "mu_cloth_elastic",
+ * "mu_cloth_cloth" (friction of the slots whose pair uses that live parameter, the pair's factor kept: d c_k = c_k / mu_live).
+ * p_dev == NULL: the solution of the last tsl_adjoint_step (as tsl_param_grad uses it); otherwise any 3*tot_NV vector (original vertex order).
+ * pos = tape state x_s, ref_angle = tape rest angles of step s-1 (needed by the Kb keys only); contact constraints as last detected / as the
+ * last adjoint step left them -- c_k and dx0 are records of the detection, the derivative does not differentiate detection.
+ * Fails (< 0, the key named in tsl_last_error) for an unknown or non-differentiated key (eps_contact, damping, k_angle, alpha, solver keys, ...),
+ * a body index out of range, "k_contact" while edge-edge constraints ("contact_ee" = 1) are present, "mu_cloth_*" while an edge-edge
+ * constraint of that parameter is present (their friction derivative is not implemented), and a contact key whose live value is 0 (the
+ * derivative exists there, but the detection records c_k vanish with the value and cannot carry it: start a fit from a small nonzero value).
+ * Deterministic: per-workgroup partials per key joined in a fixed order, a key's value is the same bits whichever other keys are asked for.
+ * One device-to-host copy and one stream synchronisation per call. */
+int tsl_param_grad_keys(tsl_ctx* ctx, const double* pos_dev, const double* ref_angle_dev, const double* p_dev, const char* const* keys,
+                        int32_t n_keys, double* out_host);
+
 /* Introspection used by the parity tests (tests/ only): assembled matrix as BSR on the host. */
 int tsl_matrix_nnzb(tsl_ctx* ctx, int32_t* nb_host, int32_t* nnzb_host);
 int tsl_matrix_export(tsl_ctx* ctx, int32_t* row_ptr_host, int32_t* col_host, double* vals_host);

@@ -175,6 +175,19 @@ class TslContext:
         check(self.L.tsl_param_grad(self.h, _ptr(pos), _ptr(ref_angle), out), "tsl_param_grad")
         return dict(kb=out[0], mu=out[1], lam=out[2])
 
+    def param_grads(self, pos, ref_angle, keys, p=None):
+        """{key: sum over the free dofs of p . d(force)/d(key)} at the tape state pos (tsl_param_grad_keys): keys as tsl_set_param spells them
+        ("cloth<i>.Kl|Ka|Kb", "elastic<i>.mu|lam", "k_contact", "mu_cloth_elastic", "mu_cloth_cloth"); p None: the solution of the last
+        adjoint_step, else a 3 * tot_NV device vector"""
+        keys = list(keys)
+        if not keys:
+            return {}
+        self.refresh_stream()
+        arr = (C.c_char_p * len(keys))(*[k.encode() for k in keys])
+        out = (C.c_double * len(keys))()
+        check(self.L.tsl_param_grad_keys(self.h, _ptr(pos), _ptr(ref_angle), _ptr(p), arr, len(keys), out), "tsl_param_grad_keys")
+        return {k: out[j] for j, k in enumerate(keys)}
+
     # ---- introspection (tests)
     def matrix(self):
         """(row_ptr, col, vals[nnzb,3,3]) of the masked system matrix of the last assemble (static part)."""

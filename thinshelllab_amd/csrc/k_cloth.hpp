@@ -116,6 +116,7 @@ TSL_DEV double hinge_energy(const ClothArgs& A, int h, const double* __restrict_
 
 // ---------------------------------------------------------------------------------------------
 // gradient: per face (edges + area, Cloth.compute_residual :653-677), per hinge (:679-687)
+// (k_param.hpp restates both terms per unit Kl / Ka / Kb for tsl_param_grad_keys: a change here goes there too)
 __global__ void k_cloth_grad_face(ClothArgs A, const double* __restrict__ pos) {
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= A.n_cface) return;

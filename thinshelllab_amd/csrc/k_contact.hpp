@@ -364,6 +364,8 @@ TSL_DEV double c_comp(const d3& v, int a) { return a == 0 ? v.x : (a == 1 ? v.y 
 // LIT ("spd_literal" = 1, spd 1 only): the normal block is projected by the reference's own projector (spd_literal9_coop, K = 20; a third LDS array for T).
 // EE: an edge-edge constraint (see k_ee_build): q = (x1 - x0, x3 - x2, x2 - x0), friction weights (-(1 - t), -t, 1 - s, s) over (x0..x3) with
 // (s, t) = (w[0], w[1]); the q-space normal block, its projection and the friction block are the same code, only the 9 -> 12 row map differs.
+// (k_param.hpp, k_pg_contact, restates the normal gradient and the friction term of the vertex-triangle slots for tsl_param_grad_keys: a change
+// here goes there too)
 template <bool LIT = false, bool EE = false>
 __global__ void __launch_bounds__(256)
 k_contact_assemble_coop(int nc, ContactArgs A, const double* __restrict__ pos, int spd, double* __restrict__ Hfull, double* __restrict__ cg) {

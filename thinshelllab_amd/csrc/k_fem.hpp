@@ -83,6 +83,7 @@ TSL_DEV double tet_energy(const TetArgs& A, int t, const double* __restrict__ po
 }
 
 // forces: model_elastic_tactile.py:144-154 / model_elastic_offset.py:188-198 ; residual contribution is -force
+// (k_param.hpp, k_pg_tet, restates dP/d(mu) and dP/d(lam) of both models for tsl_param_grad_keys: a change here goes there too)
 __global__ void k_tet_grad(TetArgs A, const double* __restrict__ pos) {
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= A.n_tet) return;

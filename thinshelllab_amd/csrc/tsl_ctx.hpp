@@ -310,6 +310,7 @@ struct tsl_ctx {
   double adj_clamp = 1000.0;
   int adj_clamp_angleref = 1;
   DevBuf<double> dmu_accum;  // d_mu of the box / ball bodies (accumulates like the reference's field)
+  DevBuf<double> pg_part, pg_out;   // tsl_param_grad_keys: per-workgroup partials of every key row, the values read back
   // preconditioner built from a different (SPD-projected) assembly than the operator: adjoint solves (un-projected H)
   DevBuf<double> vals_pc, c_H_pc;
   bool pc_separate = false, pc_frozen = false, in_step = false;

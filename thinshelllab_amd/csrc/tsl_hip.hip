@@ -4,6 +4,7 @@
 //   SparseMatrix.solve (sparse_solver.py:85-105) and Grad.transfer_grad (analytic_grad_single.py:217-257).
 // There is no CPU fallback in this library: without a HIP device every entry point fails.
 #include <stdarg.h>
+#include <cctype>
 #include <chrono>
 #include <mutex>
 
@@ -14,6 +15,7 @@
 #include "k_contact.hpp"
 #include "k_fem.hpp"
 #include "k_mg.hpp"
+#include "k_param.hpp"
 #include "k_solver.hpp"
 #include "tsl_ctx.hpp"
 
@@ -2199,6 +2201,111 @@ extern "C" int tsl_param_grad(tsl_ctx* c, const double* pos, const double* ref, 
   HIP_OK(hipMemcpyAsync(h, acc, 2 * sizeof(double), hipMemcpyDeviceToHost, s));
   HIP_OK(hipStreamSynchronize(s));
   out_host[0] = h[0]; out_host[1] = h[1]; out_host[2] = 0.0;
+  return 0;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Parameter gradients by key (system identification beyond the reference's {kb, mu, lam}): out[j] = -sum over the free dofs of p . dF/d(theta_j),
+// F = the gradient of tsl_assemble at (pos, ref_angle) with the contact constraints as they stand -- the sign of tsl_param_grad, whose kb is the sum
+// of the cloth<i>.Kb values.  One pass per element class that some requested key needs (k_param.hpp), each writing one partial per workgroup and key
+// row; k_pg_final sums the requested keys' partials; one read-back.
+extern "C" int tsl_param_grad_keys(tsl_ctx* c, const double* pos, const double* ref, const double* p_dev, const char* const* keys, int32_t n_keys,
+                                   double* out_host) {
+  Scope scope(c);
+  if (n_keys <= 0) return 0;
+  if (!keys || !out_host || !pos) return tsl_fail("tsl_param_grad_keys: null argument");
+  hipStream_t s = c->stream;
+  const int n_cloth = (int)c->h_cloth.size(), n_el = (int)c->h_el.size();
+  const int nvf = c->nc - c->nc_ee;   // vertex-triangle slots, then the edge-edge slots ("contact_ee")
+  const char* supported = "cloth<i>.Kl|Ka|Kb, elastic<i>.mu|lam, k_contact, mu_cloth_elastic, mu_cloth_cloth";
+  // ---- keys -> (class, row): class 0 faces (rows 2 i + {Kl, Ka}), 1 hinges (row i), 2 tets (rows 2 i + {mu, lam}), 3 contact slots (rows k_contact,
+  //      mu_cloth_elastic, mu_cloth_cloth)
+  std::vector<std::array<int, 2>> kr(n_keys);
+  bool need[4] = {false, false, false, false};
+  for (int j = 0; j < n_keys; j++) {
+    if (!keys[j]) return tsl_fail("tsl_param_grad_keys: key %d is null", j);
+    const std::string k(keys[j]);
+    int cls = -1, row = -1;
+    if (k == "k_contact") { cls = 3; row = 0; }
+    else if (k == "mu_cloth_elastic") { cls = 3; row = 1; }
+    else if (k == "mu_cloth_cloth") { cls = 3; row = 2; }
+    else if ((k.rfind("cloth", 0) == 0 || k.rfind("elastic", 0) == 0) && k.find('.') != std::string::npos) {
+      const bool is_cloth = k[0] == 'c';
+      const size_t p0 = is_cloth ? 5 : 7, dot = k.find('.');
+      char* endp = nullptr;
+      const long idx = strtol(k.c_str() + p0, &endp, 10);
+      // (an index is a plain decimal number: no sign other than a minus, no blanks -- "cloth+1.Kl", "cloth 1.Kl" are not keys)
+      const char c0 = k[p0];
+      if (endp != k.c_str() + dot || dot == p0 || !(isdigit((unsigned char)c0) || c0 == '-')) return tsl_fail("tsl_param_grad_keys: bad index in %s", keys[j]);
+      const std::string f = k.substr(dot + 1);
+      if (is_cloth) {
+        if (f == "Kl" || f == "Ka") { cls = 0; row = f == "Kl" ? 0 : 1; }
+        else if (f == "Kb") { cls = 1; row = 0; }
+        if (cls >= 0 && (idx < 0 || idx >= n_cloth)) return tsl_fail("tsl_param_grad_keys: bad cloth index in %s (%d cloths)", keys[j], n_cloth);
+        if (cls == 0) row += 2 * (int)idx; else if (cls == 1) row = (int)idx;
+      } else {
+        if (f == "mu" || f == "lam") { cls = 2; row = f == "mu" ? 0 : 1; }
+        if (cls >= 0 && (idx < 0 || idx >= n_el)) return tsl_fail("tsl_param_grad_keys: bad elastic index in %s (%d bodies)", keys[j], n_el);
+        if (cls == 2) row += 2 * (int)idx;
+      }
+    }
+    if (cls < 0) return tsl_fail("tsl_param_grad_keys: %s is not a differentiated key (supported: %s)", keys[j], supported);
+    if (cls == 3) {
+      if (row == 0 && c->nc_ee > 0)
+        return tsl_fail("tsl_param_grad_keys: k_contact: %d edge-edge constraints (contact_ee = 1) are present; their friction derivative is not implemented", c->nc_ee);
+      const double live = row == 0 ? c->k_contact : (row == 1 ? c->mu_cloth_elastic : c->mu_cloth_cloth);
+      bool used = row == 0;
+      for (const auto& pr : c->h_pairs) used |= pr.mu_is_param == row;
+      if (live == 0.0 && used && nvf > 0)
+        return tsl_fail("tsl_param_grad_keys: %s = 0: the friction weights c_k of the detection vanish with it, their derivative is not available", keys[j]);
+    }
+    if (cls == 1 && !ref) return tsl_fail("tsl_param_grad_keys: %s needs ref_angle", keys[j]);
+    kr[j] = {cls, row};
+    need[cls] = true;
+  }
+  // ---- partial layout: class q holds rows[q] rows of nb[q] partials
+  const int rows[4] = {2 * n_cloth, n_cloth, 2 * n_el, 3};
+  const int nb[4] = {c->n_cface > 0 ? nblk(c->n_cface, PG_THREADS) : 0, c->n_hinge > 0 ? nblk(c->n_hinge, PG_THREADS) : 0, c->n_tet > 0 ? nblk(c->n_tet, PG_THREADS) : 0,
+                     nvf > 0 ? nblk(nvf, PG_THREADS) : 0};
+  size_t off[4], tot = 0;
+  for (int q = 0; q < 4; q++) { off[q] = tot; if (need[q]) tot += (size_t)rows[q] * nb[q]; }
+  if (tot > (size_t)INT32_MAX) return tsl_fail("tsl_param_grad_keys: too many partials");
+  if (c->pg_part.n < std::max<size_t>(tot, 1)) TSL_TRY(c->pg_part.alloc(std::max<size_t>(tot, 1)));
+  if (c->pg_out.n < (size_t)n_keys + 2) TSL_TRY(c->pg_out.alloc((size_t)n_keys + 2));
+  const double* p = p_dev ? p_dev : c->pdir.p;
+  const int* fz = c->frozen.p;
+  double* part = c->pg_part.p;
+  if (need[0] && nb[0]) hipLaunchKernelGGL(k_pg_face, dim3(nb[0]), dim3(PG_THREADS), 0, s, cloth_args(c), n_cloth, pos, p, fz, part + off[0]);
+  if (need[1] && nb[1]) hipLaunchKernelGGL(k_pg_hinge, dim3(nb[1]), dim3(PG_THREADS), 0, s, cloth_args(c), n_cloth, pos, ref, p, fz, part + off[1]);
+  if (need[2] && nb[2]) hipLaunchKernelGGL(k_pg_tet, dim3(nb[2]), dim3(PG_THREADS), 0, s, tet_args(c), n_el, pos, p, fz, part + off[2]);
+  if (need[3] && nb[3])
+    hipLaunchKernelGGL(k_pg_contact, dim3(nb[3]), dim3(PG_THREADS), 0, s, nvf, contact_args(c), (const int*)c->c_kind.p, c->mu_cloth_elastic, c->mu_cloth_cloth, pos, p, fz,
+                       part + off[3]);
+  // the (offset, count) table as kernel arguments, PG_KEYS_PER_LAUNCH keys per launch; the first launch also counts the kinds of the edge-edge
+  // slots -- only when a friction key asks (k_contact with such slots failed above)
+  const int n_ee = need[3] ? c->nc_ee : 0;
+  for (int j0 = 0; j0 < n_keys; j0 += PG_KEYS_PER_LAUNCH) {
+    PgTable tab;
+    tab.n = std::min(PG_KEYS_PER_LAUNCH, n_keys - j0);
+    for (int j = 0; j < tab.n; j++) {
+      const int q = kr[j0 + j][0];
+      tab.off[j] = (int)(off[q] + (size_t)kr[j0 + j][1] * nb[q]);
+      tab.cnt[j] = nb[q];
+    }
+    hipLaunchKernelGGL(k_pg_final, dim3(1), dim3(PG_THREADS), 0, s, tab, (const double*)part, j0 == 0 ? n_ee : 0,
+                       n_ee > 0 ? (const int*)c->c_kind.p + nvf : (const int*)nullptr, c->pg_out.p + j0, j0 == 0 ? c->pg_out.p + n_keys : (double*)nullptr);
+  }
+  HIP_OK(hipGetLastError());
+  std::vector<double> h((size_t)n_keys + 2);
+  HIP_OK(hipMemcpyAsync(h.data(), c->pg_out.p, h.size() * sizeof(double), hipMemcpyDeviceToHost, s));
+  HIP_OK(hipStreamSynchronize(s));
+  for (int j = 0; j < n_keys; j++) {
+    if (kr[j][0] != 3 || kr[j][1] == 0) continue;
+    const double n_kind = h[n_keys + kr[j][1] - 1];
+    if (n_kind > 0)
+      return tsl_fail("tsl_param_grad_keys: %s: %d edge-edge constraints (contact_ee = 1) use it; their friction derivative is not implemented", keys[j], (int)n_kind);
+  }
+  for (int j = 0; j < n_keys; j++) out_host[j] = h[j];
   return 0;
 }
 

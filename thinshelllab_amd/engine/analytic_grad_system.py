@@ -6,6 +6,10 @@ reference class: ``pos_grad`` is clamped to +-1 and nothing else (:104-109), the
 accumulates the parameter gradients ``grad_kb`` / ``grad_mu`` / ``grad_lam`` = sum over the free dofs of
 ``p . d(force)/d(parameter)`` (:69-80, ``tsl_param_grad``) or, with ``count_friction_grad``, the friction-coefficient gradient of
 ``Scene_sliding`` (``contact_energy_backprop_friction``, Scene_sliding.py:139-176, ``tsl_friction_grad``).
+
+Beyond the reference: ``param_keys`` names further scalars, spelled as ``tsl_set_param`` spells them ("cloth<i>.Kl|Ka|Kb",
+"elastic<i>.mu|lam", "k_contact", "mu_cloth_elastic", "mu_cloth_cloth"); every reverse step then adds their
+``p . d(force)/d(key)`` (``tsl_param_grad_keys``) to ``grad_params[key]``.  Empty (the default): no such call, the reference's behaviour.
 """
 import torch
 
@@ -42,6 +46,8 @@ class Grad:
         self.count_friction_grad = False
         self.count_mu_lam_grad = False
         self.count_kb_grad = True
+        self.param_keys = []
+        self.grad_params = {}
         self.last_stats = {}
 
     def reset(self):  # :33-39
@@ -51,6 +57,7 @@ class Grad:
         self.grad_lam[None] = 0
         self.grad_friction_coef[None] = 0
         self.grad_kb[None] = 0
+        self.grad_params = {}
 
     def init_mass(self, sys):  # :41-44
         self.mass.copy_from(sys.mass)
@@ -82,6 +89,7 @@ class Grad:
                 g = dict(kb=0.0, mu=0.0, lam=0.0)
             else:
                 g = ctx.param_grad(self.pos_buffer.t[step], self.ref_angle_buffer.t[step - 1])
+            gp = ctx.param_grads(self.pos_buffer.t[step], self.ref_angle_buffer.t[step - 1], self.param_keys) if self.param_keys else {}
         finally:
             ctx.set_param("adj_clamp", 1000.0); ctx.set_param("adj_clamp_angleref", 1.0)
         if not self.count_friction_grad:
@@ -90,6 +98,8 @@ class Grad:
                 self.grad_lam[None] = self.grad_lam[None] + g["lam"]
             if self.count_kb_grad:
                 self.grad_kb[None] = self.grad_kb[None] + g["kb"]
+        for k, v in gp.items():
+            self.grad_params[k] = self.grad_params.get(k, 0.0) + v
         sys.copy_pos_and_refangle(self, step)
 
     # ---- loss seeds
