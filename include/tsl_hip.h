@@ -90,7 +90,8 @@ typedef struct {
   double rel_residual;           /* true residual |b - Hx| / |b| of the returned solution */
   int32_t method;                /* solver that produced x: 0 PCG, 1 MINRES, 2 GMRES, 3 BiCGStab, 4 sparse LU + iterative refinement (GMRES where that stalls) */
   int32_t attained;              /* 1: accepted by the attainable-accuracy rule instead of rel_residual <= cg_tol */
-  double backward_error;         /* method 4: |b - Hx| / (|H|_inf |x| + |b|) of the returned solution (0 if not evaluated) */
+  double backward_error;         /* method 4: |b - Hx| / (|H|_inf |x| + |b|) of the returned solution (0 if not evaluated); |H|_inf is the norm
+                                    of the static part only (the contact blocks are left out: the value can only overstate the error) */
 } tsl_solve_stats;
 
 const char* tsl_version(void);
@@ -219,6 +220,10 @@ int tsl_param_grad_keys(tsl_ctx* ctx, const double* pos_dev, const double* ref_a
 /* Introspection used by the parity tests (tests/ only): assembled matrix as BSR on the host. */
 int tsl_matrix_nnzb(tsl_ctx* ctx, int32_t* nb_host, int32_t* nnzb_host);
 int tsl_matrix_export(tsl_ctx* ctx, int32_t* row_ptr_host, int32_t* col_host, double* vals_host);
+/* The inverse of tsl_matrix_export (tests/ only): vals_host [nnzb][3][3] in exactly the pattern and order tsl_matrix_export returns
+ * replaces the static part of the operator; the contact blocks of the last detection are kept.  The factors, |H|_inf, the multigrid
+ * operators and a separate preconditioner matrix are marked stale, as tsl_assemble does; the values hold until the next assemble or step. */
+int tsl_matrix_import(tsl_ctx* ctx, const double* vals_host);
 int tsl_constraints_export(tsl_ctx* ctx, int32_t* idx_host, double* w_host, double* k_host, double* dx0_host,
                            double* T_host, double* n_host, double* mu_host, int32_t max_n);
 /* per-constraint dense 12x12 blocks (vertex order idx0..idx3) of the last assemble; masked = frozen rule applied */

@@ -127,9 +127,11 @@ extern "C" int dsref_solve(int NV, const int* row_ptr, const int* col, const dou
   return 0;
 }
 
-// plan statistics for a pattern + constraint set (scripts / tests): prints the batches of the factorisation
+// plan statistics for a pattern + constraint set (scripts / tests): prints the batches of the factorisation.  fronts (may be null: out[0]
+// fronts of DSREF_FRONT_INTS each, in supernode order): {p, b, pp, bp, tree level, children, first own vertex, parent, fronts of its batch, max pp of its batch, second own vertex}
+#define DSREF_FRONT_INTS 11
 extern "C" int dsref_plan_stats(int NV, const int* row_ptr, const int* col, int n_grids, const int* grids, int n_blocks, const int* blocks, int n_cons, const int* cons, int leaf,
-                                int verbose, double* out) {
+                                int verbose, double* out, int* fronts) {
   std::vector<std::vector<int>> adj(NV);
   for (int r = 0; r < NV; r++) adj[r].assign(col + row_ptr[r], col + row_ptr[r + 1]);
   std::vector<int> rp(row_ptr, row_ptr + NV + 1);
@@ -154,6 +156,15 @@ extern "C" int dsref_plan_stats(int NV, const int* row_ptr, const int* col, int 
   double n_ent = 0;   // Schur-complement entries stored per factorisation
   for (const DsFrontDesc& f : P.fr) n_ent += (double)f.b * f.b;
   out[7] = n_ent;
+  if (fronts) {
+    for (int s = 0; s < P.sym.n_sn; s++) {
+      const DsFrontDesc& f = P.fr[s];
+      int* o = fronts + (size_t)DSREF_FRONT_INTS * s;
+      o[0] = f.p; o[1] = f.b; o[2] = f.pp; o[3] = f.bp; o[4] = P.sym.level[s]; o[5] = f.nchild; o[6] = f.nv_own > 0 ? P.vtx[f.vtx_off] : -1; o[7] = f.parent; o[10] = f.nv_own > 1 ? P.vtx[f.vtx_off + 1] : -1;
+    }
+    for (const DsBatch& b : P.batches)
+      for (int q = 0; q < b.count; q++) { int* o = fronts + (size_t)DSREF_FRONT_INTS * P.level_sn[b.first + q]; o[8] = b.count; o[9] = b.max_pp; }
+  }
   out[0] = P.sym.n_sn; out[1] = P.n_levels; out[2] = (double)P.batches.size(); out[3] = steps; out[4] = P.flops; out[5] = (double)P.arena * 8; out[6] = solve_bytes;
   return 0;
 }

@@ -13,8 +13,7 @@ import scipy.sparse.linalg as spla
 HERE = os.path.dirname(os.path.abspath(__file__))
 
 
-@pytest.fixture(scope="module")
-def dsref():
+def dsref_lib():
     src = os.path.join(HERE, "native", "ds_ref.cpp")
     lib = os.path.join(HERE, "native", "libdsref.so")
     deps = [src] + [os.path.join(HERE, "..", "thinshelllab_amd", "csrc", f) for f in ("direct_sym.hpp", "direct_plan.hpp")]
@@ -22,7 +21,77 @@ def dsref():
         subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", src, "-o", lib])
     L = C.CDLL(lib)
     L.dsref_solve.restype = C.c_int
+    L.dsref_plan_stats.restype = C.c_int
     return L
+
+
+@pytest.fixture(scope="module")
+def dsref():
+    return dsref_lib()
+
+
+FRONT_FIELDS = ("p", "b", "pp", "bp", "level", "nchild", "v0", "parent", "batch_count", "batch_max_pp", "v1")
+
+
+def plan_fronts(L, NV, row_ptr, col, grids, leaf, blocks=None):
+    """per-front shape of the multifrontal plan of a pattern (no constraints): an int array [fronts, len(FRONT_FIELDS)] in supernode order,
+    columns FRONT_FIELDS (v0 / v1: the first two own vertices, whose dofs 0..5 open the front's pivot block)"""
+    row_ptr = np.ascontiguousarray(row_ptr, np.int32); col = np.ascontiguousarray(col, np.int32)
+    g = np.ascontiguousarray(grids, np.int32).reshape(-1)
+    bl = np.zeros(2, np.int32) if blocks is None else np.ascontiguousarray(blocks, np.int32).reshape(-1)
+    out = np.zeros(8)
+    a = lambda fr: (NV, row_ptr.ctypes.data_as(C.c_void_p), col.ctypes.data_as(C.c_void_p), len(g) // 3, g.ctypes.data_as(C.c_void_p),
+                    0 if blocks is None else len(bl) // 2, bl.ctypes.data_as(C.c_void_p), 0, None, leaf, 0, out.ctypes.data_as(C.c_void_p), fr)
+    assert L.dsref_plan_stats(*a(None)) == 0
+    F = np.full((int(out[0]), len(FRONT_FIELDS)), -1, np.int32)
+    assert L.dsref_plan_stats(*a(F.ctypes.data_as(C.c_void_p))) == 0
+    return F
+
+
+def drape_pattern(N, M):
+    """block pattern of an N x M cloth grid (vertex rows of the triangle and hinge cliques, sorted), as tsl_matrix_export orders it"""
+    NV = (N + 1) * (M + 1)
+    _, cl = cloth_cliques(N, M)
+    rows = [set([v]) for v in range(NV)]
+    for c in cl:
+        for a in c:
+            rows[a].update(c)
+    rows = [sorted(r) for r in rows]
+    row_ptr = np.zeros(NV + 1, np.int32)
+    row_ptr[1:] = np.cumsum([len(r) for r in rows])
+    return NV, row_ptr, np.concatenate(rows).astype(np.int32)
+
+
+# Drape plans of the first-pass tests (test_gpu_direct_first_pass.py) and the kernel edges each one holds: own dof counts p and boundary sizes b
+# one below / at / one above a multiple of the tile edge DS_T = 32 (the padding of p / b), the root (b = 0), padded pivot counts on both sides
+# of DS_SMALL = 128 (the LDS kernel) and of 512 (the inversion class DS_CLS), and a plan of one front (leaf >= vertices)
+FIRST_PASS_SHAPES = {
+    (100, 60, 256): dict(p_mod={0, 1, 31}, b_mod={1, 31}, pp_le_128=True, pp_128_512=True, pp_gt_512=False),
+    (64, 64, 256): dict(p_mod={31}, b_mod={31}, pp_le_128=True, pp_128_512=True, pp_gt_512=True),
+    (33, 70, 16): dict(p_mod={1, 31}, b_mod={1, 31}, pp_le_128=True, pp_128_512=True, pp_gt_512=False),
+    (20, 20, 500): dict(p_mod=set(), b_mod=set(), pp_le_128=False, pp_128_512=False, pp_gt_512=True, single=True),
+}
+
+
+def check_plan_shape(F, claim):
+    """the plan F (plan_fronts) holds every edge `claim` names"""
+    p, b, pp = F[:, 0], F[:, 1], F[:, 2]
+    assert claim["p_mod"] <= set((p % 32).tolist()), (claim, sorted(set((p % 32).tolist())))
+    assert claim["b_mod"] <= set((b[b > 0] % 32).tolist()), (claim, sorted(set((b[b > 0] % 32).tolist())))
+    assert (b == 0).sum() >= 1 and (F[:, 7] < 0).sum() == (b == 0).sum()       # the root(s): no boundary, no parent
+    assert bool((pp <= 128).any()) == claim["pp_le_128"] and bool(((pp > 128) & (pp <= 512)).any()) == claim["pp_128_512"], (claim, sorted(set(pp.tolist())))
+    assert bool((pp > 512).any()) == claim["pp_gt_512"], (claim, sorted(set(pp.tolist())))
+    assert (len(F) == 1) == claim.get("single", False)
+    assert ((pp % 32) == 0).all() and (pp >= p).all() and (pp - p < 32).all() and ((F[:, 3] % 32) == 0).all() and (F[:, 3] >= b).all()
+
+
+@pytest.mark.parametrize("N,M,leaf", sorted(FIRST_PASS_SHAPES))
+def test_first_pass_plans_hold_their_kernel_edges(dsref, N, M, leaf):
+    """the shapes the first-pass tests claim, checked on the CPU with the product's own plan (direct_plan.hpp): a plan change that drops an
+    edge fails here, not silently on the GPU"""
+    NV, rp, col = drape_pattern(N, M)
+    F = plan_fronts(dsref, NV, rp, col, [0, N, M], leaf)
+    check_plan_shape(F, FIRST_PASS_SHAPES[(N, M, leaf)])
 
 
 def cloth_cliques(N, M, off=0):

@@ -73,7 +73,7 @@ class SolveStats(C.Structure):
 EXPORTS = [
     "tsl_version", "tsl_last_error", "tsl_ctx_create", "tsl_ctx_destroy", "tsl_set_stream", "tsl_set_param", "tsl_set_frozen",
     "tsl_set_ext_force", "tsl_set_gravity", "tsl_energy", "tsl_assemble", "tsl_solve", "tsl_step", "tsl_contact_detect",
-    "tsl_contact_reset", "tsl_contact_counts", "tsl_update_ref_angle", "tsl_adjoint_step", "tsl_param_grad", "tsl_param_grad_keys", "tsl_friction_grad", "tsl_elastic_force", "tsl_matrix_nnzb", "tsl_matrix_export",
+    "tsl_contact_reset", "tsl_contact_counts", "tsl_update_ref_angle", "tsl_adjoint_step", "tsl_param_grad", "tsl_param_grad_keys", "tsl_friction_grad", "tsl_elastic_force", "tsl_matrix_nnzb", "tsl_matrix_export", "tsl_matrix_import",
     "tsl_constraints_export", "tsl_contact_blocks_export", "tsl_proj_export", "tsl_proj_import", "tsl_set_border", "tsl_spd_project", "tsl_profile_reset", "tsl_profile_read", "tsl_profile_read_events",
     "tsl_bench_spmv", "tsl_bench_direct", "tsl_direct_info", "tsl_direct_counters",
     "tsl_group_create", "tsl_group_destroy", "tsl_group_step", "tsl_group_adjoint_step", "tsl_group_info",
@@ -120,6 +120,7 @@ def load():
                                    C.POINTER(SolveStats)]
     L.tsl_matrix_nnzb.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     L.tsl_matrix_export.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.tsl_matrix_import.argtypes = [C.c_void_p, C.c_void_p]
     L.tsl_constraints_export.argtypes = [C.c_void_p] + [C.c_void_p] * 7 + [C.c_int32]
     L.tsl_contact_blocks_export.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32]
     L.tsl_proj_export.argtypes = [C.c_void_p] + [C.c_void_p] * 4

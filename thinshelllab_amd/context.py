@@ -197,6 +197,13 @@ class TslContext:
         check(self.L.tsl_matrix_export(self.h, rp.ctypes.data, col.ctypes.data, vals.ctypes.data), "tsl_matrix_export")
         return rp, col, vals
 
+    def matrix_import(self, vals):
+        """write vals[nnzb,3,3] -- the pattern and order of matrix() -- into the static part of the operator (until the next assemble or step)"""
+        rp, col, _ = self.matrix()
+        v = np.ascontiguousarray(vals, dtype=np.float64)
+        assert v.shape == (len(col), 3, 3), (v.shape, len(col))
+        check(self.L.tsl_matrix_import(self.h, v.ctypes.data), "tsl_matrix_import")
+
     def matrix_csr(self):
         import scipy.sparse as sp
         rp, col, vals = self.matrix()

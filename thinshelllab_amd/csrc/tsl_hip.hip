@@ -811,6 +811,9 @@ extern "C" int tsl_assemble(tsl_ctx* c, const double* pos, const double* prev, c
   Scope scope(c);
   c->bd_valid = false;
   c->mg_omega_valid = false; c->mg_cinv_valid = false;
+  // an assembly from outside a step may hold any operator (a new scene state, a new scale): the backward errors of its solves are measured
+  // against its own |H|_inf, not one kept from an earlier assembly (the 64-factorisation cache is for the Newton iterations inside tsl_step)
+  c->ds.anorm_valid = false;
   return assemble(c, pos, prev, vel, ref, spd, grad);
 }
 
@@ -2672,6 +2675,28 @@ extern "C" int tsl_matrix_export(tsl_ctx* c, int32_t* row_ptr, int32_t* col, dou
     }
     row_ptr[v + 1] = (int32_t)k;
   }
+  return 0;
+}
+
+// the inverse of tsl_matrix_export: BSR values in exactly the pattern and order it returns, written into the SELL layout of the static
+// part; the contact blocks of the last detection stay as they are.  Everything built from the values is marked stale, as an assembly does.
+extern "C" int tsl_matrix_import(tsl_ctx* c, const double* vals) {
+  Scope scope(c);
+  HIP_OK(hipStreamSynchronize(c->stream));
+  std::vector<double> hv(c->vals.n);
+  HIP_OK(hipMemcpy(hv.data(), c->vals.p, hv.size() * sizeof(double), hipMemcpyDeviceToHost));
+  long k = 0;
+  for (int v = 0; v < c->NV; v++) {
+    const int p = c->h_rowpos[v], s = p >> 6, lane = p & 63;
+    for (size_t j = 0; j < c->h_rows[v].size(); j++, k++) {
+      const size_t base = ((size_t)c->h_slice_off[s] + 64 * j) * 9 + lane;
+      for (int e = 0; e < 9; e++) hv[base + 64 * e] = vals[9 * k + e];
+    }
+  }
+  HIP_OK(hipMemcpy(c->vals.p, hv.data(), hv.size() * sizeof(double), hipMemcpyHostToDevice));
+  c->ds.numeric_valid = false; c->ds.anorm_valid = false;
+  c->mg_ops_valid = false; c->pc_separate = false;
+  c->bd_valid = false; c->mg_omega_valid = false; c->mg_cinv_valid = false;
   return 0;
 }
 
