@@ -106,6 +106,12 @@ int tsl_set_stream(tsl_ctx* ctx, void* hip_stream);
 /* 0-d field writes of the reference and the engine's own switches (41 keys + three patterns; an unknown key is an error).
  *  Scene (trajopt_folding.py:50,66; Scene_folding.py:30-31; geometry.py:8-19; geometry_self.py:166-230):
  *   "cloth<i>.Kb|Kl|Ka|k_angle", "elastic<i>.mu|lam|alpha", "mu_cloth_elastic", "mu_cloth_cloth", "k_contact", "eps_contact", "eps_v", "damping",
+ *   "cloth<i>.membrane" (0 default: edge springs Kl + area term Ka, as the reference; 1: a St. Venant-Kirchhoff membrane per face, A0 Psi(F) with
+ *   F = [x1 - x0, x2 - x0] Dm^-1, Dm the rest triangle rebuilt from the face's rest lengths (fails naming a face whose lengths violate the triangle
+ *   inequality), Psi = mu |E|^2 + lam/2 tr(E)^2, E = (F^T F - I) / 2, A0 the rest area; it replaces the springs and the area term of the cloth's
+ *   faces, bending / inertia / contact unchanged; spd 1 clamps the 6 x 6 d2Psi/dF2 by eigen-clamp, "spd_literal" does not apply to it; any value but
+ *   0 / 1 fails), "cloth<i>.stvk_mu", "cloth<i>.stvk_lam" (its Lame parameters in N/m, default 0; Kl / Ka of a StVK cloth are kept unused, as are
+ *   stvk_* of a spring cloth; switching at any time keeps the block pattern and the plans of the factorisation),
  *   "newton_cap", "plastic", "contact" (0: no detection in tsl_step), "grid_h", "grid_extent" (broad-phase cell and box), "self_contact<body>"
  *   (0 / 1: the body's vertices are also projected onto its own triangles), "contact_ee" (0 default: vertex-triangle contact only, as the reference;
  *   1: edge-edge constraints between the surface edges of different bodies are appended behind the vertex-triangle ones, see tsl_contact_counts), "adj_clamp", "adj_clamp_angleref" (the clamping of analytic_grad_single:
@@ -202,7 +208,8 @@ int tsl_friction_grad(tsl_ctx* ctx, const double* pos_dev, double* out_host);
 /* d(loss)/d(theta) contributions of one reverse step for any of the material and contact scalars: out_host[j] = sum over the free dofs of
  * p . d(force)/d(theta_j) (force = -F, F the gradient tsl_assemble forms: the sign of tsl_param_grad, whose kb is the sum of the "cloth<i>.Kb"
  * values), theta_j = the value tsl_set_param(keys[j]) sets, every other key held fixed.
- * Keys: "cloth<i>.Kl", "cloth<i>.Ka", "cloth<i>.Kb", "elastic<i>.mu", "elastic<i>.lam" (both material models, alpha fixed), "k_contact" (normal
+ * Keys: "cloth<i>.Kl", "cloth<i>.Ka", "cloth<i>.Kb", "cloth<i>.stvk_mu", "cloth<i>.stvk_lam" (StVK membrane, "cloth<i>.membrane" = 1), "elastic<i>.mu",
+ * "elastic<i>.lam" (both material models, alpha fixed), "k_contact" (normal
  * term of every vertex-triangle slot and the friction weights c_k = -mu k_contact (gap - eps) of the detection), "mu_cloth_elastic",
  * "mu_cloth_cloth" (friction of the slots whose pair uses that live parameter, the pair's factor kept: d c_k = c_k / mu_live).
  * p_dev == NULL: the solution of the last tsl_adjoint_step (as tsl_param_grad uses it); otherwise any 3*tot_NV vector (original vertex order).
@@ -212,6 +219,7 @@ int tsl_friction_grad(tsl_ctx* ctx, const double* pos_dev, double* out_host);
  * a body index out of range, "k_contact" while edge-edge constraints ("contact_ee" = 1) are present, "mu_cloth_*" while an edge-edge
  * constraint of that parameter is present (their friction derivative is not implemented), and a contact key whose live value is 0 (the
  * derivative exists there, but the detection records c_k vanish with the value and cannot carry it: start a fit from a small nonzero value).
+ * A key that does not enter F is exactly 0: "stvk_*" of a cloth with membrane = 0, "Kl" / "Ka" of a cloth with membrane = 1.
  * Deterministic: per-workgroup partials per key joined in a fixed order, a key's value is the same bits whichever other keys are asked for.
  * One device-to-host copy and one stream synchronisation per call. */
 int tsl_param_grad_keys(tsl_ctx* ctx, const double* pos_dev, const double* ref_angle_dev, const double* p_dev, const char* const* keys,

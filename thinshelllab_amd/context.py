@@ -177,7 +177,7 @@ class TslContext:
 
     def param_grads(self, pos, ref_angle, keys, p=None):
         """{key: sum over the free dofs of p . d(force)/d(key)} at the tape state pos (tsl_param_grad_keys): keys as tsl_set_param spells them
-        ("cloth<i>.Kl|Ka|Kb", "elastic<i>.mu|lam", "k_contact", "mu_cloth_elastic", "mu_cloth_cloth"); p None: the solution of the last
+        ("cloth<i>.Kl|Ka|Kb|stvk_mu|stvk_lam", "elastic<i>.mu|lam", "k_contact", "mu_cloth_elastic", "mu_cloth_cloth"); p None: the solution of the last
         adjoint_step, else a 3 * tot_NV device vector"""
         keys = list(keys)
         if not keys:

@@ -90,6 +90,47 @@ TSL_DEV double cface_energy(const ClothDev& c, const d3 P[3], double V, const do
   return e;
 }
 
+// ---------------------------------------------------------------------------------------------
+// St. Venant-Kirchhoff membrane of a face (no counterpart in the reference, which has the springs and the area term above):
+//   F = [x1 - x0, x2 - x0] Dm^-1 (3 x 2), E = (F^T F - I) / 2, Psi = mu |E|_F^2 + lam/2 tr(E)^2, face energy A0 Psi with A0 = V[f];
+//   Dm is the rest triangle rebuilt from the three rest lengths (stvk_prepare in tsl_hip.hip).  tests/stvk_numpy.py restates every term here.
+// Column j of F is f_j = sum_v b_vj x_v with b_1j = Dm^-1[0][j], b_2j = Dm^-1[1][j], b_0j = -(b_1j + b_2j): the 6 x 9 map B of the Hessian.
+struct StvkFace {
+  d3 f[2];          // columns of F
+  double b[3][2];   // b[v][j]
+  double E00, E01, E11;
+};
+TSL_DEV StvkFace stvk_face(const d3 P[3], const double* __restrict__ Di) {
+  StvkFace s;
+  const double d00 = Di[0], d01 = Di[1], d10 = Di[2], d11 = Di[3];
+  const d3 e1 = P[1] - P[0], e2 = P[2] - P[0];
+  s.f[0] = e1 * d00 + e2 * d10;
+  s.f[1] = e1 * d01 + e2 * d11;
+  s.b[1][0] = d00; s.b[1][1] = d01; s.b[2][0] = d10; s.b[2][1] = d11;
+  s.b[0][0] = -(d00 + d10); s.b[0][1] = -(d01 + d11);
+  s.E00 = 0.5 * (dot(s.f[0], s.f[0]) - 1.0);
+  s.E01 = 0.5 * dot(s.f[0], s.f[1]);
+  s.E11 = 0.5 * (dot(s.f[1], s.f[1]) - 1.0);
+  return s;
+}
+TSL_DEV double stvk_psi(const StvkFace& s, double mu, double lam) {
+  const double tr = s.E00 + s.E11;
+  return mu * (s.E00 * s.E00 + 2.0 * s.E01 * s.E01 + s.E11 * s.E11) + 0.5 * lam * tr * tr;
+}
+// gradient A0 F S Dm^-T, S = 2 mu E + lam tr(E) I: vertex v receives A0 sum_j b_vj (F S)_j
+TSL_DEV void stvk_grad(const StvkFace& s, double mu, double lam, double A0, d3 g[3]) {
+  const double tr = s.E00 + s.E11;
+  const double S00 = 2.0 * mu * s.E00 + lam * tr, S01 = 2.0 * mu * s.E01, S11 = 2.0 * mu * s.E11 + lam * tr;
+  const d3 P0 = s.f[0] * S00 + s.f[1] * S01, P1 = s.f[0] * S01 + s.f[1] * S11;
+#pragma unroll
+  for (int v = 0; v < 3; v++) g[v] = (P0 * s.b[v][0] + P1 * s.b[v][1]) * A0;
+}
+// per-face membrane energy of the <STVK> kernels: StVK for a cloth with membrane = 1, else cface_energy unchanged
+TSL_DEV double cface_energy_sel(const ClothDev& c, const double* __restrict__ st, const double* __restrict__ Di, const d3 P[3], double V, const double* li) {
+  if (st[0] != 0.0) return V * stvk_psi(stvk_face(P, Di), st[1], st[2]);
+  return cface_energy(c, P, V, li);
+}
+
 struct ClothArgs {
   int n_cface, n_hinge;
   const ClothDev* cloth;
@@ -102,6 +143,13 @@ struct ClothArgs {
   // vertex in a fixed order
   double* gstage;
   int gs_hinge;
+};
+// StVK membrane ("cloth<i>.membrane" = 1): per cloth {membrane, mu, lam, 0}, per face Dm^-1 (row-major 2 x 2).  The face kernels take it as their
+// LAST argument (the arguments before it keep their offsets) and read it only in the <STVK = true> instantiations, which run only while some cloth
+// of the context has membrane = 1 (both tables exist then)
+struct StvkArgs {
+  const double* stvk;
+  const double* dminv;
 };
 
 // hinge energy (Cloth.compute_bending_energy :108-120)
@@ -117,7 +165,10 @@ TSL_DEV double hinge_energy(const ClothArgs& A, int h, const double* __restrict_
 // ---------------------------------------------------------------------------------------------
 // gradient: per face (edges + area, Cloth.compute_residual :653-677), per hinge (:679-687)
 // (k_param.hpp restates both terms per unit Kl / Ka / Kb for tsl_param_grad_keys: a change here goes there too)
-__global__ void k_cloth_grad_face(ClothArgs A, const double* __restrict__ pos) {
+// STVK (launched only while some cloth has membrane = 1): the faces of such cloths take the StVK gradient instead of the springs and the area term.
+// S is the last argument: the <false> instantiation reads its other arguments at the offsets of the springs-only engine
+template <bool STVK = false>
+__global__ void k_cloth_grad_face(ClothArgs A, const double* __restrict__ pos, StvkArgs S) {
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= A.n_cface) return;
   const int f = A.f_order[t];
@@ -125,6 +176,15 @@ __global__ void k_cloth_grad_face(ClothArgs A, const double* __restrict__ pos) {
   int v[3]; d3 P[3];
   load_face(pos, A.f2v, f, v, P);
   d3 g[3] = {d3(), d3(), d3()};
+  if constexpr (STVK) {
+    const double* st = S.stvk + 4 * A.cid[f];
+    if (st[0] != 0.0) {
+      stvk_grad(stvk_face(P, S.dminv + 4 * f), st[1], st[2], A.V[f], g);
+#pragma unroll
+      for (int l = 0; l < 3; l++) st3(A.gstage, 3 * f + l, g[l]);
+      return;
+    }
+  }
 #pragma unroll
   for (int l = 0; l < 3; l++) {
     const int m = (l + 1) % 3;
@@ -212,9 +272,14 @@ __global__ void k_cloth_quirk(ClothArgs A, int n_cloth, const double* __restrict
 // CLAMP_ALL: the whole 9x9 face block (springs + un-projected area and bending parts) is projected as well -- used only to
 // build an SPD preconditioner when the reference's partially projected Hessian turns out indefinite.
 // LIT ("spd_literal" = 1, spd 1 only): the spring blocks are projected by the reference's own projector (spd_literal3, K = 10) instead of the eigen-clamp.
-template <bool CLAMP_ALL, bool LIT = false>
+// STVK (launched only while some cloth has membrane = 1): the faces of such cloths take the StVK block A0 B^T (d2Psi/dF2) B in place of the
+// springs and the area term; bending is unchanged.  spd 1 and 2 clamp the 6 x 6 d2Psi/dF2 in the lane (spd_clamp<6>), which makes the 9 x 9 block
+// PSD without a 9 x 9 eigen-solve; spd 2 then projects the whole face block as for the springs.  LIT does not apply to the StVK block (the
+// reference has none): it keeps the eigen-clamp there.
+template <bool CLAMP_ALL, bool LIT = false, bool STVK = false>
 __global__ void __launch_bounds__(128)
-k_cloth_hess_face(ClothArgs A, const double* __restrict__ pos, const double* __restrict__ ref_angle, const double* __restrict__ Q, int spd, double* __restrict__ rec) {
+k_cloth_hess_face(ClothArgs A, const double* __restrict__ pos, const double* __restrict__ ref_angle, const double* __restrict__ Q, int spd, double* __restrict__ rec,
+                  StvkArgs S) {
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= A.n_cface) return;
   const int f = A.f_order[t];
@@ -226,83 +291,126 @@ k_cloth_hess_face(ClothArgs A, const double* __restrict__ pos, const double* __r
 #pragma unroll
   for (int i = 0; i < 81; i++) L[i] = 0;
 
-  // ---- edge springs: K = dl * G + dl2 * d d^T ; G_jj = (1 - d_j^2)/len, G_jk = + d_j d_k / len (sign as in :292-294)
+  bool springs = true;
+  if constexpr (STVK) {
+    const double* st = S.stvk + 4 * cid;
+    if (st[0] != 0.0) {
+      springs = false;
+      const double mu = st[1], lam = st[2];
+      const StvkFace s = stvk_face(P, S.dminv + 4 * f);
+      const double tr = s.E00 + s.E11;
+      const double Sp[4] = {2.0 * mu * s.E00 + lam * tr, 2.0 * mu * s.E01, 2.0 * mu * s.E01, 2.0 * mu * s.E11 + lam * tr};   // second Piola-Kirchhoff stress
+      const double fa[2][3] = {{s.f[0].x, s.f[0].y, s.f[0].z}, {s.f[1].x, s.f[1].y, s.f[1].z}};
+      // d2Psi / df_i df_k (rows i a, columns k b) = S_ki d_ab + mu f_k[a] f_i[b] + mu d_ik (F F^T)_ab + lam f_i[a] f_k[b]
+      double M[36];
 #pragma unroll
-  for (int l = 0; l < 3; l++) {
-    const int m = (l + 1) % 3;
-    const d3 delta = P[l] - P[m];
-    const double len = norm(delta);
-    const d3 d = delta / len;
-    const double base = A.li[3 * f + l];
-    const double dl = -c.Kl * 2.0 * (1.0 - len / base);
-    const double dl2 = c.Kl * 2.0 / base;
-    double K[9];
-    const double dd[3] = {d.x, d.y, d.z};
+      for (int i = 0; i < 2; i++)
 #pragma unroll
-    for (int j = 0; j < 3; j++)
+        for (int a = 0; a < 3; a++)
 #pragma unroll
-      for (int k = 0; k < 3; k++) {
-        const double G = (j == k) ? (1.0 - dd[j] * dd[j]) / len : dd[j] * dd[k] / len;
-        K[j * 3 + k] = dl * G + dl2 * dd[j] * dd[k];
-      }
-    if (spd) {
-      if constexpr (LIT) spd_literal3<10>(K);
-      else spd_clamp<3>(K);
+          for (int k = 0; k < 2; k++)
+#pragma unroll
+            for (int b = 0; b < 3; b++) {
+              double m = mu * fa[k][a] * fa[i][b] + lam * fa[i][a] * fa[k][b];
+              if (a == b) m += Sp[k * 2 + i];
+              if (i == k) m += mu * (fa[0][a] * fa[0][b] + fa[1][a] * fa[1][b]);
+              M[(i * 3 + a) * 6 + k * 3 + b] = m;
+            }
+      if (spd) spd_clamp<6>(M);
+      const double A0 = A.V[f];
+#pragma unroll
+      for (int l = 0; l < 3; l++)
+#pragma unroll
+        for (int m = 0; m < 3; m++) {
+          const double w00 = A0 * s.b[l][0] * s.b[m][0], w01 = A0 * s.b[l][0] * s.b[m][1], w10 = A0 * s.b[l][1] * s.b[m][0], w11 = A0 * s.b[l][1] * s.b[m][1];
+#pragma unroll
+          for (int j = 0; j < 3; j++)
+#pragma unroll
+            for (int k = 0; k < 3; k++)
+              L[(l * 3 + j) * 9 + m * 3 + k] = w00 * M[j * 6 + k] + w01 * M[j * 6 + 3 + k] + w10 * M[(3 + j) * 6 + k] + w11 * M[(3 + j) * 6 + 3 + k];
+        }
     }
-#pragma unroll
-    for (int j = 0; j < 3; j++)
-#pragma unroll
-      for (int k = 0; k < 3; k++) {
-        const double kv = K[j * 3 + k];
-        L[(l * 3 + j) * 9 + l * 3 + k] += kv;
-        L[(l * 3 + j) * 9 + m * 3 + k] -= kv;
-        L[(m * 3 + j) * 9 + l * 3 + k] -= kv;
-        L[(m * 3 + j) * 9 + m * 3 + k] += kv;
-      }
   }
 
-  // ---- area term: darea2 g g^T + darea * d2A, d2A from  A = |N|/2, N = sum_l x_l x x_{l+1}:
-  //   d2A_lm = 1/2 [ ((e_l.e_m) I - e_m e_l^T - 4 g_l g_m^T)/|N| + sigma_lm [n]x ],  e_l = x_{l+2} - x_{l+1},
-  //   sigma = +1 (m = l+2), -1 (m = l+1), 0 (m = l); minus the reference's factor-2 slip in compute_area_dxy_p12 (:369)
-  //   on the (l != m, j != k) entries.
-  {
-    const d3 Nn = cross(P[1] - P[0], P[2] - P[0]);
-    const double nN = norm(Nn);
-    const double area = 0.5 * nN;
-    const double base_area = A.V[f];
-    const double da = -c.Ka * 2.0 * (1.0 - area / base_area);
-    const double da2 = c.Ka * 2.0 / base_area;
-    const d3 nh = Nn / nN;
-    d3 e[3], g[3];
+  if (springs) {
+    // ---- edge springs: K = dl * G + dl2 * d d^T ; G_jj = (1 - d_j^2)/len, G_jk = + d_j d_k / len (sign as in :292-294)
 #pragma unroll
-    for (int l = 0; l < 3; l++) { e[l] = P[(l + 2) % 3] - P[(l + 1) % 3]; g[l] = 0.5 * cross(nh, e[l]); }
-    const double nx[9] = {0, -nh.z, nh.y, nh.z, 0, -nh.x, -nh.y, nh.x, 0};
-    const double a2 = 2.0 * area, a2c = a2 * a2 * a2;
+    for (int l = 0; l < 3; l++) {
+      const int m = (l + 1) % 3;
+      const d3 delta = P[l] - P[m];
+      const double len = norm(delta);
+      const d3 d = delta / len;
+      const double base = A.li[3 * f + l];
+      const double dl = -c.Kl * 2.0 * (1.0 - len / base);
+      const double dl2 = c.Kl * 2.0 / base;
+      double K[9];
+      const double dd[3] = {d.x, d.y, d.z};
 #pragma unroll
-    for (int l = 0; l < 3; l++)
+      for (int j = 0; j < 3; j++)
 #pragma unroll
-      for (int m = 0; m < 3; m++) {
-        const double elm = dot(e[l], e[m]);
-        const double sigma = (m == l) ? 0.0 : ((m == (l + 2) % 3) ? 1.0 : -1.0);
-        const double el[3] = {e[l].x, e[l].y, e[l].z}, em[3] = {e[m].x, e[m].y, e[m].z};
-        const double gl[3] = {g[l].x, g[l].y, g[l].z}, gm[3] = {g[m].x, g[m].y, g[m].z};
-        const int o = 3 - l - m;  // third vertex when l != m
-#pragma unroll
-        for (int j = 0; j < 3; j++)
-#pragma unroll
-          for (int k = 0; k < 3; k++) {
-            double h2 = 0.5 * ((((j == k) ? elm : 0.0) - em[j] * el[k] - 4.0 * gl[j] * gm[k]) / nN + sigma * nx[j * 3 + k]);
-            if (l != m && j != k) {
-              const d3 p1 = P[l], p2 = P[m], p3 = P[o];
-              const int d2 = 3 - j - k;
-              const double Cjk = (p2[j] - p1[j]) * (p3[k] - p1[k]) - (p3[j] - p1[j]) * (p2[k] - p1[k]);
-              const double Cjd = (p2[j] - p1[j]) * (p3[d2] - p1[d2]) - (p3[j] - p1[j]) * (p2[d2] - p1[d2]);
-              const double S = (p2[k] - p3[k]) * Cjk + (p2[d2] - p3[d2]) * Cjd;
-              h2 -= 0.5 * (p1[j] - p3[j]) * Cjk * S / a2c;
-            }
-            L[(l * 3 + j) * 9 + m * 3 + k] += da2 * gl[j] * gm[k] + da * h2;
-          }
+        for (int k = 0; k < 3; k++) {
+          const double G = (j == k) ? (1.0 - dd[j] * dd[j]) / len : dd[j] * dd[k] / len;
+          K[j * 3 + k] = dl * G + dl2 * dd[j] * dd[k];
+        }
+      if (spd) {
+        if constexpr (LIT) spd_literal3<10>(K);
+        else spd_clamp<3>(K);
       }
+#pragma unroll
+      for (int j = 0; j < 3; j++)
+#pragma unroll
+        for (int k = 0; k < 3; k++) {
+          const double kv = K[j * 3 + k];
+          L[(l * 3 + j) * 9 + l * 3 + k] += kv;
+          L[(l * 3 + j) * 9 + m * 3 + k] -= kv;
+          L[(m * 3 + j) * 9 + l * 3 + k] -= kv;
+          L[(m * 3 + j) * 9 + m * 3 + k] += kv;
+        }
+    }
+
+    // ---- area term: darea2 g g^T + darea * d2A, d2A from  A = |N|/2, N = sum_l x_l x x_{l+1}:
+    //   d2A_lm = 1/2 [ ((e_l.e_m) I - e_m e_l^T - 4 g_l g_m^T)/|N| + sigma_lm [n]x ],  e_l = x_{l+2} - x_{l+1},
+    //   sigma = +1 (m = l+2), -1 (m = l+1), 0 (m = l); minus the reference's factor-2 slip in compute_area_dxy_p12 (:369)
+    //   on the (l != m, j != k) entries.
+    {
+      const d3 Nn = cross(P[1] - P[0], P[2] - P[0]);
+      const double nN = norm(Nn);
+      const double area = 0.5 * nN;
+      const double base_area = A.V[f];
+      const double da = -c.Ka * 2.0 * (1.0 - area / base_area);
+      const double da2 = c.Ka * 2.0 / base_area;
+      const d3 nh = Nn / nN;
+      d3 e[3], g[3];
+#pragma unroll
+      for (int l = 0; l < 3; l++) { e[l] = P[(l + 2) % 3] - P[(l + 1) % 3]; g[l] = 0.5 * cross(nh, e[l]); }
+      const double nx[9] = {0, -nh.z, nh.y, nh.z, 0, -nh.x, -nh.y, nh.x, 0};
+      const double a2 = 2.0 * area, a2c = a2 * a2 * a2;
+#pragma unroll
+      for (int l = 0; l < 3; l++)
+#pragma unroll
+        for (int m = 0; m < 3; m++) {
+          const double elm = dot(e[l], e[m]);
+          const double sigma = (m == l) ? 0.0 : ((m == (l + 2) % 3) ? 1.0 : -1.0);
+          const double el[3] = {e[l].x, e[l].y, e[l].z}, em[3] = {e[m].x, e[m].y, e[m].z};
+          const double gl[3] = {g[l].x, g[l].y, g[l].z}, gm[3] = {g[m].x, g[m].y, g[m].z};
+          const int o = 3 - l - m;  // third vertex when l != m
+#pragma unroll
+          for (int j = 0; j < 3; j++)
+#pragma unroll
+            for (int k = 0; k < 3; k++) {
+              double h2 = 0.5 * ((((j == k) ? elm : 0.0) - em[j] * el[k] - 4.0 * gl[j] * gm[k]) / nN + sigma * nx[j * 3 + k]);
+              if (l != m && j != k) {
+                const d3 p1 = P[l], p2 = P[m], p3 = P[o];
+                const int d2 = 3 - j - k;
+                const double Cjk = (p2[j] - p1[j]) * (p3[k] - p1[k]) - (p3[j] - p1[j]) * (p2[k] - p1[k]);
+                const double Cjd = (p2[j] - p1[j]) * (p3[d2] - p1[d2]) - (p3[j] - p1[j]) * (p2[d2] - p1[d2]);
+                const double S = (p2[k] - p3[k]) * Cjk + (p2[d2] - p3[d2]) * Cjd;
+                h2 -= 0.5 * (p1[j] - p3[j]) * Cjk * S / a2c;
+              }
+              L[(l * 3 + j) * 9 + m * 3 + k] += da2 * gl[j] * gm[k] + da * h2;
+            }
+        }
+    }
   }
 
   // ---- bending, second-order part (literal structure of :585-614)

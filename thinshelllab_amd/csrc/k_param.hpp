@@ -38,35 +38,66 @@ TSL_DEV void pg_block_write(const double v[NK], int g, int n_group, double* __re
   }
 }
 
-// faces: {Kl, Ka} of cloth cid[f] -- the spring and area terms of k_cloth_grad_face with Kl = Ka = 1
+// faces: {Kl, Ka} of cloth cid[f] -- the spring and area terms of k_cloth_grad_face with Kl = Ka = 1.  STVK (some cloth has membrane = 1): the faces
+// of such cloths have no spring or area term and add exact zeros
+template <bool STVK = false>
 __global__ void __launch_bounds__(PG_THREADS) k_pg_face(ClothArgs A, int n_cloth, const double* __restrict__ pos, const double* __restrict__ p,
-                                                        const int* __restrict__ frozen, double* __restrict__ part) {
+                                                        const int* __restrict__ frozen, double* __restrict__ part, StvkArgs S) {
   __shared__ double sm[PG_THREADS / 64];
   const int f = blockIdx.x * blockDim.x + threadIdx.x;
   double v[2] = {0.0, 0.0};
   int g = -1;
   if (f < A.n_cface) {
     g = A.cid[f];
-    int vi[3]; d3 P[3];
-    load_face(pos, A.f2v, f, vi, P);
-    d3 gl[3] = {d3(), d3(), d3()};
+    if (!STVK || S.stvk[4 * g] == 0.0) {
+      int vi[3]; d3 P[3];
+      load_face(pos, A.f2v, f, vi, P);
+      d3 gl[3] = {d3(), d3(), d3()};
 #pragma unroll
-    for (int l = 0; l < 3; l++) {
-      const int m = (l + 1) % 3;
-      const d3 delta = P[l] - P[m];
-      const double len = norm(delta);
-      const d3 t = delta * (-2.0 * (1.0 - len / A.li[3 * f + l]) / len);
-      gl[l] = gl[l] + t;
-      gl[m] = gl[m] - t;
+      for (int l = 0; l < 3; l++) {
+        const int m = (l + 1) % 3;
+        const d3 delta = P[l] - P[m];
+        const double len = norm(delta);
+        const d3 t = delta * (-2.0 * (1.0 - len / A.li[3 * f + l]) / len);
+        gl[l] = gl[l] + t;
+        gl[m] = gl[m] - t;
+      }
+      const d3 Nn = cross(P[1] - P[0], P[2] - P[0]);
+      const double nN = norm(Nn);
+      const double da = -2.0 * (1.0 - 0.5 * nN / A.V[f]);
+      const d3 nh = Nn / nN;
+#pragma unroll
+      for (int l = 0; l < 3; l++) {
+        v[0] -= pg_dot_free(p, frozen, vi[l], gl[l]);
+        v[1] -= pg_dot_free(p, frozen, vi[l], da * (0.5 * cross(nh, P[(l + 2) % 3] - P[(l + 1) % 3])));
+      }
     }
-    const d3 Nn = cross(P[1] - P[0], P[2] - P[0]);
-    const double nN = norm(Nn);
-    const double da = -2.0 * (1.0 - 0.5 * nN / A.V[f]);
-    const d3 nh = Nn / nN;
+  }
+  pg_block_write<2>(v, g, n_cloth, part, sm);
+}
+
+// faces: {stvk_mu, stvk_lam} of cloth cid[f] -- the StVK gradient of k_cloth_grad_face<true> with (mu, lam) = (1, 0) and (0, 1); faces of cloths
+// with membrane = 0 add exact zeros
+__global__ void __launch_bounds__(PG_THREADS) k_pg_stvk(ClothArgs A, int n_cloth, const double* __restrict__ pos, const double* __restrict__ p,
+                                                        const int* __restrict__ frozen, double* __restrict__ part, StvkArgs S) {
+  __shared__ double sm[PG_THREADS / 64];
+  const int f = blockIdx.x * blockDim.x + threadIdx.x;
+  double v[2] = {0.0, 0.0};
+  int g = -1;
+  if (f < A.n_cface) {
+    g = A.cid[f];
+    if (S.stvk[4 * g] != 0.0) {
+      int vi[3]; d3 P[3];
+      load_face(pos, A.f2v, f, vi, P);
+      const StvkFace s = stvk_face(P, S.dminv + 4 * f);
+      d3 gm[3], gl[3];
+      stvk_grad(s, 1.0, 0.0, A.V[f], gm);
+      stvk_grad(s, 0.0, 1.0, A.V[f], gl);
 #pragma unroll
-    for (int l = 0; l < 3; l++) {
-      v[0] -= pg_dot_free(p, frozen, vi[l], gl[l]);
-      v[1] -= pg_dot_free(p, frozen, vi[l], da * (0.5 * cross(nh, P[(l + 2) % 3] - P[(l + 1) % 3])));
+      for (int l = 0; l < 3; l++) {
+        v[0] -= pg_dot_free(p, frozen, vi[l], gm[l]);
+        v[1] -= pg_dot_free(p, frozen, vi[l], gl[l]);
+      }
     }
   }
   pg_block_write<2>(v, g, n_cloth, part, sm);

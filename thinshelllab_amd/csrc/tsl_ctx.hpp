@@ -235,6 +235,11 @@ struct tsl_ctx {
   DevBuf<double> norm_dir;                      // n_cface x 3
   DevBuf<double> quirk;                         // n_cloth x 3 faces x 3 slots x 10 (c_i, mat_N)
   std::vector<int> h_cf_f2v, h_cf_cf, h_cf_cp;
+  // StVK membrane ("cloth<i>.membrane" / "stvk_mu" / "stvk_lam", k_cloth.hpp): per cloth {membrane, mu, lam, 0} (allocated at the first such key),
+  // per face Dm^-1 (4 doubles, built from cf_li at the first membrane = 1 and kept)
+  std::vector<double> h_stvk;
+  DevBuf<double> d_stvk, cf_dminv;
+  int n_stvk = 0;   // cloths with membrane = 1: the <STVK> face kernels run while this is > 0
 
   // ---- tets
   std::vector<ElasticDev> h_el;

@@ -120,6 +120,7 @@ static ClothArgs cloth_args(tsl_ctx* c) {
   A.gstage = nullptr; A.gs_hinge = c->vg_hinge0;
   return A;
 }
+static StvkArgs stvk_args(tsl_ctx* c) { return StvkArgs{c->d_stvk.p, c->cf_dminv.p}; }
 static VertArgs vert_args(tsl_ctx* c) {
   VertArgs A;
   A.NV = c->NV; A.mass = c->mass.p; A.grav = c->grav.p; A.fext = c->fext.p; A.dt = c->dt;
@@ -426,6 +427,43 @@ extern "C" void tsl_ctx_destroy(tsl_ctx* c) {
 
 extern "C" int tsl_set_stream(tsl_ctx* c, void* s) { c->user_stream = (hipStream_t)s; return 0; }
 
+// Dm^-1 of every cloth face for the StVK membrane, from the rest lengths l0 = |x0 - x1|, l1 = |x1 - x2|, l2 = |x2 - x0|: the rest triangle
+// X0 = (0, 0), X1 = (l0, 0), X2 = (a, b), a = (l0^2 + l2^2 - l1^2) / (2 l0), b = sqrt(l2^2 - a^2); Dm = [X1 - X0, X2 - X0].  Built once.
+static int stvk_prepare(tsl_ctx* c) {
+  if (c->cf_dminv.n > 0 || c->n_cface == 0) return 0;
+  std::vector<double> li(3 * (size_t)c->n_cface), dm(4 * (size_t)c->n_cface);
+  HIP_OK(hipMemcpy(li.data(), c->cf_li.p, li.size() * sizeof(double), hipMemcpyDeviceToHost));
+  std::vector<int> cid(c->n_cface);
+  HIP_OK(hipMemcpy(cid.data(), c->cf_cloth.p, cid.size() * sizeof(int), hipMemcpyDeviceToHost));
+  for (int f = 0; f < c->n_cface; f++) {
+    const double l0 = li[3 * f], l1 = li[3 * f + 1], l2 = li[3 * f + 2];
+    if (!(l0 > 0 && l1 > 0 && l2 > 0 && l0 < l1 + l2 && l1 < l2 + l0 && l2 < l0 + l1))
+      return tsl_fail("tsl_set_param: StVK membrane: rest lengths (%g, %g, %g) of face %d (cloth %d, face %d of the cloth) violate the triangle inequality", l0, l1, l2, f,
+                      cid[f], f - c->h_cloth[cid[f]].face_start);
+    const double a = (l0 * l0 + l2 * l2 - l1 * l1) / (2.0 * l0), b = sqrt(l2 * l2 - a * a);
+    dm[4 * f] = 1.0 / l0; dm[4 * f + 1] = -a / (l0 * b); dm[4 * f + 2] = 0.0; dm[4 * f + 3] = 1.0 / b;
+  }
+  return c->cf_dminv.upload(dm);
+}
+
+// "cloth<i>.membrane" (0 springs + area term, 1 StVK), "cloth<i>.stvk_mu", "cloth<i>.stvk_lam"
+static int stvk_set(tsl_ctx* c, const char* key, long idx, const std::string& f, double v) {
+  const int n_cloth = (int)c->h_cloth.size();
+  if (f == "membrane") {
+    if (v != 0.0 && v != 1.0) return tsl_fail("tsl_set_param: %s must be 0 or 1 (got %g)", key, v);
+    if (v == 1.0) TSL_TRY(stvk_prepare(c));
+  }
+  if (c->h_stvk.empty()) {
+    c->h_stvk.assign(4 * (size_t)n_cloth, 0.0);
+    TSL_TRY(c->d_stvk.alloc(c->h_stvk.size()));
+  }
+  c->h_stvk[4 * idx + (f == "membrane" ? 0 : (f == "stvk_mu" ? 1 : 2))] = v;
+  c->n_stvk = 0;
+  for (int i = 0; i < n_cloth; i++) c->n_stvk += c->h_stvk[4 * i] != 0.0;
+  HIP_OK(hipMemcpy(c->d_stvk.p, c->h_stvk.data(), c->h_stvk.size() * sizeof(double), hipMemcpyHostToDevice));
+  return 0;
+}
+
 extern "C" int tsl_set_param(tsl_ctx* c, const char* key, double v) {
   Scope scope(c);
   (void)hipStreamSynchronize(c->stream);
@@ -484,7 +522,7 @@ extern "C" int tsl_set_param(tsl_ctx* c, const char* key, double v) {
   else if (k == "mg_coarse_exact") c->mg_coarse_exact = (int)v;
   else if (k == "mg_dense_nodes") { c->mg_dense_auto = v < 0; if (v >= 0) c->mg_dense_nodes = (int)v; c->mg_ops_valid = false; }
   else if ((k.rfind("cloth", 0) == 0 || k.rfind("elastic", 0) == 0) && k.find('.') != std::string::npos) {
-    // "cloth<i>.Kb|Kl|Ka|k_angle", "elastic<i>.mu|lam|alpha" (0-d field writes after the context exists)
+    // "cloth<i>.Kb|Kl|Ka|k_angle|membrane|stvk_mu|stvk_lam", "elastic<i>.mu|lam|alpha" (0-d field writes after the context exists)
     const bool is_cloth = k[0] == 'c';
     const size_t p0 = is_cloth ? 5 : 7, dot = k.find('.');
     char* endp = nullptr;
@@ -494,6 +532,7 @@ extern "C" int tsl_set_param(tsl_ctx* c, const char* key, double v) {
     if (is_cloth) {
       if (idx < 0 || idx >= (long)c->h_cloth.size()) return tsl_fail("tsl_set_param: bad cloth index in %s", key);
       ClothDev& cd = c->h_cloth[idx];
+      if (f == "membrane" || f == "stvk_mu" || f == "stvk_lam") return stvk_set(c, key, idx, f, v);
       if (f == "Kb") cd.Kb = v; else if (f == "Kl") cd.Kl = v; else if (f == "Ka") cd.Ka = v; else if (f == "k_angle") cd.k_angle = v;
       else return tsl_fail("tsl_set_param: unknown key %s", key);
       HIP_OK(hipMemcpy(c->d_cloth.p, c->h_cloth.data(), c->h_cloth.size() * sizeof(ClothDev), hipMemcpyHostToDevice));
@@ -533,8 +572,9 @@ extern "C" int tsl_set_gravity(tsl_ctx* c, const double* g) {
 }
 
 // ------------------------------------------------------------------------------------------------
-__global__ void k_energy(VertArgs VA, ClothArgs CA, TetArgs TA, const double* __restrict__ pos, const double* __restrict__ prev,
-                         const double* __restrict__ vel, const double* __restrict__ ref_angle, double* __restrict__ e_part) {
+template <bool STVK>   // STVK: some cloth has membrane = 1 (cface_energy_sel)
+TSL_DEV void energy_body(VertArgs VA, ClothArgs CA, TetArgs TA, const double* __restrict__ pos, const double* __restrict__ prev,
+                         const double* __restrict__ vel, const double* __restrict__ ref_angle, double* __restrict__ e_part, StvkArgs S) {
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
   double e = 0;
   if (t < VA.NV) e += vert_energy(VA, t, pos, prev, vel);
@@ -542,7 +582,8 @@ __global__ void k_energy(VertArgs VA, ClothArgs CA, TetArgs TA, const double* __
     int v[3]; d3 P[3];
     load_face(pos, CA.f2v, t, v, P);
     const double li[3] = {CA.li[3 * t], CA.li[3 * t + 1], CA.li[3 * t + 2]};
-    e += cface_energy(CA.cloth[CA.cid[t]], P, CA.V[t], li);
+    if constexpr (STVK) e += cface_energy_sel(CA.cloth[CA.cid[t]], S.stvk + 4 * CA.cid[t], S.dminv + 4 * t, P, CA.V[t], li);
+    else e += cface_energy(CA.cloth[CA.cid[t]], P, CA.V[t], li);
   }
   if (t < CA.n_hinge) e += hinge_energy(CA, t, pos, ref_angle);
   if (t < TA.n_tet) e += tet_energy(TA, t, pos);
@@ -552,6 +593,14 @@ __global__ void k_energy(VertArgs VA, ClothArgs CA, TetArgs TA, const double* __
   if ((threadIdx.x & 63) == 0) sw[threadIdx.x >> 6] = e;
   __syncthreads();
   if (threadIdx.x == 0) e_part[blockIdx.x] = ((sw[0] + sw[1]) + sw[2]) + sw[3];
+}
+__global__ void k_energy(VertArgs VA, ClothArgs CA, TetArgs TA, const double* __restrict__ pos, const double* __restrict__ prev,
+                         const double* __restrict__ vel, const double* __restrict__ ref_angle, double* __restrict__ e_part) {
+  energy_body<false>(VA, CA, TA, pos, prev, vel, ref_angle, e_part, StvkArgs{nullptr, nullptr});
+}
+__global__ void k_energy_stvk(VertArgs VA, ClothArgs CA, TetArgs TA, const double* __restrict__ pos, const double* __restrict__ prev,
+                              const double* __restrict__ vel, const double* __restrict__ ref_angle, double* __restrict__ e_part, StvkArgs S) {
+  energy_body<true>(VA, CA, TA, pos, prev, vel, ref_angle, e_part, S);
 }
 // sum of n partial energies in a fixed order (one workgroup: strided per-thread sums, then a fixed tree)
 __global__ void __launch_bounds__(256) k_energy_final(int n, const double* __restrict__ part, double* __restrict__ e_out) {
@@ -575,7 +624,8 @@ static int energy_async(tsl_ctx* c, const double* pos, const double* prev, const
   const int nvf = c->nc - c->nc_ee;   // vertex-triangle slots, then the edge-edge slots ("contact_ee")
   const int nb1 = nblk(nmax, 256), nb2 = nvf > 0 ? nblk(nvf, 64) : 0, nb3 = c->nc_ee > 0 ? nblk(c->nc_ee, 64) : 0;
   if (c->e_part.n < (size_t)nb1 + (size_t)nblk(c->max_n_constraints, 64) + 1) { if (c->e_part.alloc((size_t)nb1 + (size_t)nblk(c->max_n_constraints, 64) + 1)) return -1; }
-  hipLaunchKernelGGL(k_energy, dim3(nb1), dim3(256), 0, s, vert_args(c), cloth_args(c), tet_args(c), pos, prev, vel, ref, c->e_part.p);
+  if (c->n_stvk > 0) hipLaunchKernelGGL(k_energy_stvk, dim3(nb1), dim3(256), 0, s, vert_args(c), cloth_args(c), tet_args(c), pos, prev, vel, ref, c->e_part.p, stvk_args(c));
+  else hipLaunchKernelGGL(k_energy, dim3(nb1), dim3(256), 0, s, vert_args(c), cloth_args(c), tet_args(c), pos, prev, vel, ref, c->e_part.p);
   if (nb2 > 0) hipLaunchKernelGGL(k_contact_energy, dim3(nb2), dim3(64), 0, s, nvf, contact_args(c), pos, c->e_part.p + nb1);
   if (nb3 > 0) hipLaunchKernelGGL(k_ee_energy, dim3(nb3), dim3(64), 0, s, c->nc_ee, ee_args(contact_args(c), nvf), pos, c->e_part.p + nb1 + nb2);
   hipLaunchKernelGGL(k_energy_final, dim3(1), dim3(256), 0, s, nb1 + nb2 + nb3, (const double*)c->e_part.p, &SC(c)->energy);
@@ -622,6 +672,26 @@ __global__ void __launch_bounds__(256) k_contact_row_gather(int NV, const int* _
   if (lane == 0) st3(F, v, ld3(F, v) + d3(a0, a1, a2));
 }
 
+// The face kernels of an assembly: the <STVK> instantiations only while some cloth has membrane = 1, else the spring ones as they were
+static void cloth_grad_face_launch(tsl_ctx* c, hipStream_t s, const ClothArgs& CA, const double* pos) {
+  if (c->n_stvk > 0) hipLaunchKernelGGL(k_cloth_grad_face<true>, dim3(nblk(c->n_cface, 256)), dim3(256), 0, s, CA, pos, stvk_args(c));
+  else hipLaunchKernelGGL(k_cloth_grad_face<false>, dim3(nblk(c->n_cface, 256)), dim3(256), 0, s, CA, pos, stvk_args(c));
+}
+static void cloth_hess_face_launch(tsl_ctx* c, hipStream_t s, const ClothArgs& CA, const double* pos, const double* ref, int spd) {
+  const dim3 g(nblk(c->n_cface, 128)), b(128);
+  const StvkArgs S = stvk_args(c);
+  const bool lit = c->spd_literal && spd == 1;
+  if (c->n_stvk > 0) {
+    if (spd == 2) hipLaunchKernelGGL((k_cloth_hess_face<true, false, true>), g, b, 0, s, CA, pos, ref, c->quirk.p, spd, c->cg_frec.p, S);
+    else if (lit) hipLaunchKernelGGL((k_cloth_hess_face<false, true, true>), g, b, 0, s, CA, pos, ref, c->quirk.p, spd, c->cg_frec.p, S);
+    else hipLaunchKernelGGL((k_cloth_hess_face<false, false, true>), g, b, 0, s, CA, pos, ref, c->quirk.p, spd, c->cg_frec.p, S);
+  } else {
+    if (spd == 2) hipLaunchKernelGGL((k_cloth_hess_face<true>), g, b, 0, s, CA, pos, ref, c->quirk.p, spd, c->cg_frec.p, S);
+    else if (lit) hipLaunchKernelGGL((k_cloth_hess_face<false, true>), g, b, 0, s, CA, pos, ref, c->quirk.p, spd, c->cg_frec.p, S);
+    else hipLaunchKernelGGL((k_cloth_hess_face<false>), g, b, 0, s, CA, pos, ref, c->quirk.p, spd, c->cg_frec.p, S);
+  }
+}
+
 // GPU work of one assembly (no host state, no allocation: assemble() below prepares both, so that the launches can be captured into a graph)
 static int assemble_enqueue_early(tsl_ctx* c, const double* pos, const double* prev, const double* vel, const double* ref, int spd, double* grad, int tet_warm_flag);
 static int assemble_enqueue(tsl_ctx* c, const double* pos, const double* prev, const double* vel, const double* ref, int spd, double* grad, int tet_warm_flag) {
@@ -640,15 +710,13 @@ static int assemble_enqueue(tsl_ctx* c, const double* pos, const double* prev, c
   }
   hipLaunchKernelGGL(k_vert_hess, dim3(nblk(NV, 256)), dim3(256), 0, s, VA, c->diag_blk.p, c->vals_full.p);      // (the mass diagonal: the first contribution to its blocks)
   if (grad) {
-    if (c->n_cface) hipLaunchKernelGGL(k_cloth_grad_face, dim3(nblk(c->n_cface, 256)), dim3(256), 0, s, CA, pos);
+    if (c->n_cface) cloth_grad_face_launch(c, s, CA, pos);
     if (c->n_hinge) hipLaunchKernelGGL(k_cloth_grad_hinge, dim3(nblk(c->n_hinge, 256)), dim3(256), 0, s, CA, pos, ref);
   }
   if (c->n_cface) {
     const int nq = (int)c->h_cloth.size() * 9;
     hipLaunchKernelGGL(k_cloth_quirk, dim3(nblk(nq, 64)), dim3(64), 0, s, CA, (int)c->h_cloth.size(), pos, ref, c->quirk.p);
-    if (spd == 2) hipLaunchKernelGGL((k_cloth_hess_face<true>), dim3(nblk(c->n_cface, 128)), dim3(128), 0, s, CA, pos, ref, c->quirk.p, spd, c->cg_frec.p);
-    else if (c->spd_literal && spd == 1) hipLaunchKernelGGL((k_cloth_hess_face<false, true>), dim3(nblk(c->n_cface, 128)), dim3(128), 0, s, CA, pos, ref, c->quirk.p, spd, c->cg_frec.p);
-    else hipLaunchKernelGGL((k_cloth_hess_face<false>), dim3(nblk(c->n_cface, 128)), dim3(128), 0, s, CA, pos, ref, c->quirk.p, spd, c->cg_frec.p);
+    cloth_hess_face_launch(c, s, CA, pos, ref, spd);
   }
   if (c->n_hinge) hipLaunchKernelGGL(k_cloth_hess_hinge, dim3(nblk(c->n_hinge, 256)), dim3(256), 0, s, CA, pos, c->cg_hrec.p);
   if (c->n_cgblk_cloth > 0)
@@ -723,9 +791,7 @@ static int assemble_enqueue_early(tsl_ctx* c, const double* pos, const double* p
   if (c->n_cface) {
     const int nq = (int)c->h_cloth.size() * 9;
     hipLaunchKernelGGL(k_cloth_quirk, dim3(nblk(nq, 64)), dim3(64), 0, s, CA, (int)c->h_cloth.size(), pos, ref, c->quirk.p);
-    if (spd == 2) hipLaunchKernelGGL((k_cloth_hess_face<true>), dim3(nblk(c->n_cface, 128)), dim3(128), 0, s, CA, pos, ref, c->quirk.p, spd, c->cg_frec.p);
-    else if (c->spd_literal && spd == 1) hipLaunchKernelGGL((k_cloth_hess_face<false, true>), dim3(nblk(c->n_cface, 128)), dim3(128), 0, s, CA, pos, ref, c->quirk.p, spd, c->cg_frec.p);
-    else hipLaunchKernelGGL((k_cloth_hess_face<false>), dim3(nblk(c->n_cface, 128)), dim3(128), 0, s, CA, pos, ref, c->quirk.p, spd, c->cg_frec.p);
+    cloth_hess_face_launch(c, s, CA, pos, ref, spd);
   }
   // element stream, second part (behind the normals and the mass diagonal).  Round 6: the element blocks of the bodies take 55 us since they are formed by 16 lanes
   // per element (k_tet_hess_coop; 170 before), so the hinge blocks (records, 45-60 us) run HERE, next to the face blocks on the engine stream, and the face
@@ -743,7 +809,7 @@ static int assemble_enqueue_early(tsl_ctx* c, const double* pos, const double* p
     if (fork_t) HIP_OK(hipStreamWaitEvent(st, c->ev_fork, 0));
     if (c->n_hinge) hipLaunchKernelGGL(k_cloth_grad_hinge, dim3(nblk(c->n_hinge, 256)), dim3(256), 0, st, CA, pos, ref);
     if (c->n_cface) {
-      hipLaunchKernelGGL(k_cloth_grad_face, dim3(nblk(c->n_cface, 256)), dim3(256), 0, hh_side ? stt : st, CA, pos);
+      cloth_grad_face_launch(c, hh_side ? stt : st, CA, pos);
       if (hh_side) HIP_OK(hipEventRecord(c->ev_gf, stt));
     }
   }
@@ -2220,11 +2286,11 @@ extern "C" int tsl_param_grad_keys(tsl_ctx* c, const double* pos, const double* 
   hipStream_t s = c->stream;
   const int n_cloth = (int)c->h_cloth.size(), n_el = (int)c->h_el.size();
   const int nvf = c->nc - c->nc_ee;   // vertex-triangle slots, then the edge-edge slots ("contact_ee")
-  const char* supported = "cloth<i>.Kl|Ka|Kb, elastic<i>.mu|lam, k_contact, mu_cloth_elastic, mu_cloth_cloth";
+  const char* supported = "cloth<i>.Kl|Ka|Kb|stvk_mu|stvk_lam, elastic<i>.mu|lam, k_contact, mu_cloth_elastic, mu_cloth_cloth";
   // ---- keys -> (class, row): class 0 faces (rows 2 i + {Kl, Ka}), 1 hinges (row i), 2 tets (rows 2 i + {mu, lam}), 3 contact slots (rows k_contact,
-  //      mu_cloth_elastic, mu_cloth_cloth)
+  //      mu_cloth_elastic, mu_cloth_cloth), 4 faces of the StVK membrane (rows 2 i + {stvk_mu, stvk_lam})
   std::vector<std::array<int, 2>> kr(n_keys);
-  bool need[4] = {false, false, false, false};
+  bool need[5] = {false, false, false, false, false};
   for (int j = 0; j < n_keys; j++) {
     if (!keys[j]) return tsl_fail("tsl_param_grad_keys: key %d is null", j);
     const std::string k(keys[j]);
@@ -2244,8 +2310,9 @@ extern "C" int tsl_param_grad_keys(tsl_ctx* c, const double* pos, const double* 
       if (is_cloth) {
         if (f == "Kl" || f == "Ka") { cls = 0; row = f == "Kl" ? 0 : 1; }
         else if (f == "Kb") { cls = 1; row = 0; }
+        else if (f == "stvk_mu" || f == "stvk_lam") { cls = 4; row = f == "stvk_mu" ? 0 : 1; }
         if (cls >= 0 && (idx < 0 || idx >= n_cloth)) return tsl_fail("tsl_param_grad_keys: bad cloth index in %s (%d cloths)", keys[j], n_cloth);
-        if (cls == 0) row += 2 * (int)idx; else if (cls == 1) row = (int)idx;
+        if (cls == 0 || cls == 4) row += 2 * (int)idx; else if (cls == 1) row = (int)idx;
       } else {
         if (f == "mu" || f == "lam") { cls = 2; row = f == "mu" ? 0 : 1; }
         if (cls >= 0 && (idx < 0 || idx >= n_el)) return tsl_fail("tsl_param_grad_keys: bad elastic index in %s (%d bodies)", keys[j], n_el);
@@ -2266,19 +2333,24 @@ extern "C" int tsl_param_grad_keys(tsl_ctx* c, const double* pos, const double* 
     kr[j] = {cls, row};
     need[cls] = true;
   }
-  // ---- partial layout: class q holds rows[q] rows of nb[q] partials
-  const int rows[4] = {2 * n_cloth, n_cloth, 2 * n_el, 3};
-  const int nb[4] = {c->n_cface > 0 ? nblk(c->n_cface, PG_THREADS) : 0, c->n_hinge > 0 ? nblk(c->n_hinge, PG_THREADS) : 0, c->n_tet > 0 ? nblk(c->n_tet, PG_THREADS) : 0,
-                     nvf > 0 ? nblk(nvf, PG_THREADS) : 0};
-  size_t off[4], tot = 0;
-  for (int q = 0; q < 4; q++) { off[q] = tot; if (need[q]) tot += (size_t)rows[q] * nb[q]; }
+  // ---- partial layout: class q holds rows[q] rows of nb[q] partials (class 4 behind the others: their layout does not depend on it).  With no cloth
+  //      of membrane = 1 the StVK keys have no partials and read exact zeros
+  const int rows[5] = {2 * n_cloth, n_cloth, 2 * n_el, 3, 2 * n_cloth};
+  const int nb[5] = {c->n_cface > 0 ? nblk(c->n_cface, PG_THREADS) : 0, c->n_hinge > 0 ? nblk(c->n_hinge, PG_THREADS) : 0, c->n_tet > 0 ? nblk(c->n_tet, PG_THREADS) : 0,
+                     nvf > 0 ? nblk(nvf, PG_THREADS) : 0, c->n_cface > 0 && c->n_stvk > 0 ? nblk(c->n_cface, PG_THREADS) : 0};
+  size_t off[5], tot = 0;
+  for (int q = 0; q < 5; q++) { off[q] = tot; if (need[q]) tot += (size_t)rows[q] * nb[q]; }
   if (tot > (size_t)INT32_MAX) return tsl_fail("tsl_param_grad_keys: too many partials");
   if (c->pg_part.n < std::max<size_t>(tot, 1)) TSL_TRY(c->pg_part.alloc(std::max<size_t>(tot, 1)));
   if (c->pg_out.n < (size_t)n_keys + 2) TSL_TRY(c->pg_out.alloc((size_t)n_keys + 2));
   const double* p = p_dev ? p_dev : c->pdir.p;
   const int* fz = c->frozen.p;
   double* part = c->pg_part.p;
-  if (need[0] && nb[0]) hipLaunchKernelGGL(k_pg_face, dim3(nb[0]), dim3(PG_THREADS), 0, s, cloth_args(c), n_cloth, pos, p, fz, part + off[0]);
+  if (need[0] && nb[0]) {
+    if (c->n_stvk > 0) hipLaunchKernelGGL(k_pg_face<true>, dim3(nb[0]), dim3(PG_THREADS), 0, s, cloth_args(c), n_cloth, pos, p, fz, part + off[0], stvk_args(c));
+    else hipLaunchKernelGGL(k_pg_face<false>, dim3(nb[0]), dim3(PG_THREADS), 0, s, cloth_args(c), n_cloth, pos, p, fz, part + off[0], stvk_args(c));
+  }
+  if (need[4] && nb[4]) hipLaunchKernelGGL(k_pg_stvk, dim3(nb[4]), dim3(PG_THREADS), 0, s, cloth_args(c), n_cloth, pos, p, fz, part + off[4], stvk_args(c));
   if (need[1] && nb[1]) hipLaunchKernelGGL(k_pg_hinge, dim3(nb[1]), dim3(PG_THREADS), 0, s, cloth_args(c), n_cloth, pos, ref, p, fz, part + off[1]);
   if (need[2] && nb[2]) hipLaunchKernelGGL(k_pg_tet, dim3(nb[2]), dim3(PG_THREADS), 0, s, tet_args(c), n_el, pos, p, fz, part + off[2]);
   if (need[3] && nb[3])

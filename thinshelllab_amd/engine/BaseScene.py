@@ -345,6 +345,9 @@ class BaseScene:
             self._ctx.set_param("spd_literal", int(bool(self.spd_literal)))
             if self.contact_ee:
                 self._ctx.set_param("contact_ee", 1)
+            for i, c in enumerate(self.cloths):
+                for k, v in c._stvk_params():
+                    self._ctx.set_param(f"cloth{i}.{k}", v)
             self._ctx.set_ext_force(self._ext_force_array())
             self._dirty.clear()
         if self._dirty:

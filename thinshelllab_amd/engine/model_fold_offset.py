@@ -34,6 +34,11 @@ class Cloth:
         self.Ka = ScalarField(1000.0, self._param("Ka"))
         self.Kb = ScalarField(100.0, self._param("Kb"))
         self.k_angle = ScalarField(3.14, self._param("k_angle"))
+        # membrane model (no counterpart in the reference): 0 the reference's edge springs + area term (Kl, Ka), 1 a St. Venant-Kirchhoff membrane
+        # with the Lame parameters stvk_mu / stvk_lam in N/m (per unit rest area); bending is the hinge model either way
+        self.membrane = ScalarField(0.0, self._param("membrane"))
+        self.stvk_mu = ScalarField(0.0, self._param("stvk_mu"))
+        self.stvk_lam = ScalarField(0.0, self._param("stvk_lam"))
         self.gravity = ScalarField([0.0, 0.0, -9.8], self._gravity_written)
         z3 = lambda n: torch.zeros((n, 3), dtype=torch.float64)
         self.pos = Field(z3(self.NV))
@@ -57,6 +62,22 @@ class Cloth:
             if self._sys is not None and self._sys._ctx is not None:
                 self._sys._ctx.set_param(f"cloth{self._idx}.{name}", field.value)
         return cb
+
+    def set_stvk(self, E, nu, thickness):
+        """Switch this cloth to the StVK membrane with the plane-stress Lame parameters of a sheet of Young's modulus E (Pa), Poisson ratio nu
+        and thickness h (m): mu = E h / (2 (1 + nu)), lam = E h nu / (1 - nu^2), both in N/m.  Returns (mu, lam)."""
+        if not (-1.0 < nu <= 0.5):
+            raise ValueError(f"set_stvk: Poisson ratio {nu} outside (-1, 0.5]")
+        mu = E * thickness / (2.0 * (1.0 + nu))
+        lam = E * thickness * nu / (1.0 - nu * nu)
+        self.stvk_mu[None] = mu
+        self.stvk_lam[None] = lam
+        self.membrane[None] = 1.0
+        return mu, lam
+
+    def _stvk_params(self):
+        """(key suffix, value) of the membrane settings that differ from the defaults (pushed by BaseScene when it creates the engine context)"""
+        return [(k, f.value) for k, f in (("stvk_mu", self.stvk_mu), ("stvk_lam", self.stvk_lam), ("membrane", self.membrane)) if f.value != 0.0]
 
     def _gravity_written(self, field):
         if self._sys is not None:
