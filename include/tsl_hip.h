@@ -103,9 +103,10 @@ int tsl_ctx_create(const tsl_scene_desc* desc, tsl_ctx** out);
 void tsl_ctx_destroy(tsl_ctx* ctx);
 int tsl_set_stream(tsl_ctx* ctx, void* hip_stream);
 
-/* 0-d field writes of the reference and the engine's own switches (41 keys + three patterns; an unknown key is an error).
+/* 0-d field writes of the reference and the engine's own switches (42 keys + three patterns; an unknown key is an error).
  *  Scene (trajopt_folding.py:50,66; Scene_folding.py:30-31; geometry.py:8-19; geometry_self.py:166-230):
  *   "cloth<i>.Kb|Kl|Ka|k_angle", "elastic<i>.mu|lam|alpha", "mu_cloth_elastic", "mu_cloth_cloth", "k_contact", "eps_contact", "eps_v", "damping",
+ *   "k_handle" (0 default: stiffness in N/m of the soft handles of tsl_set_handles; negative fails; with 0, or with no handles, no handle kernel is launched),
  *   "cloth<i>.membrane" (0 default: edge springs Kl + area term Ka, as the reference; 1: a St. Venant-Kirchhoff membrane per face, A0 Psi(F) with
  *   F = [x1 - x0, x2 - x0] Dm^-1, Dm the rest triangle rebuilt from the face's rest lengths (fails naming a face whose lengths violate the triangle
  *   inequality), Psi = mu |E|^2 + lam/2 tr(E)^2, E = (F^T F - I) / 2, A0 the rest area; it replaces the springs and the area term of the cloth's
@@ -148,6 +149,26 @@ int tsl_set_param(tsl_ctx* ctx, const char* key, double value);
 int tsl_set_frozen(tsl_ctx* ctx, const int32_t* frozen_host);          /* BaseScene.set_frozen */
 int tsl_set_ext_force(tsl_ctx* ctx, const double* ext_force_host);      /* BaseScene.ext_force / manipulate_force */
 int tsl_set_gravity(tsl_ctx* ctx, const double* gravity_host);          /* per-vertex, tot_NV x 3 */
+
+/* Soft handles (no reference counterpart: its only hold on a vertex is set_frozen): handle i is a spring from vertex verts[i] to a world-space
+ * target t_i, E_h = 1/2 k_handle sum_i w_i |x_{v_i} - t_i|^2 with the scalar "k_handle" of tsl_set_param.  The term enters tsl_energy,
+ * tsl_assemble (gradient row v_i: k_handle w_i (x - t_i); diagonal block: k_handle w_i I_3, positive semi-definite as it stands, so every spd mode
+ * and "spd_literal" add the same numbers), tsl_step, tsl_adjoint_step and both scene-group steps; frozen dofs follow the mask rule of every other
+ * term.  The block pattern, the plans of the factorisation and their cache do not depend on handles.
+ * Conventions of tsl_set_ext_force: host pointers, the stream is synchronised, the lists are copied into buffers of the context.
+ *   tsl_set_handles: n handles (global vertex ids); weights_host == NULL: every weight is 1; n = 0 removes all handles (the launches of a context
+ *     that never had any).  Fails, naming the offender, for a vertex out of range, a vertex with more than one handle, a negative or non-finite
+ *     weight.  The targets start at zero: set them before use.
+ *   tsl_set_handle_targets: n x 3, the targets of the next energy, assemble, step or adjoint step.  The adjoint re-assembles the operator at x_s;
+ *     tsl_handle_grad and the "k_handle" key of tsl_param_grad_keys read the targets: set the targets of step s before the reverse step s.
+ *   tsl_handle_force: out_host (n x 3) = k_handle w_i (t_i - x_{v_i}), the force handle i applies to the cloth; frozen dofs are NOT masked
+ *     (a read-out, like tsl_elastic_force).
+ *   tsl_handle_grad: the contribution of one reverse step to d(loss)/d(t_i), sign of tsl_param_grad_keys: out_host (n x 3) = -p . dF/dt_i =
+ *     k_handle w_i p_{v_i} on free dofs, exactly 0 on frozen ones; p_dev == NULL: the solution of the last tsl_adjoint_step. */
+int tsl_set_handles(tsl_ctx* ctx, const int32_t* verts_host, const double* weights_host, int32_t n);
+int tsl_set_handle_targets(tsl_ctx* ctx, const double* targets_host);
+int tsl_handle_force(tsl_ctx* ctx, const double* pos_dev, double* out_host);
+int tsl_handle_grad(tsl_ctx* ctx, const double* p_dev, double* out_host);
 
 /* BaseScene.compute_energy (BaseScene.py:427-451) at the given state, constraints as last detected. */
 int tsl_energy(tsl_ctx* ctx, const double* pos_dev, const double* prev_pos_dev, const double* vel_dev,
@@ -211,7 +232,8 @@ int tsl_friction_grad(tsl_ctx* ctx, const double* pos_dev, double* out_host);
  * Keys: "cloth<i>.Kl", "cloth<i>.Ka", "cloth<i>.Kb", "cloth<i>.stvk_mu", "cloth<i>.stvk_lam" (StVK membrane, "cloth<i>.membrane" = 1), "elastic<i>.mu",
  * "elastic<i>.lam" (both material models, alpha fixed), "k_contact" (normal
  * term of every vertex-triangle slot and the friction weights c_k = -mu k_contact (gap - eps) of the detection), "mu_cloth_elastic",
- * "mu_cloth_cloth" (friction of the slots whose pair uses that live parameter, the pair's factor kept: d c_k = c_k / mu_live).
+ * "mu_cloth_cloth" (friction of the slots whose pair uses that live parameter, the pair's factor kept: d c_k = c_k / mu_live),
+ * "k_handle" (soft handles: -sum_i w_i p_{v_i} . (x_{v_i} - t_i) over free dofs with the targets as last set; exactly 0 with no handles) -- eleven key forms.
  * p_dev == NULL: the solution of the last tsl_adjoint_step (as tsl_param_grad uses it); otherwise any 3*tot_NV vector (original vertex order).
  * pos = tape state x_s, ref_angle = tape rest angles of step s-1 (needed by the Kb keys only); contact constraints as last detected / as the
  * last adjoint step left them -- c_k and dx0 are records of the detection, the derivative does not differentiate detection.

@@ -110,6 +110,36 @@ class TslContext:
         g = _np(g, np.float64)
         check(self.L.tsl_set_gravity(self.h, g.ctypes.data), "tsl_set_gravity")
 
+    # ---- soft handles (tsl_set_handles; stiffness: set_param("k_handle", k))
+    def set_handles(self, verts, weights=None):
+        """n handles on the global vertex ids `verts` (at most one per vertex), weights None: all 1; an empty list removes them.  Targets start at zero."""
+        v = _np(verts, np.int32).reshape(-1)
+        w = None if weights is None else _np(weights, np.float64).reshape(-1)
+        assert w is None or w.shape == v.shape, (v.shape, w.shape)
+        check(self.L.tsl_set_handles(self.h, v.ctypes.data if len(v) else None, None if w is None or not len(v) else w.ctypes.data, len(v)), "tsl_set_handles")
+        self.n_handle = len(v)
+
+    def set_handle_targets(self, targets):
+        t = _np(targets, np.float64)
+        assert t.shape == (getattr(self, "n_handle", 0), 3), t.shape
+        if len(t):
+            check(self.L.tsl_set_handle_targets(self.h, t.ctypes.data), "tsl_set_handle_targets")
+
+    def handle_force(self, pos):
+        """(n, 3) k_handle w_i (t_i - x_{v_i}): the force every handle applies to the cloth at the state pos (frozen dofs not masked)"""
+        self.refresh_stream()
+        out = np.zeros((getattr(self, "n_handle", 0), 3))
+        check(self.L.tsl_handle_force(self.h, _ptr(pos), out.ctypes.data), "tsl_handle_force")
+        return out
+
+    def handle_grad(self, p=None):
+        """(n, 3) contribution of one reverse step to d(loss)/d(target): k_handle w_i p_{v_i} on free dofs, 0 on frozen ones; p None: the solution of
+        the last adjoint_step, else a 3 * tot_NV device vector"""
+        self.refresh_stream()
+        out = np.zeros((getattr(self, "n_handle", 0), 3))
+        check(self.L.tsl_handle_grad(self.h, _ptr(p), out.ctypes.data), "tsl_handle_grad")
+        return out
+
     # ---- engine calls
     def energy(self, pos, prev_pos, vel, ref_angle):
         self.refresh_stream()
@@ -119,7 +149,7 @@ class TslContext:
 
     def assemble(self, pos, prev_pos, vel, ref_angle, spd=True, grad=None):
         self.refresh_stream()
-        check(self.L.tsl_assemble(self.h, _ptr(pos), _ptr(prev_pos), _ptr(vel), _ptr(ref_angle), int(bool(spd)), _ptr(grad)), "tsl_assemble")
+        check(self.L.tsl_assemble(self.h, _ptr(pos), _ptr(prev_pos), _ptr(vel), _ptr(ref_angle), int(spd), _ptr(grad)), "tsl_assemble")
 
     def solve(self, rhs, x=None):
         self.refresh_stream()
@@ -177,7 +207,7 @@ class TslContext:
 
     def param_grads(self, pos, ref_angle, keys, p=None):
         """{key: sum over the free dofs of p . d(force)/d(key)} at the tape state pos (tsl_param_grad_keys): keys as tsl_set_param spells them
-        ("cloth<i>.Kl|Ka|Kb|stvk_mu|stvk_lam", "elastic<i>.mu|lam", "k_contact", "mu_cloth_elastic", "mu_cloth_cloth"); p None: the solution of the last
+        ("cloth<i>.Kl|Ka|Kb|stvk_mu|stvk_lam", "elastic<i>.mu|lam", "k_contact", "mu_cloth_elastic", "mu_cloth_cloth", "k_handle"); p None: the solution of the last
         adjoint_step, else a 3 * tot_NV device vector"""
         keys = list(keys)
         if not keys:

@@ -1,7 +1,7 @@
 // Parameter vector-Jacobian products of the system-identification adjoint (tsl_param_grad_keys): for every material or contact scalar theta,
 // -sum over the free dofs of p . dF/d(theta), F the gradient tsl_assemble forms (so the value is p . d(force)/d(theta), the sign of tsl_param_grad).
 // Every supported scalar enters F linearly, so an element's dF/d(theta) is its own gradient term with the scalar set to one; the terms below
-// restate the forward kernels' expressions (k_cloth_grad_face, k_cloth_grad_hinge, k_tet_grad, k_contact_assemble_coop) through the same device
+// restate the forward kernels' expressions (k_cloth_grad_face, k_cloth_grad_hinge, k_tet_grad, k_contact_assemble_coop, k_handle_grad) through the same device
 // functions (load_face, face_geom, hinge_grad, dihedral, tet_F, m3_cof2, fr_f1) without touching those kernels.
 // One pass per element class, one lane per element, no per-vertex gather: the element dots its dF/d(theta) with p at its free dofs, the workgroup
 // joins the lanes by the fixed tree of block_sum and writes ONE partial per key (part[key_row * gridDim.x + blockIdx.x]); k_pg_final sums a key's
@@ -10,6 +10,7 @@
 #include "k_cloth.hpp"
 #include "k_contact.hpp"
 #include "k_fem.hpp"
+#include "k_handle.hpp"
 #include "tsl_device.hpp"
 
 #define PG_THREADS 256
@@ -233,4 +234,17 @@ __global__ void __launch_bounds__(PG_THREADS) k_pg_final(PgTable tab, const doub
   k1 = block_sum(k1, sm);
   k2 = block_sum(k2, sm);
   if (threadIdx.x == 0) { cnt_out[0] = k1; cnt_out[1] = k2; }
+}
+
+// soft handles: {k_handle} -- the gradient row of k_handle_grad with k_handle = 1, w_i (x - t_i) at vertex v_i; one lane per handle
+__global__ void __launch_bounds__(PG_THREADS) k_pg_handle(HandleArgs A, const double* __restrict__ pos, const double* __restrict__ p,
+                                                          const int* __restrict__ frozen, double* __restrict__ part) {
+  __shared__ double sm[PG_THREADS / 64];
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  double v[1] = {0.0};
+  if (i < A.n) {
+    const int vi = A.v[i];
+    v[0] = -pg_dot_free(p, frozen, vi, (ld3(pos, vi) - ld3(A.t, i)) * A.w[i]);
+  }
+  pg_block_write<1>(v, i < A.n ? 0 : -1, 1, part, sm);
 }

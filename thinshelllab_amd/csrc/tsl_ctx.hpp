@@ -254,6 +254,12 @@ struct tsl_ctx {
   DevBuf<int> diag_blk;             // NV
   std::vector<int> h_frozen;
   std::vector<double> h_mass;
+  // soft handles (tsl_set_handles, k_handle.hpp): vertex, weight and target of each, copies the context owns; the handle kernels run while
+  // n_handle > 0 and k_handle != 0
+  int n_handle = 0;
+  double k_handle = 0.0;
+  DevBuf<int> hd_v;
+  DevBuf<double> hd_w, hd_t, hd_out;   // n, n x 3, n x 3 (read-outs of tsl_handle_force / tsl_handle_grad)
 
   // ---- matrix (SELL-64 of 3x3 blocks, rows permuted by length)
   int n_slices = 0;

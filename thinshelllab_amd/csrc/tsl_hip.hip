@@ -14,9 +14,11 @@
 #include "k_cloth.hpp"
 #include "k_contact.hpp"
 #include "k_fem.hpp"
+#include "k_handle.hpp"
 #include "k_mg.hpp"
 #include "k_param.hpp"
 #include "k_solver.hpp"
+#include "handle_host.hpp"
 #include "tsl_ctx.hpp"
 
 thread_local std::string g_tsl_err;
@@ -131,6 +133,9 @@ static TetArgs tet_args(tsl_ctx* c) {
   A.n_tet = c->n_tet; A.el = c->d_el.p; A.tv = c->tet_v.p; A.tel = c->tet_el.p; A.B = c->tet_B.p; A.W = c->tet_W.p; A.gstage = nullptr;
   return A;
 }
+static HandleArgs handle_args(tsl_ctx* c) { return HandleArgs{c->n_handle, c->hd_v.p, c->hd_w.p, c->hd_t.p, c->k_handle}; }
+// the handle kernels of an energy / assembly / reverse step run only while this holds: without it the launches are the ones they were
+static bool handles_on(const tsl_ctx* c) { return c->n_handle > 0 && c->k_handle != 0.0; }
 static ContactArgs contact_args(tsl_ctx* c) {
   ContactArgs A;
   A.idx = c->c_idx.p; A.w = c->c_w.p; A.n = c->c_n.p; A.dx0 = c->c_dx0.p; A.k = c->c_k.p; A.mu = c->c_mu.p; A.T = c->c_T.p;
@@ -476,6 +481,10 @@ extern "C" int tsl_set_param(tsl_ctx* c, const char* key, double v) {
   else if (k == "eps_contact") c->eps_contact = v;
   else if (k == "eps_v") c->eps_v = v;
   else if (k == "damping") c->damping = v;
+  else if (k == "k_handle") {
+    if (!(v >= 0.0) || !std::isfinite(v)) return tsl_fail("tsl_set_param: k_handle must be finite and >= 0 (got %g)", v);
+    c->k_handle = v;
+  }
   else if (k == "cg_tol") c->cg_tol = v;
   else if (k == "cg_maxit") c->cg_maxit = (int)v;
   else if (k == "newton_cap") c->newton_cap = (int)v;
@@ -571,6 +580,57 @@ extern "C" int tsl_set_gravity(tsl_ctx* c, const double* g) {
   return 0;
 }
 
+// Soft handles (k_handle.hpp): the lists are checked on the host (handle_host.hpp) and copied into buffers of the context; targets start at zero
+extern "C" int tsl_set_handles(tsl_ctx* c, const int32_t* verts, const double* weights, int32_t n) {
+  Scope scope(c);
+  (void)hipStreamSynchronize(c->stream);
+  std::string err;
+  if (handle_validate(c->NV, verts, weights, n, err)) return tsl_fail("tsl_set_handles: %s", err.c_str());
+  c->mg_omega_valid = false; c->mg_cinv_valid = false;
+  c->ds.anorm_valid = false;   // (the scale of the operator may change: |H|_inf is formed again when a refinement asks for it)
+  c->n_handle = 0;
+  if (n == 0) { c->hd_v.release(); c->hd_w.release(); c->hd_t.release(); c->hd_out.release(); return 0; }
+  std::vector<int> hv(verts, verts + n);
+  std::vector<double> hw(n, 1.0);
+  if (weights) hw.assign(weights, weights + n);
+  TSL_TRY(c->hd_v.upload(hv));
+  TSL_TRY(c->hd_w.upload(hw));
+  TSL_TRY(c->hd_t.upload(std::vector<double>(3 * (size_t)n, 0.0)));
+  TSL_TRY(c->hd_out.alloc(3 * (size_t)n));
+  c->n_handle = n;
+  return 0;
+}
+extern "C" int tsl_set_handle_targets(tsl_ctx* c, const double* targets) {
+  Scope scope(c);
+  (void)hipStreamSynchronize(c->stream);
+  if (c->n_handle == 0) return 0;
+  if (!targets) return tsl_fail("tsl_set_handle_targets: null targets for %d handles", c->n_handle);
+  HIP_OK(hipMemcpy(c->hd_t.p, targets, 3 * (size_t)c->n_handle * sizeof(double), hipMemcpyHostToDevice));
+  return 0;
+}
+// read-outs, one value per handle and axis: the kernel writes hd_out, one copy to the host, one synchronisation
+static int handle_readout(tsl_ctx* c, double* out_host) {
+  HIP_OK(hipGetLastError());
+  HIP_OK(hipMemcpyAsync(out_host, c->hd_out.p, 3 * (size_t)c->n_handle * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIP_OK(hipStreamSynchronize(c->stream));
+  return 0;
+}
+extern "C" int tsl_handle_force(tsl_ctx* c, const double* pos, double* out_host) {
+  Scope scope(c);
+  if (c->n_handle == 0) return 0;
+  if (!pos || !out_host) return tsl_fail("tsl_handle_force: null argument");
+  hipLaunchKernelGGL(k_handle_force, dim3(nblk(c->n_handle, 256)), dim3(256), 0, c->stream, handle_args(c), pos, c->hd_out.p);
+  return handle_readout(c, out_host);
+}
+extern "C" int tsl_handle_grad(tsl_ctx* c, const double* p_dev, double* out_host) {
+  Scope scope(c);
+  if (c->n_handle == 0) return 0;
+  if (!out_host) return tsl_fail("tsl_handle_grad: null argument");
+  hipLaunchKernelGGL(k_handle_backprop, dim3(nblk(c->n_handle, 256)), dim3(256), 0, c->stream, handle_args(c), p_dev ? p_dev : (const double*)c->pdir.p,
+                     (const int*)c->frozen.p, c->hd_out.p);
+  return handle_readout(c, out_host);
+}
+
 // ------------------------------------------------------------------------------------------------
 template <bool STVK>   // STVK: some cloth has membrane = 1 (cface_energy_sel)
 TSL_DEV void energy_body(VertArgs VA, ClothArgs CA, TetArgs TA, const double* __restrict__ pos, const double* __restrict__ prev,
@@ -623,12 +683,15 @@ static int energy_async(tsl_ctx* c, const double* pos, const double* prev, const
   // partials per workgroup, added in a fixed order (the line search decides on E < E0)
   const int nvf = c->nc - c->nc_ee;   // vertex-triangle slots, then the edge-edge slots ("contact_ee")
   const int nb1 = nblk(nmax, 256), nb2 = nvf > 0 ? nblk(nvf, 64) : 0, nb3 = c->nc_ee > 0 ? nblk(c->nc_ee, 64) : 0;
-  if (c->e_part.n < (size_t)nb1 + (size_t)nblk(c->max_n_constraints, 64) + 1) { if (c->e_part.alloc((size_t)nb1 + (size_t)nblk(c->max_n_constraints, 64) + 1)) return -1; }
+  const int nb4 = handles_on(c) ? nblk(c->n_handle, 256) : 0;   // soft handles: their partials behind the contact ones
+  const size_t n_part = (size_t)nb1 + (size_t)nblk(c->max_n_constraints, 64) + 1 + (size_t)nblk(c->n_handle, 256);
+  if (c->e_part.n < n_part) { if (c->e_part.alloc(n_part)) return -1; }
   if (c->n_stvk > 0) hipLaunchKernelGGL(k_energy_stvk, dim3(nb1), dim3(256), 0, s, vert_args(c), cloth_args(c), tet_args(c), pos, prev, vel, ref, c->e_part.p, stvk_args(c));
   else hipLaunchKernelGGL(k_energy, dim3(nb1), dim3(256), 0, s, vert_args(c), cloth_args(c), tet_args(c), pos, prev, vel, ref, c->e_part.p);
   if (nb2 > 0) hipLaunchKernelGGL(k_contact_energy, dim3(nb2), dim3(64), 0, s, nvf, contact_args(c), pos, c->e_part.p + nb1);
   if (nb3 > 0) hipLaunchKernelGGL(k_ee_energy, dim3(nb3), dim3(64), 0, s, c->nc_ee, ee_args(contact_args(c), nvf), pos, c->e_part.p + nb1 + nb2);
-  hipLaunchKernelGGL(k_energy_final, dim3(1), dim3(256), 0, s, nb1 + nb2 + nb3, (const double*)c->e_part.p, &SC(c)->energy);
+  if (nb4 > 0) hipLaunchKernelGGL(k_handle_energy, dim3(nb4), dim3(256), 0, s, handle_args(c), pos, c->e_part.p + nb1 + nb2 + nb3);
+  hipLaunchKernelGGL(k_energy_final, dim3(1), dim3(256), 0, s, nb1 + nb2 + nb3 + nb4, (const double*)c->e_part.p, &SC(c)->energy);
   return 0;
 }
 static int energy_sync(tsl_ctx* c, const double* pos, const double* prev, const double* vel, const double* ref, double* E) {
@@ -692,6 +755,14 @@ static void cloth_hess_face_launch(tsl_ctx* c, hipStream_t s, const ClothArgs& C
   }
 }
 
+// Soft handles in an assembly: their gradient rows and diagonal entries behind the vertex terms on the same stream (nothing while no handle is on)
+static void handle_assemble_launch(tsl_ctx* c, hipStream_t s, const double* pos, double* grad) {
+  if (!handles_on(c)) return;
+  const HandleArgs HA = handle_args(c);
+  if (grad) hipLaunchKernelGGL(k_handle_grad, dim3(nblk(HA.n, 256)), dim3(256), 0, s, HA, pos, grad);
+  hipLaunchKernelGGL(k_handle_hess, dim3(nblk(HA.n, 256)), dim3(256), 0, s, HA, (const int*)c->diag_blk.p, c->vals_full.p);
+}
+
 // GPU work of one assembly (no host state, no allocation: assemble() below prepares both, so that the launches can be captured into a graph)
 static int assemble_enqueue_early(tsl_ctx* c, const double* pos, const double* prev, const double* vel, const double* ref, int spd, double* grad, int tet_warm_flag);
 static int assemble_enqueue(tsl_ctx* c, const double* pos, const double* prev, const double* vel, const double* ref, int spd, double* grad, int tet_warm_flag) {
@@ -709,6 +780,7 @@ static int assemble_enqueue(tsl_ctx* c, const double* pos, const double* prev, c
     hipLaunchKernelGGL(k_vert_grad, dim3(nblk(NV, 256)), dim3(256), 0, s, VA, pos, prev, vel, grad);
   }
   hipLaunchKernelGGL(k_vert_hess, dim3(nblk(NV, 256)), dim3(256), 0, s, VA, c->diag_blk.p, c->vals_full.p);      // (the mass diagonal: the first contribution to its blocks)
+  handle_assemble_launch(c, s, pos, grad);
   if (grad) {
     if (c->n_cface) cloth_grad_face_launch(c, s, CA, pos);
     if (c->n_hinge) hipLaunchKernelGGL(k_cloth_grad_hinge, dim3(nblk(c->n_hinge, 256)), dim3(256), 0, s, CA, pos, ref);
@@ -787,6 +859,7 @@ static int assemble_enqueue_early(tsl_ctx* c, const double* pos, const double* p
     hipLaunchKernelGGL(k_vert_grad, dim3(nblk(NV, 256)), dim3(256), 0, s, VA, pos, prev, vel, grad);
   }
   hipLaunchKernelGGL(k_vert_hess, dim3(nblk(NV, 256)), dim3(256), 0, s, VA, c->diag_blk.p, c->vals_full.p);   // (the mass diagonal: the first contribution to its blocks)
+  handle_assemble_launch(c, s, pos, grad);   // (on the stream of the vertex terms, in front of ev_fork: the gathers and masks of the other streams wait for it as they do for those)
   HIP_OK(hipEventRecord(c->ev_fork, s));   // normals, vertex gradient and mass diagonal are in place
   if (c->n_cface) {
     const int nq = (int)c->h_cloth.size() * 9;
@@ -2286,11 +2359,11 @@ extern "C" int tsl_param_grad_keys(tsl_ctx* c, const double* pos, const double* 
   hipStream_t s = c->stream;
   const int n_cloth = (int)c->h_cloth.size(), n_el = (int)c->h_el.size();
   const int nvf = c->nc - c->nc_ee;   // vertex-triangle slots, then the edge-edge slots ("contact_ee")
-  const char* supported = "cloth<i>.Kl|Ka|Kb|stvk_mu|stvk_lam, elastic<i>.mu|lam, k_contact, mu_cloth_elastic, mu_cloth_cloth";
+  const char* supported = "cloth<i>.Kl|Ka|Kb|stvk_mu|stvk_lam, elastic<i>.mu|lam, k_contact, mu_cloth_elastic, mu_cloth_cloth, k_handle";
   // ---- keys -> (class, row): class 0 faces (rows 2 i + {Kl, Ka}), 1 hinges (row i), 2 tets (rows 2 i + {mu, lam}), 3 contact slots (rows k_contact,
-  //      mu_cloth_elastic, mu_cloth_cloth), 4 faces of the StVK membrane (rows 2 i + {stvk_mu, stvk_lam})
+  //      mu_cloth_elastic, mu_cloth_cloth), 4 faces of the StVK membrane (rows 2 i + {stvk_mu, stvk_lam}), 5 soft handles (row k_handle)
   std::vector<std::array<int, 2>> kr(n_keys);
-  bool need[5] = {false, false, false, false, false};
+  bool need[6] = {false, false, false, false, false, false};
   for (int j = 0; j < n_keys; j++) {
     if (!keys[j]) return tsl_fail("tsl_param_grad_keys: key %d is null", j);
     const std::string k(keys[j]);
@@ -2298,6 +2371,7 @@ extern "C" int tsl_param_grad_keys(tsl_ctx* c, const double* pos, const double* 
     if (k == "k_contact") { cls = 3; row = 0; }
     else if (k == "mu_cloth_elastic") { cls = 3; row = 1; }
     else if (k == "mu_cloth_cloth") { cls = 3; row = 2; }
+    else if (k == "k_handle") { cls = 5; row = 0; }
     else if ((k.rfind("cloth", 0) == 0 || k.rfind("elastic", 0) == 0) && k.find('.') != std::string::npos) {
       const bool is_cloth = k[0] == 'c';
       const size_t p0 = is_cloth ? 5 : 7, dot = k.find('.');
@@ -2334,12 +2408,13 @@ extern "C" int tsl_param_grad_keys(tsl_ctx* c, const double* pos, const double* 
     need[cls] = true;
   }
   // ---- partial layout: class q holds rows[q] rows of nb[q] partials (class 4 behind the others: their layout does not depend on it).  With no cloth
-  //      of membrane = 1 the StVK keys have no partials and read exact zeros
-  const int rows[5] = {2 * n_cloth, n_cloth, 2 * n_el, 3, 2 * n_cloth};
-  const int nb[5] = {c->n_cface > 0 ? nblk(c->n_cface, PG_THREADS) : 0, c->n_hinge > 0 ? nblk(c->n_hinge, PG_THREADS) : 0, c->n_tet > 0 ? nblk(c->n_tet, PG_THREADS) : 0,
-                     nvf > 0 ? nblk(nvf, PG_THREADS) : 0, c->n_cface > 0 && c->n_stvk > 0 ? nblk(c->n_cface, PG_THREADS) : 0};
-  size_t off[5], tot = 0;
-  for (int q = 0; q < 5; q++) { off[q] = tot; if (need[q]) tot += (size_t)rows[q] * nb[q]; }
+  //      of membrane = 1 the StVK keys have no partials and read exact zeros, as k_handle does with no handles
+  const int rows[6] = {2 * n_cloth, n_cloth, 2 * n_el, 3, 2 * n_cloth, 1};
+  const int nb[6] = {c->n_cface > 0 ? nblk(c->n_cface, PG_THREADS) : 0, c->n_hinge > 0 ? nblk(c->n_hinge, PG_THREADS) : 0, c->n_tet > 0 ? nblk(c->n_tet, PG_THREADS) : 0,
+                     nvf > 0 ? nblk(nvf, PG_THREADS) : 0, c->n_cface > 0 && c->n_stvk > 0 ? nblk(c->n_cface, PG_THREADS) : 0,
+                     c->n_handle > 0 ? nblk(c->n_handle, PG_THREADS) : 0};
+  size_t off[6], tot = 0;
+  for (int q = 0; q < 6; q++) { off[q] = tot; if (need[q]) tot += (size_t)rows[q] * nb[q]; }
   if (tot > (size_t)INT32_MAX) return tsl_fail("tsl_param_grad_keys: too many partials");
   if (c->pg_part.n < std::max<size_t>(tot, 1)) TSL_TRY(c->pg_part.alloc(std::max<size_t>(tot, 1)));
   if (c->pg_out.n < (size_t)n_keys + 2) TSL_TRY(c->pg_out.alloc((size_t)n_keys + 2));
@@ -2350,6 +2425,7 @@ extern "C" int tsl_param_grad_keys(tsl_ctx* c, const double* pos, const double* 
     if (c->n_stvk > 0) hipLaunchKernelGGL(k_pg_face<true>, dim3(nb[0]), dim3(PG_THREADS), 0, s, cloth_args(c), n_cloth, pos, p, fz, part + off[0], stvk_args(c));
     else hipLaunchKernelGGL(k_pg_face<false>, dim3(nb[0]), dim3(PG_THREADS), 0, s, cloth_args(c), n_cloth, pos, p, fz, part + off[0], stvk_args(c));
   }
+  if (need[5] && nb[5]) hipLaunchKernelGGL(k_pg_handle, dim3(nb[5]), dim3(PG_THREADS), 0, s, handle_args(c), pos, p, fz, part + off[5]);
   if (need[4] && nb[4]) hipLaunchKernelGGL(k_pg_stvk, dim3(nb[4]), dim3(PG_THREADS), 0, s, cloth_args(c), n_cloth, pos, p, fz, part + off[4], stvk_args(c));
   if (need[1] && nb[1]) hipLaunchKernelGGL(k_pg_hinge, dim3(nb[1]), dim3(PG_THREADS), 0, s, cloth_args(c), n_cloth, pos, ref, p, fz, part + off[1]);
   if (need[2] && nb[2]) hipLaunchKernelGGL(k_pg_tet, dim3(nb[2]), dim3(PG_THREADS), 0, s, tet_args(c), n_el, pos, p, fz, part + off[2]);

@@ -30,6 +30,30 @@ class Body:
     f_end: int
 
 
+def validate_handles(tot_NV, vertex_ids, weights=None):
+    """The checks of tsl_set_handles on the host, with its messages: returns (int32 vertex ids, float64 weights or None) or raises ValueError naming
+    the offender -- a vertex outside [0, tot_NV), a vertex with more than one handle, a negative or non-finite weight."""
+    v = np.asarray(vertex_ids)
+    if v.ndim != 1 or (v.size and not np.issubdtype(v.dtype, np.integer)):
+        raise ValueError(f"set_handles: vertex ids must be a flat list of integers (got shape {v.shape}, dtype {v.dtype})")
+    v = v.astype(np.int64)
+    w = None
+    if weights is not None:
+        w = np.asarray(weights, dtype=np.float64)
+        if w.shape != v.shape:
+            raise ValueError(f"set_handles: {w.size} weights for {v.size} handles")
+    seen = set()
+    for i, vi in enumerate(v.tolist()):
+        if vi < 0 or vi >= tot_NV:
+            raise ValueError(f"set_handles: vertex {vi} out of range [0, {tot_NV})")
+        if vi in seen:
+            raise ValueError(f"set_handles: vertex {vi} has more than one handle")
+        seen.add(vi)
+        if w is not None and not (w[i] >= 0.0 and np.isfinite(w[i])):
+            raise ValueError(f"set_handles: weight {w[i]:g} of vertex {vi} is negative or not finite")
+    return v.astype(np.int32), w
+
+
 class _SystemMatrix:
     """Stand-in for ``SparseMatrix`` (sparse_solver.py): the matrix itself lives inside the context."""
 
@@ -81,6 +105,11 @@ class BaseScene:
         self._ctx = None
         self._dirty = set()
         self.last_stats = {}
+        # soft handles (set_handles): vertex ids, weights, targets and the stiffness k_handle, kept here and pushed to the engine context lazily
+        self._handle_v = np.zeros(0, np.int32)
+        self._handle_w = None
+        self._handle_t = np.zeros((0, 3))
+        self.k_handle = 0.0
 
         self.init_scene_parameters()
         if self.effector_cnt == -1:
@@ -349,8 +378,14 @@ class BaseScene:
                 for k, v in c._stvk_params():
                     self._ctx.set_param(f"cloth{i}.{k}", v)
             self._ctx.set_ext_force(self._ext_force_array())
+            if self.n_handle:
+                self._push_handles()
             self._dirty.clear()
         if self._dirty:
+            if "handles" in self._dirty:
+                self._push_handles()
+            elif "handle_targets" in self._dirty:
+                self._ctx.set_handle_targets(self._handle_t)
             if "frozen" in self._dirty:
                 self._ctx.set_frozen(self.frozen.to_numpy())
             if "border" in self._dirty:
@@ -380,6 +415,40 @@ class BaseScene:
         self.contact_ee = bool(on)
         if self._ctx is not None:
             self._ctx.set_param("contact_ee", int(self.contact_ee))
+
+    # ------------------------------------------------------------------ soft handles (no counterpart in the reference)
+    @property
+    def n_handle(self):
+        return len(self._handle_v)
+
+    def set_handles(self, vertex_ids, k, weights=None):
+        """Target springs on vertices: E_h = 1/2 k sum_i w_i |x_{v_i} - t_i|^2 with global vertex ids v_i (at most one handle per vertex), stiffness
+        k >= 0 in N/m and weights w_i >= 0 (None: all 1).  An empty list removes the handles.  The targets start at zero: set_handle_targets.
+        The lists are checked here, before any library call; the engine context receives them at its next use."""
+        v, w = validate_handles(self.tot_NV, vertex_ids, weights)
+        k = float(k)
+        if not (k >= 0.0 and np.isfinite(k)):
+            raise ValueError(f"set_handles: k_handle must be finite and >= 0 (got {k:g})")
+        self._handle_v, self._handle_w, self.k_handle = v, w, k
+        self._handle_t = np.zeros((len(v), 3))
+        self._dirty.add("handles")
+
+    def set_handle_targets(self, targets):
+        """world-space targets (n, 3) of the next energy, assembly, time step or reverse step"""
+        t = np.array(targets.detach().cpu().numpy() if isinstance(targets, torch.Tensor) else targets, dtype=np.float64)
+        if t.shape != (self.n_handle, 3):
+            raise ValueError(f"set_handle_targets: targets of shape {t.shape} for {self.n_handle} handles (expected ({self.n_handle}, 3))")
+        self._handle_t = t
+        self._dirty.add("handle_targets")
+
+    def handle_force(self):
+        """(n, 3): the force k w_i (t_i - x_{v_i}) every handle applies to the cloth at the current positions"""
+        return self._ensure_ctx().handle_force(self.pos.t)
+
+    def _push_handles(self):
+        self._ctx.set_handles(self._handle_v, self._handle_w)
+        self._ctx.set_param("k_handle", self.k_handle)
+        self._ctx.set_handle_targets(self._handle_t)
 
     def set_frozen_kernel(self):
         # BaseScene.py:1445-1463

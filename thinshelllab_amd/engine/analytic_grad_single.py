@@ -12,6 +12,27 @@ import torch
 from .field import Field
 
 
+# ---- soft handles on the tape (BaseScene.set_handles; shared with analytic_grad_system.Grad and SceneGroup.transfer_grad)
+def handle_tape_init(grad, sys, T):
+    """handle_targets / handle_grad (T, n, 3) when the scene has handles; nothing otherwise"""
+    grad.n_handle = getattr(sys, "n_handle", 0)
+    if grad.n_handle:
+        grad.handle_targets = Field(torch.zeros((T, grad.n_handle, 3), dtype=torch.float64))
+        grad.handle_grad = Field(torch.zeros((T, grad.n_handle, 3), dtype=torch.float64))
+
+
+def handle_tape_push(grad, sys, step):
+    """the targets of step `step` back into the scene: the reverse step re-assembles at x_step and reads them"""
+    if grad.n_handle:
+        sys.set_handle_targets(grad.handle_targets.t[step].numpy())
+
+
+def handle_tape_pull(grad, ctx, step):
+    """handle_grad[step] += d(loss)/d(targets of step `step`) of the reverse step just taken"""
+    if grad.n_handle:
+        grad.handle_grad.t[step] += torch.as_tensor(ctx.handle_grad())
+
+
 class Grad:
     def __init__(self, sys, tot_timestep, n_parts, friction_loss=False, f_loss_ratio=0.001, vertical_only=False):
         # analytic_grad_single.py:5-26
@@ -38,11 +59,15 @@ class Grad:
         self.f_loss_ratio = f_loss_ratio
         self.vertical_only = vertical_only
         self.last_stats = {}
+        handle_tape_init(self, sys, T)
 
     def reset(self):
         self.pos_buffer.fill(0)
         self.pos_grad.fill(0)
         self.angleref_grad.fill(0)
+        if self.n_handle:
+            self.handle_targets.fill(0)
+            self.handle_grad.fill(0)
 
     def init_mass(self, sys):
         self.mass.copy_from(sys.mass)
@@ -51,6 +76,8 @@ class Grad:
     def copy_pos(self, sys, step):
         self.pos_buffer.t[step].copy_(sys.pos.t)
         self.ref_angle_buffer.t[step].view(-1, 3).copy_(sys._ref_angle[: self.cloth_cnt * self.NF])
+        if self.n_handle:
+            self.handle_targets.t[step] = torch.as_tensor(sys._handle_t)
         if self.n_part > 0 and hasattr(sys, "gripper"):
             self.gripper_pos_buffer.t[step].copy_(sys.gripper.pos.t)
             self.gripper_rot_buffer.t[step].copy_(sys.gripper.rot.t)
@@ -74,11 +101,13 @@ class Grad:
 
     # :217-257
     def transfer_grad(self, step, sys, f_contact):
+        handle_tape_push(self, sys, step)
         ctx = sys._ensure_ctx()
         ctx.set_param("contact", 0.0 if f_contact is None else 1.0)
         self.last_stats = ctx.adjoint_step(step, self.tot_timestep, self.pos_buffer.t, self.pos_grad.t, self.ref_angle_buffer.t, self.angleref_grad.t,
                                            sys.tmp_z_frozen.t, self.damping)
         self.check_solve(step)
+        handle_tape_pull(self, ctx, step)
         # leave the scene in the state the reference leaves it in (copy_pos_and_refangle + gripper.set)
         sys.copy_pos_and_refangle(self, step)
         if self.n_part > 0 and hasattr(sys, "gripper"):

@@ -8,11 +8,12 @@ accumulates the parameter gradients ``grad_kb`` / ``grad_mu`` / ``grad_lam`` = s
 ``Scene_sliding`` (``contact_energy_backprop_friction``, Scene_sliding.py:139-176, ``tsl_friction_grad``).
 
 Beyond the reference: ``param_keys`` names further scalars, spelled as ``tsl_set_param`` spells them ("cloth<i>.Kl|Ka|Kb",
-"cloth<i>.stvk_mu|stvk_lam" (StVK membrane), "elastic<i>.mu|lam", "k_contact", "mu_cloth_elastic", "mu_cloth_cloth"); every reverse step then adds their
+"cloth<i>.stvk_mu|stvk_lam" (StVK membrane), "elastic<i>.mu|lam", "k_contact", "mu_cloth_elastic", "mu_cloth_cloth", "k_handle" (soft handles)); every reverse step then adds their
 ``p . d(force)/d(key)`` (``tsl_param_grad_keys``) to ``grad_params[key]``.  Empty (the default): no such call, the reference's behaviour.
 """
 import torch
 
+from .analytic_grad_single import handle_tape_init, handle_tape_pull, handle_tape_push
 from .field import Field, ScalarField
 
 
@@ -49,6 +50,7 @@ class Grad:
         self.param_keys = []
         self.grad_params = {}
         self.last_stats = {}
+        handle_tape_init(self, sys, T)
 
     def reset(self):  # :33-39
         self.pos_buffer.fill(0)
@@ -58,6 +60,9 @@ class Grad:
         self.grad_friction_coef[None] = 0
         self.grad_kb[None] = 0
         self.grad_params = {}
+        if self.n_handle:
+            self.handle_targets.fill(0)
+            self.handle_grad.fill(0)
 
     def init_mass(self, sys):  # :41-44
         self.mass.copy_from(sys.mass)
@@ -65,6 +70,8 @@ class Grad:
     def copy_pos(self, sys, step):  # :46-59
         self.pos_buffer.t[step].copy_(sys.pos.t)
         self.ref_angle_buffer.t[step].view(-1, 3).copy_(sys._ref_angle[: self.cloth_cnt * self.NF])
+        if self.n_handle:
+            self.handle_targets.t[step] = torch.as_tensor(sys._handle_t)
         if self.n_part > 0 and hasattr(sys, "gripper"):
             self.gripper_pos_buffer.t[step].copy_(sys.gripper.pos.t)
             self.gripper_rot_buffer.t[step].copy_(sys.gripper.rot.t)
@@ -77,6 +84,7 @@ class Grad:
         self.pos_grad.t[step].clamp_(-1, 1)
 
     def transfer_grad(self, step, sys, f_contact):  # :112-160
+        handle_tape_push(self, sys, step)
         ctx = sys._ensure_ctx()
         ctx.set_param("contact", 0.0 if f_contact is None else 1.0)
         ctx.set_param("adj_clamp", 1.0); ctx.set_param("adj_clamp_angleref", 0.0)
@@ -84,6 +92,7 @@ class Grad:
             self.last_stats = ctx.adjoint_step(step, self.tot_timestep, self.pos_buffer.t, self.pos_grad.t, self.ref_angle_buffer.t, self.angleref_grad.t,
                                                sys.tmp_z_frozen.t, self.damping)
             self.check_solve(step)
+            handle_tape_pull(self, ctx, step)
             if self.count_friction_grad:   # :150-153: either the friction coefficient or the stiffness parameters
                 self.grad_friction_coef[None] = self.grad_friction_coef[None] + ctx.friction_grad(self.pos_buffer.t[step])
                 g = dict(kb=0.0, mu=0.0, lam=0.0)

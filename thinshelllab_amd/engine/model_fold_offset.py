@@ -75,6 +75,11 @@ class Cloth:
         self.membrane[None] = 1.0
         return mu, lam
 
+    def corner_ids(self):
+        """global vertex ids of the four grid corners (i, j) = (0, 0), (0, M), (N, 0), (N, M) -- e.g. for BaseScene.set_handles"""
+        N, M = self.N, self.M
+        return [self.offset + v for v in (0, M, N * (M + 1), N * (M + 1) + M)]
+
     def _stvk_params(self):
         """(key suffix, value) of the membrane settings that differ from the defaults (pushed by BaseScene when it creates the engine context)"""
         return [(k, f.value) for k, f in (("stvk_mu", self.stvk_mu), ("stvk_lam", self.stvk_lam), ("membrane", self.membrane)) if f.value != 0.0]

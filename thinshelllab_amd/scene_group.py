@@ -12,6 +12,7 @@ import ctypes as C
 from . import _lib
 from ._lib import SolveStats, StepStats, check
 from .context import _ptr
+from .engine.analytic_grad_single import handle_tape_pull, handle_tape_push
 
 
 class SceneGroup:
@@ -78,6 +79,7 @@ class SceneGroup:
         damp = (C.c_double * n)()
         for i, (s, g) in enumerate(zip(self.scenes, grads)):
             assert g.tot_timestep == T, "the members' tapes must have one length"
+            handle_tape_push(g, s, step)   # (soft handles: every member's own targets of this step)
             ctx = s._ensure_ctx()
             ctx.set_param("contact", 0.0 if f_contact is None else 1.0)
             ctx.refresh_stream()
@@ -90,6 +92,7 @@ class SceneGroup:
         for s, g, r in zip(self.scenes, grads, st):
             g.last_stats = r.as_dict()
             g.check_solve(step)
+            handle_tape_pull(g, s._ensure_ctx(), step)
             s.copy_pos_and_refangle(g, step)
             if g.n_part > 0 and hasattr(s, "gripper"):
                 s.gripper.set(g.gripper_pos_buffer, g.gripper_rot_buffer, step)
