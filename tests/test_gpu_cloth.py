@@ -61,9 +61,10 @@ def test_energy_gradient_hessian(oracle, N, M):
         assert o.stats()["missing"] == 0
 
 
-@pytest.mark.parametrize("N,M", [(12, 12), (15, 9), (32, 16)])
+@pytest.mark.parametrize("N,M", [(12, 12), (15, 9), (32, 16), (34, 18)])
 def test_solve_matches_spsolve(oracle, N, M):
-    """(12,12), (32,16): multigrid-preconditioned PCG (2 and 3 levels); (15,9): block-Jacobi PCG"""
+    """(12,12), (32,16): multigrid-preconditioned PCG (2 and 3 levels); (15,9): block-Jacobi PCG; (34,18): one stencil level of 18 x 10
+    nodes, too large for the dense inverse and the one-workgroup kernel: the last level is smoothed by Jacobi sweeps, one launch each"""
     import scipy.sparse.linalg as spl
     sys, o = _pair(oracle, N, M, amp=5e-5)
     sys.compute_residual_and_Hessian(spd=True)

@@ -7,7 +7,7 @@
 // products A_{l+1} = P^T A_l P recomputed after every assembly.  Level 0 is the global SELL-64 operator (all bodies +
 // matrix-free contact blocks); FEM vertices and contact couplings are only smoothed there.  Levels >= 1 are stored as a
 // radius-2 block stencil (25 slots x 9 doubles per vertex, slot-major / SoA so that every load of a wave is contiguous).
-// Cycle: V(nu,nu) with damped block-Jacobi smoothing (symmetric => the preconditioner is SPD and PCG stays valid).
+// Cycle: V(1,1) with damped block-Jacobi smoothing (symmetric => the preconditioner is SPD and PCG stays valid).
 #pragma once
 #include "k_solver.hpp"
 #include "tsl_ctx.hpp"
@@ -23,31 +23,6 @@ TSL_DEV int mg_coarse(int i, int q, double& w) {
 struct MgGrid { int N, M; };  // cells; vertices (N+1) x (M+1), index i*(M+1)+j
 
 // ---- stencil-level kernels (levels >= 1).  A[(s*9+e)*n + row], s = (dI+2)*5 + (dJ+2)
-__global__ void k_st_spmv(MgGrid g, const double* __restrict__ A, const double* __restrict__ x, double* __restrict__ y) {
-  const int n = (g.N + 1) * (g.M + 1);
-  const int row = blockIdx.x * blockDim.x + threadIdx.x;
-  if (row >= n) return;
-  const int I = row / (g.M + 1), J = row % (g.M + 1);
-  double y0 = 0, y1 = 0, y2 = 0;
-#pragma unroll
-  for (int dI = -2; dI <= 2; dI++) {
-    const int I2 = I + dI;
-    if (I2 < 0 || I2 > g.N) continue;
-#pragma unroll
-    for (int dJ = -2; dJ <= 2; dJ++) {
-      const int J2 = J + dJ;
-      if (J2 < 0 || J2 > g.M) continue;
-      const int s = (dI + 2) * 5 + (dJ + 2);
-      const double* a = A + (size_t)s * 9 * n + row;
-      const d3 xj = ld3(x, I2 * (g.M + 1) + J2);
-      y0 += a[0] * xj.x + a[(size_t)n] * xj.y + a[2 * (size_t)n] * xj.z;
-      y1 += a[3 * (size_t)n] * xj.x + a[4 * (size_t)n] * xj.y + a[5 * (size_t)n] * xj.z;
-      y2 += a[6 * (size_t)n] * xj.x + a[7 * (size_t)n] * xj.y + a[8 * (size_t)n] * xj.z;
-    }
-  }
-  st3(y, row, d3(y0, y1, y2));
-}
-
 // 5 lanes per row (one per stencil row dI): 64 rows x 5 = 320 threads per block; partial sums meet in LDS.
 // FUSE = 0: y = A x.   FUSE = 1: x_out = x + omega * Dinv * (r - A x)  (one damped-Jacobi sweep, ping-pong buffers).
 template <int FUSE>
@@ -95,58 +70,13 @@ k_st_spmv5(MgGrid g, const double* __restrict__ A, const double* __restrict__ x,
 
 // ---- fused variants: a V-cycle is a chain of dependent launches of 4-5 us each on a few thousand nodes, so the number
 // of launches, not the arithmetic, sets its cost.
-// (1) first sweep from a zero guess + residual product: x = omega Dinv r, t = A x with the neighbours' x recomputed on the fly
-__global__ void __launch_bounds__(320)
-k_st_first_resid(MgGrid g, const double* __restrict__ A, const double* __restrict__ Dinv, const double* __restrict__ r, const double* __restrict__ omega_dev,
-                 double* __restrict__ x, double* __restrict__ t) {
-  __shared__ double red[5][3][64];
-  const int n = (g.N + 1) * (g.M + 1);
-  const int lane = threadIdx.x & 63, q = threadIdx.x >> 6;
-  const int row = blockIdx.x * 64 + lane;
-  const double omega = *omega_dev;
-  double y0 = 0, y1 = 0, y2 = 0;
-  if (row < n) {
-    const int I = row / (g.M + 1), J = row % (g.M + 1);
-    const int I2 = I + q - 2;
-    if (I2 >= 0 && I2 <= g.N) {
-#pragma unroll
-      for (int dJ = -2; dJ <= 2; dJ++) {
-        const int J2 = J + dJ;
-        if (J2 < 0 || J2 > g.M) continue;
-        const int s = q * 5 + (dJ + 2);
-        const double* a = A + (size_t)s * 9 * n + row;
-        const int c = I2 * (g.M + 1) + J2;
-        m3 D;
-#pragma unroll
-        for (int e = 0; e < 9; e++) D.m[e] = Dinv[9 * (size_t)c + e];
-        const d3 xj = omega * m3_mulv(D, ld3(r, c));
-        y0 += a[0] * xj.x + a[(size_t)n] * xj.y + a[2 * (size_t)n] * xj.z;
-        y1 += a[3 * (size_t)n] * xj.x + a[4 * (size_t)n] * xj.y + a[5 * (size_t)n] * xj.z;
-        y2 += a[6 * (size_t)n] * xj.x + a[7 * (size_t)n] * xj.y + a[8 * (size_t)n] * xj.z;
-      }
-    }
-  }
-  red[q][0][lane] = y0; red[q][1][lane] = y1; red[q][2][lane] = y2;
-  __syncthreads();
-  if (q == 0 && row < n) {
-#pragma unroll
-    for (int k = 1; k < 5; k++) { y0 += red[k][0][lane]; y1 += red[k][1][lane]; y2 += red[k][2][lane]; }
-    st3(t, row, d3(y0, y1, y2));
-    m3 D;
-#pragma unroll
-    for (int e = 0; e < 9; e++) D.m[e] = Dinv[9 * (size_t)row + e];
-    st3(x, row, omega * m3_mulv(D, ld3(r, row)));
-  }
-}
-
-// (1b) first sweep + residual + restriction in ONE launch.  With x = omega Dinv r the restricted residual is
+// (1) first sweep from a zero guess + residual + restriction in ONE launch.  With x = omega Dinv r the restricted residual is
 //   rc = P^T (r - A x) = P^T r - omega (P^T A Dinv) r,
 // so the operator S = P^T A Dinv is formed once per assembly (k_st_build_ra): 49 slots per COARSE node (restriction radius 1 +
 // stencil radius 2 on the fine grid), i.e. 12.25 blocks per fine node instead of the 25 of A, and the fine-level residual is never
 // formed (the post-sweep recomputes A x from scratch anyway).  One launch and half the bytes less per level and cycle.
-// S[(s*9+e)*nc + crow], s = (dI+3)*7 + (dJ+3), column = fine node (2I+dI, 2J+dJ)
-template <typename VT>
-__global__ void k_st_build_ra(MgGrid gf, const VT* __restrict__ A, const double* __restrict__ Dinv, VT* __restrict__ S) {
+// S[(s*9+e)*nc + crow], s = (dI+3)*7 + (dJ+3), column = fine node (2I+dI, 2J+dJ).  A and S are the single-precision copies the cycle reads.
+__global__ void k_st_build_ra(MgGrid gf, const float* __restrict__ A, const double* __restrict__ Dinv, float* __restrict__ S) {
   const int Nc = gf.N >> 1, Mc = gf.M >> 1;
   const int nc = (Nc + 1) * (Mc + 1), nf = (gf.N + 1) * (gf.M + 1);
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
@@ -158,10 +88,10 @@ __global__ void k_st_build_ra(MgGrid gf, const VT* __restrict__ A, const double*
   double acc[9];
 #pragma unroll
   for (int e = 0; e < 9; e++) acc[e] = 0.0;
-  VT* dst = S + (size_t)s * 9 * nc + crow;
+  float* dst = S + (size_t)s * 9 * nc + crow;
   if (ci < 0 || ci > gf.N || cj < 0 || cj > gf.M) {
 #pragma unroll
-    for (int e = 0; e < 9; e++) dst[(size_t)e * nc] = (VT)0;
+    for (int e = 0; e < 9; e++) dst[(size_t)e * nc] = (float)0;
     return;
   }
 #pragma unroll
@@ -173,7 +103,7 @@ __global__ void k_st_build_ra(MgGrid gf, const VT* __restrict__ A, const double*
       const int j = 2 * J + dj, b = dJ - dj;
       if (j < 0 || j > gf.M || b < -2 || b > 2) continue;
       const double w = (di == 0 ? 1.0 : 0.5) * (dj == 0 ? 1.0 : 0.5);
-      const VT* src = A + (size_t)((a + 2) * 5 + (b + 2)) * 9 * nf + (i * (gf.M + 1) + j);
+      const float* src = A + (size_t)((a + 2) * 5 + (b + 2)) * 9 * nf + (i * (gf.M + 1) + j);
 #pragma unroll
       for (int e = 0; e < 9; e++) acc[e] += w * (double)src[(size_t)e * nf];
     }
@@ -185,20 +115,20 @@ __global__ void k_st_build_ra(MgGrid gf, const VT* __restrict__ A, const double*
 #pragma unroll
   for (int r = 0; r < 3; r++)
 #pragma unroll
-    for (int cc = 0; cc < 3; cc++) dst[(size_t)(3 * r + cc) * nc] = (VT)(acc[3 * r] * d[cc] + acc[3 * r + 1] * d[3 + cc] + acc[3 * r + 2] * d[6 + cc]);
+    for (int cc = 0; cc < 3; cc++) dst[(size_t)(3 * r + cc) * nc] = (float)(acc[3 * r] * d[cc] + acc[3 * r + 1] * d[3 + cc] + acc[3 * r + 2] * d[6 + cc]);
 }
 
-// ROWS coarse nodes per workgroup, 7 threads per node (one per fine row offset dI); threads 1..4 of a node also write the
+// ST_FR_ROWS coarse nodes per workgroup (16 and 64 were measured too), 7 threads per node (one per fine row offset dI); threads 1..4 of a node also write the
 // smoothed iterate x = omega Dinv r of its four fine nodes (2I + {0,1}, 2J + {0,1}), thread 0 the coarse right-hand side.
-template <int ROWS, typename VT>
-__global__ void __launch_bounds__(7 * ROWS)
-k_st_first_restrict(MgGrid g, const VT* __restrict__ S, const double* __restrict__ Dinv, const double* __restrict__ r, const double* __restrict__ omega_dev,
+static constexpr int ST_FR_ROWS = 32;
+__global__ void __launch_bounds__(7 * ST_FR_ROWS)
+k_st_first_restrict(MgGrid g, const float* __restrict__ S, const double* __restrict__ Dinv, const double* __restrict__ r, const double* __restrict__ omega_dev,
                     double* __restrict__ x, double* __restrict__ rc) {
-  __shared__ double red[7][3][ROWS];
+  __shared__ double red[7][3][ST_FR_ROWS];
   const int Nc = g.N >> 1, Mc = g.M >> 1;
   const int nc = (Nc + 1) * (Mc + 1);
-  const int lane = threadIdx.x % ROWS, q = threadIdx.x / ROWS;
-  const int crow = blockIdx.x * ROWS + lane;
+  const int lane = threadIdx.x % ST_FR_ROWS, q = threadIdx.x / ST_FR_ROWS;
+  const int crow = blockIdx.x * ST_FR_ROWS + lane;
   const double omega = *omega_dev;
   double y0 = 0, y1 = 0, y2 = 0;
   int I = 0, J = 0;
@@ -210,7 +140,7 @@ k_st_first_restrict(MgGrid g, const VT* __restrict__ S, const double* __restrict
       for (int dJ = -3; dJ <= 3; dJ++) {
         const int j2 = 2 * J + dJ;
         if (j2 < 0 || j2 > g.M) continue;
-        const VT* a = S + (size_t)(q * 7 + dJ + 3) * 9 * nc + crow;
+        const float* a = S + (size_t)(q * 7 + dJ + 3) * 9 * nc + crow;
         const d3 rj = ld3(r, i2 * (g.M + 1) + j2);
         y0 += a[0] * rj.x + a[(size_t)nc] * rj.y + a[2 * (size_t)nc] * rj.z;
         y1 += a[3 * (size_t)nc] * rj.x + a[4 * (size_t)nc] * rj.y + a[5 * (size_t)nc] * rj.z;
@@ -279,9 +209,8 @@ TSL_DEV d3 st_prolonged(MgGrid gf, const double* __restrict__ x, const double* _
 // The 25 neighbours of the workgroup's 64 consecutive nodes lie in five runs of 68 consecutive linear indices (one per stencil row
 // dI; a linear index that wraps into the adjacent grid row is never used: those slots fail the bounds test), so xt is formed ONCE
 // per run entry and staged in LDS (340 prolongations per workgroup instead of 1600 gathers of up to five vectors each).
-template <typename VT>
 __global__ void __launch_bounds__(320)
-k_st_prolong_sweep(MgGrid g, const VT* __restrict__ A, const double* __restrict__ x, const double* __restrict__ xc, double* __restrict__ y,
+k_st_prolong_sweep(MgGrid g, const float* __restrict__ A, const double* __restrict__ x, const double* __restrict__ xc, double* __restrict__ y,
                    const double* __restrict__ Dinv, const double* __restrict__ r, const double* __restrict__ omega_dev) {
   __shared__ double red[5][3][64];
   __shared__ double xt[5][68][3];
@@ -317,7 +246,7 @@ k_st_prolong_sweep(MgGrid g, const VT* __restrict__ A, const double* __restrict_
         const int J2 = J + dJ;
         if (J2 < 0 || J2 > g.M) continue;
         const int s = q * 5 + (dJ + 2);
-        const VT* a = A + (size_t)s * 9 * n + row;
+        const float* a = A + (size_t)s * 9 * n + row;
         const double* xv = xt[q][lane + dJ + 2];
         const double x0 = xv[0], x1 = xv[1], x2 = xv[2];
         y0 += a[0] * x0 + a[(size_t)n] * x1 + a[2 * (size_t)n] * x2;
@@ -673,55 +602,7 @@ k_mg_jacobi_next(int n, const double* __restrict__ Dinv, const double* __restric
   }
 }
 
-// rc = P^T (r - t) from a fine STENCIL level (t may be null)
-__global__ void k_st_restrict(MgGrid gf, const double* __restrict__ r, const double* __restrict__ t, double* __restrict__ rc) {
-  const int Nc = gf.N >> 1, Mc = gf.M >> 1;
-  const int nc = (Nc + 1) * (Mc + 1);
-  const int row = blockIdx.x * blockDim.x + threadIdx.x;
-  if (row >= nc) return;
-  const int I = row / (Mc + 1), J = row % (Mc + 1);
-  d3 acc = d3();
-#pragma unroll
-  for (int di = -1; di <= 1; di++) {
-    const int i = 2 * I + di;
-    if (i < 0 || i > gf.N) continue;
-#pragma unroll
-    for (int dj = -1; dj <= 1; dj++) {
-      const int j = 2 * J + dj;
-      if (j < 0 || j > gf.M) continue;
-      const double w = (di == 0 ? 1.0 : 0.5) * (dj == 0 ? 1.0 : 0.5);
-      const int f = i * (gf.M + 1) + j;
-      d3 v = ld3(r, f);
-      if (t) v = v - ld3(t, f);
-      acc = acc + w * v;
-    }
-  }
-  st3(rc, row, acc);
-}
-
-// x_f += P x_c on a fine STENCIL level
-__global__ void k_st_prolong_add(MgGrid gf, const double* __restrict__ xc, double* __restrict__ x) {
-  const int n = (gf.N + 1) * (gf.M + 1);
-  const int Mc = gf.M >> 1;
-  const int f = blockIdx.x * blockDim.x + threadIdx.x;
-  if (f >= n) return;
-  const int i = f / (gf.M + 1), j = f % (gf.M + 1);
-  d3 acc = d3();
-#pragma unroll
-  for (int a = 0; a < 2; a++) {
-    double wa; const int I = mg_coarse(i, a, wa);
-    if (wa == 0.0) continue;
-#pragma unroll
-    for (int b = 0; b < 2; b++) {
-      double wb; const int J = mg_coarse(j, b, wb);
-      if (wb == 0.0) continue;
-      acc = acc + (wa * wb) * ld3(xc, I * (Mc + 1) + J);
-    }
-  }
-  st3(x, f, ld3(x, f) + acc);
-}
-
-// same two transfers between level 0 (global permuted vectors) and level 1 of one cloth
+// transfers between level 0 (global permuted vectors) and level 1 of one cloth: rc = P^T (r - t), x_f += P x_c
 __global__ void k_mg_restrict0(MgGrid gf, int v_offset, const int* __restrict__ rowpos, const double* __restrict__ r, const double* __restrict__ t,
                                double* __restrict__ rc) {
   const int Nc = gf.N >> 1, Mc = gf.M >> 1;
@@ -868,17 +749,6 @@ __global__ void k_st_diag_inv(int n, const double* __restrict__ A, double* __res
   const m3 Di = m3_inv(D);
 #pragma unroll
   for (int e = 0; e < 9; e++) Dinv[9 * (size_t)row + e] = Di.m[e];
-}
-
-// x (+)= alpha-free helpers on level-0 vectors
-__global__ void k_part_dot(int n, const double* __restrict__ a, const double* __restrict__ b, double* __restrict__ part) {
-  const int p = blockIdx.x * blockDim.x + threadIdx.x;
-  double acc = (p < n) ? dot(ld3(a, p), ld3(b, p)) : 0.0;
-  __shared__ double s1[4];
-  acc = wave_sum(acc);
-  if ((threadIdx.x & 63) == 0) s1[threadIdx.x >> 6] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) part[blockIdx.x] = s1[0] + s1[1] + s1[2] + s1[3];
 }
 
 // ---- damping factor from a power iteration on D^-1 A (device resident, no host round trip)

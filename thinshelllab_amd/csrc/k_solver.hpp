@@ -394,7 +394,7 @@ k_pcg_spmv(int NV, int n_slices, const int* __restrict__ slice_off, const int* _
   constexpr int MAXU = PCG_MAXPART / (64 * WPS);
   double pz[MAXU], pr[MAXU];
   {
-    const int n = sc->n_part2;   // <= PCG_MAXPART (solve_perm)
+    const int n = sc->n_part2;   // <= PCG_MAXPART (pcg_restarts)
 #pragma unroll
     for (int u = 0; u < MAXU; u++) {
       const int i = (int)threadIdx.x + 64 * WPS * u;
@@ -559,25 +559,6 @@ __global__ void k_sum_partials(const double* __restrict__ part, int n, double* o
   __shared__ double sm[8];
   const double t = block_reduce_partials(part, n, sm);
   if (threadIdx.x == 0) out[0] = t;
-}
-
-// r = b - Ax ; z = Dinv r ; p = z ; rzn[3] = r.z ; rr[3] = r.r   (start / restart of PCG)
-__global__ void k_cg_init(int NV, const double* __restrict__ b, const double* __restrict__ Ax, const double* __restrict__ Dinv,
-                          double* __restrict__ r, double* __restrict__ z, double* __restrict__ pv, CgScal* sc) {
-  const int p = blockIdx.x * blockDim.x + threadIdx.x;
-  double rz = 0, rr = 0;
-  if (p < NV) {
-    d3 rv = ld3(b, p);
-    if (Ax) rv = rv - ld3(Ax, p);
-    m3 D;
-#pragma unroll
-    for (int e = 0; e < 9; e++) D.m[e] = Dinv[9 * (size_t)p + e];
-    const d3 zv = m3_mulv(D, rv);
-    st3(r, p, rv); st3(z, p, zv); st3(pv, p, zv);
-    rz = dot(rv, zv); rr = dot(rv, rv);
-  }
-  rz = wave_sum(rz); rr = wave_sum(rr);
-  if ((threadIdx.x & 63) == 0) { atomicAdd(&sc->rzn[3], rz); atomicAdd(&sc->rr[3], rr); }
 }
 
 // alpha = rz/pAp ; x += alpha p ; r -= alpha Ap ; z = Dinv r ; rzn[slot] += r.z ; rr[slot] += r.r

@@ -82,8 +82,8 @@ struct SolverScalars {
 struct MgLevel {
   int N = 0, M = 0, n = 0;
   DevBuf<double> A, Dinv, x, x2, r, t;
-  DevBuf<float> A32, S32;  // single-precision copies for the two cycle kernels of the level (mg_st_f32)
-  DevBuf<double> S;      // P^T A Dinv towards the next level (49 slots per coarse node, k_st_build_ra); empty on the last level
+  DevBuf<float> A32, S32;  // what the two cycle kernels of the level read: A rounded to single precision, and S = P^T A32 Dinv towards the next level
+                           // (49 slots per coarse node, k_st_build_ra); empty on the last level
   DevBuf<double> omega;  // [0] damping factor, [1] lambda_max estimate (device resident)
   DevBuf<float> Cinv;    // dense inverse of the last level of the hierarchy (blocked Gauss-Jordan per assembly), symmetrised, fp32
   DevBuf<int> cbad;
@@ -210,14 +210,13 @@ struct tsl_ctx {
   long pcg_graph_key = -1;
   hipGraphExec_t mr_graph = nullptr;  // six MINRES iterations
   long mr_graph_key = -1;
-  int use_graph = 1;
   int NV = 0, NF = 0;  // tot_NV, tot_NF
   double dt = 5e-3, k_contact = 1000, eps_contact = 1e-3, eps_v = 0.01, damping = 1.0, mu_cloth_elastic = 1.0, mu_cloth_cloth = 1.0;
   int max_n_constraints = 10000;
   int newton_cap = 1000, plastic = 0, contact_enable = 1;
   int spd_literal = 0;   // 1: the forward projections of the spring, contact-normal and element blocks run the reference's Householder + QR projector (spd_literal3 / spd_literal9_coop)
   double cg_tol = 1e-10;
-  int cg_maxit = 200000, cg_check = 32;
+  int cg_maxit = 200000;
   double grid_h = 0.003;
   double grid_extent = 0.2;  // half-width of the broad-phase box (geometry.py:8-19 hard-codes 0.2 m)
 
@@ -268,9 +267,7 @@ struct tsl_ctx {
   std::vector<std::vector<int>> h_rows;  // original-order adjacency (sorted)
   DevBuf<int> rowpos, perm, slice_off, slice_len, colidx, diag_perm;
   DevBuf<double> vals, vals_full;  // masked (solver) and unmasked (adjoint) copies
-  DevBuf<float> vals32;            // single-precision copy of the preconditioner's matrix for the multigrid smoother products
-  bool vals32_valid = false;
-  int mg_f32 = 1;
+  DevBuf<float> vals32;            // single-precision copy of the preconditioner's matrix for the multigrid smoother products (mg_setup_operators)
   DevBuf<double> Dinv;             // NV x 9 (permuted)
   DevBuf<unsigned char> fzmask;    // NV (permuted) 3-bit frozen mask
   DevBuf<double> mdt2;             // NV (permuted) m/dt^2
@@ -286,11 +283,6 @@ struct tsl_ctx {
   DevBuf<int> bd_rows, bd_body_of, bd_local_of, bd_bad;
   DevBuf<double> bd_W, bd_scr;
   DevBuf<double> bd_rb;  // compact ping-pong copy of the PCG residual on the dense-body rows (body part of k_pcg_update)
-  int pcg_body_fold = 1;
-  int mg_st_f32 = 1;
-  int mg_chunk = 0;      // multigrid-PCG iterations per hipGraph replay / host convergence read (0: 8 on long solves, else 4)
-  double mr_eta = 0.3;   // MINRES stops a recurrence cycle at |eta| <= mr_eta * tol (scaled); the true residual decides afterwards
-  int mg_fr_rows = 32;   // coarse nodes per workgroup of k_st_first_restrict (16 / 32 / 64)
   DevBuf<float> bd_Binv;
   DevBuf<double> gm_V, gm_h;  // GMRES basis ((m+1) vectors) and projection coefficients
   DevBuf<double> gm_Z;        // preconditioned basis of the flexible variant (direct preconditioner)
@@ -316,7 +308,7 @@ struct tsl_ctx {
   double* h_ir = nullptr;     // pinned host copy of {r.r, x.x, b.b, max |x_i|}
   double last_xmax = 0;       // max |x_i| of the solution direct_refine returned (the Newton loop's |p|max)
   bool last_xmax_valid = false;
-  int gmres_m = 300, use_gmres = 1, use_minres = 1, verbose = 0;
+  int gmres_m = 300, verbose = 0;
   // analytic_grad_system.Grad: pos_grad clamp (1 there, 1000 in analytic_grad_single) and whether angleref_grad is clamped too
   double adj_clamp = 1000.0;
   int adj_clamp_angleref = 1;
@@ -328,7 +320,6 @@ struct tsl_ctx {
   bool cdiag_valid = false;   // c_diag holds the diagonal blocks of the contact terms in place (an assembly for the direct path does not form them)
   bool dinv_valid = false;    // Dinv holds the block-Jacobi inverse of the operator in place (an assembly for the direct path does not form it)
   const double *st_pos = nullptr, *st_prev = nullptr, *st_vel = nullptr, *st_ref = nullptr;  // state of the last assemble
-  int fwd_spd_pc = 1;
   int adj_spd_pc = 1;
   DevBuf<SolverScalars> scal;
   DevBuf<double> part_pAp, part_rz, part_rr;  // per-block partial sums of the two-kernel PCG iteration
@@ -389,14 +380,11 @@ struct tsl_ctx {
   // ---- multigrid preconditioner
   std::vector<MgCloth*> mg;
   int mg_enable = -1;  // -1 auto (on when a cloth hierarchy exists), 0 off, 1 on
-  double mg_omega = 0.0;   // > 0: fixed damping; 0: 1.5 / lambda_max(D^-1 A) per level from a power iteration
-  int mg_pi_iters = 12;
   DevBuf<double> mg_omega0, mg_pi_part, mg_pi_norm;  // level 0
-  int mg_nu = 1, mg_coarse_sweeps = 8, mg_fuse = 1, mg_fuse_restrict = 1, mg_max_levels = 16, mg_coarse_exact = 1, mg_coarse_lag = 0, mg_dense_nodes = 64, mg_dense_auto = 1;
+  int mg_coarse_exact = 1, mg_dense_nodes = 64, mg_dense_auto = 1;
   double last_step_iters_per_solve = 0.0;
-  bool warm_valid = false;
-  bool mg_cinv_valid = false;
-  bool mg_ops_valid = false, mg_suspended = false, mg_omega_valid = false;
+  bool mg_ops_valid = false, mg_omega_valid = false;
+  bool mg_suspended = false;  // set (Suspend) while plain block-Jacobi PCG retries a solve the multigrid-PCG stalled on: read by mg_active
 
   // ---- profiling of the dominant kernel
   int prof_enable = 0;
@@ -415,8 +403,7 @@ struct tsl_ctx {
   bool ev_sample_next = false;
 
   DirectSolver ds;
-  bool ds_probe = false;      // set while the iterative hierarchy runs as the capped probe of the auto mode
-  bool ds_suspended = false;  // set while the iterative hierarchy runs as the fallback of a failed direct solve
+  bool ds_suspended = false;  // set (Suspend) while the iterative hierarchy runs as the probe or the fallback of the direct solve: read by direct_takes_solve
   // stats
   tsl_step_stats step_stats{};
   ~tsl_ctx() { for (auto* m : mg) delete m; }
@@ -431,4 +418,14 @@ struct Scope {
   ~Scope() {
     if (--c->depth == 0) { (void)hipEventRecord(c->ev_out, c->stream); (void)hipStreamWaitEvent(c->user_stream, c->ev_out, 0); }
   }
+};
+
+// Sets one of the context's two solver switches (ds_suspended, mg_suspended) for the lifetime of the object: every exit path restores it.
+struct Suspend {
+  bool& flag;
+  const bool keep;
+  explicit Suspend(bool& f) : flag(f), keep(f) { flag = true; }
+  ~Suspend() { flag = keep; }
+  Suspend(const Suspend&) = delete;
+  Suspend& operator=(const Suspend&) = delete;
 };

@@ -472,7 +472,7 @@ static int stvk_set(tsl_ctx* c, const char* key, long idx, const std::string& f,
 extern "C" int tsl_set_param(tsl_ctx* c, const char* key, double v) {
   Scope scope(c);
   (void)hipStreamSynchronize(c->stream);
-  c->mg_omega_valid = false; c->mg_cinv_valid = false;
+  c->mg_omega_valid = false;
   c->ds.anorm_valid = false;   // any key may change the scale of the operator (materials, contact stiffness): |H|_inf is formed again when a refinement asks for it
   std::string k(key);
   if (k == "mu_cloth_elastic") c->mu_cloth_elastic = v;
@@ -528,7 +528,7 @@ extern "C" int tsl_set_param(tsl_ctx* c, const char* key, double v) {
     if ((long)c->self_contact.size() < c->n_body) c->self_contact.assign(c->n_body, 0);
     c->self_contact[b] = (v != 0.0);
   }
-  else if (k == "mg_coarse_exact") c->mg_coarse_exact = (int)v;
+  else if (k == "mg_coarse_exact") { c->mg_coarse_exact = (int)v; c->mg_ops_valid = false; }   // (the hierarchy may end at another level)
   else if (k == "mg_dense_nodes") { c->mg_dense_auto = v < 0; if (v >= 0) c->mg_dense_nodes = (int)v; c->mg_ops_valid = false; }
   else if ((k.rfind("cloth", 0) == 0 || k.rfind("elastic", 0) == 0) && k.find('.') != std::string::npos) {
     // "cloth<i>.Kb|Kl|Ka|k_angle|membrane|stvk_mu|stvk_lam", "elastic<i>.mu|lam|alpha" (0-d field writes after the context exists)
@@ -561,7 +561,7 @@ extern "C" int tsl_set_frozen(tsl_ctx* c, const int32_t* fr) {
   Scope scope(c);
   (void)hipStreamSynchronize(c->stream);
   c->h_frozen.assign(fr, fr + 3 * (size_t)c->NV);
-  c->mg_omega_valid = false; c->mg_cinv_valid = false;
+  c->mg_omega_valid = false;
   TSL_TRY(upload_frozen(c));
   if (c->pcg_graph) { (void)hipGraphExecDestroy(c->pcg_graph); c->pcg_graph = nullptr; }
   if (c->mr_graph) { (void)hipGraphExecDestroy(c->mr_graph); c->mr_graph = nullptr; }
@@ -586,7 +586,7 @@ extern "C" int tsl_set_handles(tsl_ctx* c, const int32_t* verts, const double* w
   (void)hipStreamSynchronize(c->stream);
   std::string err;
   if (handle_validate(c->NV, verts, weights, n, err)) return tsl_fail("tsl_set_handles: %s", err.c_str());
-  c->mg_omega_valid = false; c->mg_cinv_valid = false;
+  c->mg_omega_valid = false;
   c->ds.anorm_valid = false;   // (the scale of the operator may change: |H|_inf is formed again when a refinement asks for it)
   c->n_handle = 0;
   if (n == 0) { c->hd_v.release(); c->hd_w.release(); c->hd_t.release(); c->hd_out.release(); return 0; }
@@ -949,7 +949,7 @@ static int assemble(tsl_ctx* c, const double* pos, const double* prev, const dou
 extern "C" int tsl_assemble(tsl_ctx* c, const double* pos, const double* prev, const double* vel, const double* ref, int spd, double* grad) {
   Scope scope(c);
   c->bd_valid = false;
-  c->mg_omega_valid = false; c->mg_cinv_valid = false;
+  c->mg_omega_valid = false;
   // an assembly from outside a step may hold any operator (a new scene state, a new scale): the backward errors of its solves are measured
   // against its own |H|_inf, not one kept from an earlier assembly (the 64-factorisation cache is for the Newton iterations inside tsl_step)
   c->ds.anorm_valid = false;
@@ -1001,11 +1001,7 @@ static int read_scal(tsl_ctx* c) {
   return 0;
 }
 
-static int bicgstab(tsl_ctx* c, tsl_solve_stats* st);
-static int gmres(tsl_ctx* c, tsl_solve_stats* st, bool direct = false);
-static int direct_refine(tsl_ctx* c, tsl_solve_stats* st, bool first_done = false);
-static int solve_perm(tsl_ctx* c, tsl_solve_stats* st, const tsl_solve_stats* first = nullptr);
-// does the next linear solve of this context go straight to the factorisation (solve_perm's rule, the probe of the automatic mode included)?
+// does the next linear solve of this context go straight to the factorisation (solve_direct's rule, the probe of the automatic mode included)?
 static bool direct_takes_solve(tsl_ctx* c) {
   const DirectSolver& d = c->ds;
   return direct_enabled(c) && !c->ds_suspended && !(d.enable < 0 && !d.hard && c->n_tet == 0 && c->nc == 0);
@@ -1018,8 +1014,6 @@ static int block_jacobi_refresh(tsl_ctx* c) {
   return 0;
 }
 static int block_jacobi_ensure(tsl_ctx* c) { return c->dinv_valid ? 0 : block_jacobi_refresh(c); }
-
-static int minres(tsl_ctx* c, tsl_solve_stats* st);
 
 // ------------------------------------------------------------------------------------------------ dense body blocks (k_body.hpp)
 // which elastic bodies get an exact block: at most 512 vertices, at least one free dof
@@ -1112,8 +1106,6 @@ static int mg_build(tsl_ctx* c, const tsl_scene_desc* d) {
       mc->lv.push_back(L);
       if (rc) { delete mc; return -1; }
     }
-    for (size_t l = 0; l + 1 < mc->lv.size(); l++)
-      if (mc->lv[l]->S.alloc((size_t)441 * mc->lv[l + 1]->n)) { delete mc; return -1; }
     c->mg.push_back(mc);
   }
   if (!c->mg.empty()) {
@@ -1123,37 +1115,30 @@ static int mg_build(tsl_ctx* c, const tsl_scene_desc* d) {
 }
 
 static size_t mg_levels(tsl_ctx* c, MgCloth* mc) {
-  size_t nl = std::min<size_t>(mc->lv.size(), (size_t)std::max(1, c->mg_max_levels));
-  if (c->mg_fuse && c->mg_coarse_exact)  // the hierarchy ends at the first level small enough for a dense inverse
+  size_t nl = mc->lv.size();
+  if (c->mg_coarse_exact)  // the hierarchy ends at the first level small enough for a dense inverse
     for (size_t l = 0; l < nl; l++)
       if (mc->lv[l]->n <= std::max(c->mg_dense_nodes, 1)) { nl = l + 1; break; }
   return nl;
 }
-static bool mg_level_dense(tsl_ctx* c, MgLevel* L) { return c->mg_fuse && c->mg_coarse_exact && (L->n <= 64 || L->n <= c->mg_dense_nodes); }
+static bool mg_level_dense(tsl_ctx* c, MgLevel* L) { return c->mg_coarse_exact && (L->n <= 64 || L->n <= c->mg_dense_nodes); }
 static bool mg_active(tsl_ctx* c) { return !c->mg.empty() && c->mg_enable != 0 && !c->mg_suspended; }
 
-// plain y = H x on level 0 (matrix + matrix-free contact), no scalar side effects
+// plain y = H x on level 0 (matrix + matrix-free contact), no scalar side effects.  The smoother products read the single-precision copy of the
+// preconditioner's matrix (half the bytes): mg_setup_operators writes it before anything else, and every caller runs behind a set-up
+// (mg_setup_operators itself, and mg_vcycle, which is only reached with mg_ops_valid).
 static void mg_spmv0(tsl_ctx* c, const double* x, double* y) {
-  hipStream_t s = c->stream;
-  const double* vals = c->pc_separate ? c->vals_pc.p : c->vals.p;
   const double* cH = c->pc_separate ? c->c_H_pc.p : c->c_H.p;
-  if (c->mg_f32 && c->vals32_valid)  // smoother products read the single-precision copy made by mg_setup_operators (half the bytes)
-    hipLaunchKernelGGL((k_spmv_mw<4, 1, TSL_NT, float>), dim3(c->n_slices), dim3(256), 0, s, c->NV, c->n_slices, c->slice_off.p, c->slice_len.p, c->colidx.p, c->vals32.p, x, y,
-                       (double*)nullptr, (const int*)nullptr, contact_rows(c, cH));
-  else
-    hipLaunchKernelGGL((k_spmv_mw<4, 1, TSL_NT>), dim3(c->n_slices), dim3(256), 0, s, c->NV, c->n_slices, c->slice_off.p, c->slice_len.p, c->colidx.p, vals, x, y,
-                       (double*)nullptr, (const int*)nullptr, contact_rows(c, cH));
+  hipLaunchKernelGGL((k_spmv_mw<4, 1, TSL_NT, float>), dim3(c->n_slices), dim3(256), 0, c->stream, c->NV, c->n_slices, c->slice_off.p, c->slice_len.p, c->colidx.p, c->vals32.p, x, y,
+                     (double*)nullptr, (const int*)nullptr, contact_rows(c, cH));
 }
 
 // Galerkin coarse operators of the current (masked) matrix; called once per assembly when the preconditioner is active
 static int mg_setup_operators(tsl_ctx* c) {
   hipStream_t s = c->stream;
-  c->vals32_valid = false;
-  if (c->mg_f32) {  // the matrix in c->vals at this point is the one the preconditioner is built from (also in the separate-pc set-ups)
-    if (c->vals32.n == 0 && c->vals32.alloc(c->vals.n)) return tsl_fail("out of device memory (vals32)");
-    hipLaunchKernelGGL(k_vals_to_f32, dim3(gsz(c->vals.n)), dim3(256), 0, s, c->vals.n, c->vals.p, c->vals32.p);
-    c->vals32_valid = true;
-  }
+  // the matrix in c->vals at this point is the one the preconditioner is built from (also in the separate-pc set-ups)
+  if (c->vals32.n == 0 && c->vals32.alloc(c->vals.n)) return tsl_fail("out of device memory (vals32)");
+  hipLaunchKernelGGL(k_vals_to_f32, dim3(gsz(c->vals.n)), dim3(256), 0, s, c->vals.n, c->vals.p, c->vals32.p);
   for (MgCloth* mc : c->mg) {
     MgGrid gf{mc->N0, mc->M0};
     MgLevel* L1 = mc->lv[0];
@@ -1168,17 +1153,14 @@ static int mg_setup_operators(tsl_ctx* c) {
       HIP_OK(hipMemsetAsync(Lc->A.p, 0, Lc->A.n * sizeof(double), s));
       hipLaunchKernelGGL(k_galerkin_st, dim3(nblk((long)Lf->n * 25, 256)), dim3(256), 0, s, MgGrid{Lf->N, Lf->M}, Lf->A.p, Lc->A.p);
       hipLaunchKernelGGL(k_st_diag_inv, dim3(nblk(Lc->n, 256)), dim3(256), 0, s, Lc->n, Lc->A.p, Lc->Dinv.p);
-      if (c->mg_fuse && c->mg_fuse_restrict) {  // S = P^T A Dinv of the fine level: its first sweep, residual and restriction become one launch
-        if (c->mg_st_f32) {  // both cycle kernels of the level read single-precision copies; S is formed from the ROUNDED A so that the pair stays adjoint up to the rounding of S
-          if (Lf->A32.n == 0 && (Lf->A32.alloc(Lf->A.n) | Lf->S32.alloc(Lf->S.n))) return tsl_fail("out of device memory (stencil f32 copies)");
-          hipLaunchKernelGGL(k_vals_to_f32, dim3(gsz(Lf->A.n)), dim3(256), 0, s, Lf->A.n, Lf->A.p, Lf->A32.p);
-          hipLaunchKernelGGL((k_st_build_ra<float>), dim3(nblk((long)Lc->n * 49, 256)), dim3(256), 0, s, MgGrid{Lf->N, Lf->M}, Lf->A32.p, Lf->Dinv.p, Lf->S32.p);
-        } else
-          hipLaunchKernelGGL((k_st_build_ra<double>), dim3(nblk((long)Lc->n * 49, 256)), dim3(256), 0, s, MgGrid{Lf->N, Lf->M}, Lf->A.p, Lf->Dinv.p, Lf->S.p);
-      }
+      // S = P^T A Dinv of the fine level: its first sweep, residual and restriction are one launch.  Both cycle kernels of the level read
+      // single-precision copies; S is formed from the ROUNDED A so that the pair stays adjoint up to the rounding of S
+      if (Lf->A32.n == 0 && (Lf->A32.alloc(Lf->A.n) | Lf->S32.alloc((size_t)441 * Lc->n))) return tsl_fail("out of device memory (stencil f32 copies)");
+      hipLaunchKernelGGL(k_vals_to_f32, dim3(gsz(Lf->A.n)), dim3(256), 0, s, Lf->A.n, Lf->A.p, Lf->A32.p);
+      hipLaunchKernelGGL(k_st_build_ra, dim3(nblk((long)Lc->n * 49, 256)), dim3(256), 0, s, MgGrid{Lf->N, Lf->M}, Lf->A32.p, Lf->Dinv.p, Lf->S32.p);
     }
     MgLevel* Ll = mc->lv[mg_levels(c, mc) - 1];
-    if (mg_level_dense(c, Ll) && !(c->mg_coarse_lag && c->mg_cinv_valid && Ll->Cinv.n > 0)) {  // dense inverse of the last level
+    if (mg_level_dense(c, Ll)) {  // dense inverse of the last level
       const int n3 = 3 * Ll->n;
       if (Ll->Cinv.n == 0) {
         if (Ll->Cinv.alloc((size_t)n3 * n3) | Ll->cbad.alloc(1)) return tsl_fail("out of device memory (coarse inverse)");
@@ -1225,22 +1207,13 @@ static int mg_setup_operators(tsl_ctx* c) {
       }
     }
   }
-  c->mg_cinv_valid = true;
-  // damping factors
+  // damping factors: omega = 1.5 / lambda_max(D^-1 A) per level, lambda_max from a power iteration
   const double c_om = 1.5, om_max = 0.8;
-  auto set_fixed = [&](double* dst) -> int {
-    const double h[2] = {c->mg_omega, 0.0};
-    HIP_OK(hipMemcpyAsync(dst, h, 2 * sizeof(double), hipMemcpyHostToDevice, s));
-    return 0;
-  };
-  if (c->mg_omega > 0) {
-    TSL_TRY(set_fixed(c->mg_omega0.p));
-    for (MgCloth* mc : c->mg) for (MgLevel* L : mc->lv) TSL_TRY(set_fixed(L->omega.p));
-  } else if (!c->mg_omega_valid) {
+  if (!c->mg_omega_valid) {
     // lambda_max(D^-1 A) moves little over the Newton iterations of one step and omega = 1.5 / lambda_max keeps a 33 % margin:
     // the power iterations (~220 launches) run at the first assembly of a time / adjoint step only, and again after a breakdown
     c->mg_omega_valid = true;
-    const int K = std::min(std::max(c->mg_pi_iters, 2), 60);
+    const int K = 12;
     {  // level 0: v in v_t2, t in v_t3
       const int NV = c->NV, gb = nblk(NV, 256);
       hipLaunchKernelGGL(k_pi_init, dim3(gb), dim3(256), 0, s, NV, c->v_t2.p);
@@ -1268,65 +1241,42 @@ static int mg_setup_operators(tsl_ctx* c) {
   return 0;
 }
 
-// One V-cycle on stencil level l; returns the buffer (L->x or L->x2) holding the result.  Buffer roles are a pure function
-// of (nu, coarse_sweeps), so the launch sequence is identical for every cycle (required for hipGraph replay).
+static constexpr int MG_LAST_SWEEPS = 8;   // damped-Jacobi sweeps on a last level that has no dense inverse
+
+// One V-cycle on stencil level l; returns the buffer (L->x or L->x2) holding the result.  The launch sequence is the same for
+// every cycle (required for hipGraph replay).
 static double* mg_stencil_cycle(tsl_ctx* c, MgCloth* mc, size_t l) {
   hipStream_t s = c->stream;
   MgLevel* L = mc->lv[l];
   const MgGrid g{L->N, L->M};
-  const int gb = nblk(L->n, 256), gb5 = nblk(L->n, 64);
+  const int gb5 = nblk(L->n, 64);
   double* xa = L->x.p;
   double* xb = L->x2.p;
-  auto sweep = [&]() {  // xb = xa + omega Dinv (r - A xa); swap roles
-    hipLaunchKernelGGL((k_st_spmv5<1>), dim3(gb5), dim3(320), 0, s, g, L->A.p, xa, xb, L->Dinv.p, L->r.p, L->omega.p);
-    std::swap(xa, xb);
-  };
-  const bool last = (l + 1 == mg_levels(c, mc));
-  if (c->mg_fuse && last && (L->n <= 64 || mg_level_dense(c, L))) {  // whole coarsest level in one launch
-    if (mg_level_dense(c, L) && L->Cinv.n > 0) hipLaunchKernelGGL(k_st_coarse_apply, dim3(nblk(3 * L->n, 8)), dim3(256), 0, s, 3 * L->n, L->Cinv.p, L->r.p, xa);
-    else hipLaunchKernelGGL(k_st_coarse, dim3(1), dim3(320), 0, s, g, L->A.p, L->Dinv.p, L->r.p, L->omega.p, c->mg_coarse_sweeps, xa);
-    return xa;
-  }
-  const bool fuse_down = c->mg_fuse && !last && c->mg_nu == 1;
-  if (fuse_down && c->mg_fuse_restrict) {  // x = omega Dinv r and the coarse right-hand side in one launch (k_mg.hpp (1b))
+  if (l + 1 < mg_levels(c, mc)) {
+    // x = omega Dinv r and the coarse right-hand side in one launch (k_mg.hpp (1)), the prolongation folded into the post-sweep (2)
     MgLevel* Lc = mc->lv[l + 1];
-    if (c->mg_st_f32 && L->S32.n) {
-      hipLaunchKernelGGL((k_st_first_restrict<32, float>), dim3(nblk(Lc->n, 32)), dim3(7 * 32), 0, s, g, L->S32.p, L->Dinv.p, L->r.p, L->omega.p, xa, Lc->r.p);
-      const double* xc = mg_stencil_cycle(c, mc, l + 1);
-      hipLaunchKernelGGL((k_st_prolong_sweep<float>), dim3(gb5), dim3(320), 0, s, g, L->A32.p, xa, xc, xb, L->Dinv.p, L->r.p, L->omega.p);
-      return xb;
-    }
-    if (c->mg_fr_rows == 16) hipLaunchKernelGGL((k_st_first_restrict<16, double>), dim3(nblk(Lc->n, 16)), dim3(7 * 16), 0, s, g, L->S.p, L->Dinv.p, L->r.p, L->omega.p, xa, Lc->r.p);
-    else if (c->mg_fr_rows == 64) hipLaunchKernelGGL((k_st_first_restrict<64, double>), dim3(nblk(Lc->n, 64)), dim3(7 * 64), 0, s, g, L->S.p, L->Dinv.p, L->r.p, L->omega.p, xa, Lc->r.p);
-    else hipLaunchKernelGGL((k_st_first_restrict<32, double>), dim3(nblk(Lc->n, 32)), dim3(7 * 32), 0, s, g, L->S.p, L->Dinv.p, L->r.p, L->omega.p, xa, Lc->r.p);
+    hipLaunchKernelGGL(k_st_first_restrict, dim3(nblk(Lc->n, ST_FR_ROWS)), dim3(7 * ST_FR_ROWS), 0, s, g, L->S32.p, L->Dinv.p, L->r.p, L->omega.p, xa, Lc->r.p);
     const double* xc = mg_stencil_cycle(c, mc, l + 1);
-    hipLaunchKernelGGL((k_st_prolong_sweep<double>), dim3(gb5), dim3(320), 0, s, g, L->A.p, xa, xc, xb, L->Dinv.p, L->r.p, L->omega.p);
+    hipLaunchKernelGGL(k_st_prolong_sweep, dim3(gb5), dim3(320), 0, s, g, L->A32.p, xa, xc, xb, L->Dinv.p, L->r.p, L->omega.p);
     return xb;
   }
-  if (fuse_down) hipLaunchKernelGGL(k_st_first_resid, dim3(gb5), dim3(320), 0, s, g, L->A.p, L->Dinv.p, L->r.p, L->omega.p, xa, L->t.p);
-  else hipLaunchKernelGGL(k_mg_jacobi_first, dim3(gb), dim3(256), 0, s, L->n, L->Dinv.p, L->r.p, L->omega.p, xa);
-  const int extra = last ? c->mg_coarse_sweeps - 1 : c->mg_nu - 1;
-  for (int k = 0; k < extra; k++) sweep();
-  if (last) return xa;
-  MgLevel* Lc = mc->lv[l + 1];
-  if (!fuse_down)
-    hipLaunchKernelGGL((k_st_spmv5<0>), dim3(gb5), dim3(320), 0, s, g, L->A.p, xa, L->t.p, (const double*)nullptr, (const double*)nullptr, (const double*)nullptr);
-  hipLaunchKernelGGL(k_st_restrict, dim3(nblk(Lc->n, 256)), dim3(256), 0, s, g, L->r.p, L->t.p, Lc->r.p);
-  const double* xc = mg_stencil_cycle(c, mc, l + 1);
-  if (c->mg_fuse) {  // prolongation folded into the first post-sweep
-    hipLaunchKernelGGL((k_st_prolong_sweep<double>), dim3(gb5), dim3(320), 0, s, g, L->A.p, xa, xc, xb, L->Dinv.p, L->r.p, L->omega.p);
+  if (L->n <= 64 || mg_level_dense(c, L)) {  // the whole last level in one launch
+    if (mg_level_dense(c, L) && L->Cinv.n > 0) hipLaunchKernelGGL(k_st_coarse_apply, dim3(nblk(3 * L->n, 8)), dim3(256), 0, s, 3 * L->n, L->Cinv.p, L->r.p, xa);
+    else hipLaunchKernelGGL(k_st_coarse, dim3(1), dim3(320), 0, s, g, L->A.p, L->Dinv.p, L->r.p, L->omega.p, MG_LAST_SWEEPS, xa);
+    return xa;
+  }
+  // a last level too large for either: x = omega Dinv r, then xb = xa + omega Dinv (r - A xa) with the roles swapped after each sweep
+  hipLaunchKernelGGL(k_mg_jacobi_first, dim3(nblk(L->n, 256)), dim3(256), 0, s, L->n, L->Dinv.p, L->r.p, L->omega.p, xa);
+  for (int k = 1; k < MG_LAST_SWEEPS; k++) {
+    hipLaunchKernelGGL((k_st_spmv5<1>), dim3(gb5), dim3(320), 0, s, g, L->A.p, xa, xb, L->Dinv.p, L->r.p, L->omega.p);
     std::swap(xa, xb);
-    for (int k = 1; k < c->mg_nu; k++) sweep();
-  } else {
-    hipLaunchKernelGGL(k_st_prolong_add, dim3(gb), dim3(256), 0, s, g, xc, xa);
-    for (int k = 0; k < c->mg_nu; k++) sweep();
   }
   return xa;
 }
 
-static bool pcg_fold(tsl_ctx* c) { return c->pcg_body_fold && mg_active(c) && body_active(c) && c->bd_valid; }
+static bool pcg_fold(tsl_ctx* c) { return mg_active(c) && body_active(c) && c->bd_valid; }
 
-// z = M^-1 r (one V(nu,nu) cycle); part_rz receives the per-block partials of r.z
+// z = M^-1 r (one V(1,1) cycle); part_rz receives the per-block partials of r.z
 static void mg_vcycle(tsl_ctx* c, const double* r, double* z, double* part_rz, bool first_sweep_done = false, bool body_sweep_done = false) {
   hipStream_t s = c->stream;
   const int NV = c->NV, gb = nblk(NV, 256);
@@ -1335,11 +1285,6 @@ static void mg_vcycle(tsl_ctx* c, const double* r, double* z, double* part_rz, b
   const bool bd = body_active(c) && c->bd_valid;
   if (!first_sweep_done) hipLaunchKernelGGL(k_mg_jacobi_first, dim3(gb), dim3(256), 0, s, NV, c->Dinv.p, r, om, z);
   if (bd && !body_sweep_done) body_apply(c, 0, r, nullptr, z, nullptr, nullptr);
-  for (int k = 0; k < c->mg_nu - 1; k++) {
-    mg_spmv0(c, z, t);
-    hipLaunchKernelGGL(k_mg_jacobi_next, dim3(gb), dim3(256), 0, s, NV, c->Dinv.p, r, t, om, z, (const double*)nullptr, (double*)nullptr);
-    if (bd) body_apply(c, 1, r, t, z, nullptr, nullptr);
-  }
   mg_spmv0(c, z, t);
   for (MgCloth* mc : c->mg) {
     MgLevel* L1 = mc->lv[0];
@@ -1347,17 +1292,9 @@ static void mg_vcycle(tsl_ctx* c, const double* r, double* z, double* part_rz, b
     const double* x1 = mg_stencil_cycle(c, mc, 0);
     hipLaunchKernelGGL(k_mg_prolong0_add, dim3(nblk((mc->N0 + 1) * (mc->M0 + 1), 256)), dim3(256), 0, s, MgGrid{mc->N0, mc->M0}, mc->v_offset, c->rowpos.p, x1, z);
   }
-  for (int k = 0; k < c->mg_nu; k++) {
-    mg_spmv0(c, z, t);
-    const bool lastk = (k == c->mg_nu - 1);
-    if (bd && c->mg_fuse)
-      hipLaunchKernelGGL(k_post_smooth, dim3(gb + c->bd_wg), dim3(256), 0, s, c->bd_args, c->bd_Binv.p, gb, NV, c->Dinv.p, r, t, om, z, lastk ? r : (const double*)nullptr,
-                         lastk ? part_rz : (double*)nullptr);
-    else {
-      hipLaunchKernelGGL(k_mg_jacobi_next, dim3(gb), dim3(256), 0, s, NV, c->Dinv.p, r, t, om, z, lastk ? r : (const double*)nullptr, lastk ? part_rz : (double*)nullptr);
-      if (bd) body_apply(c, 1, r, t, z, lastk ? r : (const double*)nullptr, lastk ? part_rz + gb : (double*)nullptr);
-    }
-  }
+  mg_spmv0(c, z, t);
+  if (bd) hipLaunchKernelGGL(k_post_smooth, dim3(gb + c->bd_wg), dim3(256), 0, s, c->bd_args, c->bd_Binv.p, gb, NV, c->Dinv.p, r, t, om, z, r, part_rz);
+  else hipLaunchKernelGGL(k_mg_jacobi_next, dim3(gb), dim3(256), 0, s, NV, c->Dinv.p, r, t, om, z, r, part_rz);
 }
 
 
@@ -1388,11 +1325,19 @@ static void launch_pcg_iteration(tsl_ctx* c, int parity, int first, unsigned lon
   else if (body_active(c) && c->bd_valid) body_apply(c, 0, c->v_r.p, nullptr, c->v_z.p, c->v_r.p, c->part_rz.p + nblk(NV, 256));
 }
 
+// Key of the captured launch sequences (PCG chunk, MINRES period): whatever changes a captured launch or a captured pointer.  mg_coarse_exact and
+// mg_dense_nodes decide where the hierarchy ends and how its last level is solved, pc_separate which contact blocks the smoother reads, nc the
+// contact launches, the dense body inverse and the profile further launches / arguments.
+static long solver_graph_key(tsl_ctx* c) {
+  const long flags = (mg_active(c) ? 1 : 0) | (c->prof_enable ? 2 : 0) | (c->pc_separate ? 4 : 0) | ((body_active(c) && c->bd_valid) ? 8 : 0) | (c->mg_coarse_exact ? 16 : 0);
+  return flags | ((long)(c->mg_dense_nodes & 0xfffff) << 5) | ((long)c->nc << 25);
+}
+
 // Chunk of `chunk` (even) iterations with parities 1,0,1,0,... captured once as a hipGraph and replayed: a multigrid-PCG
 // iteration is ~20 short kernels.  The first K1 of the chunk stamps
 // the device clock into a fixed buffer when profiling is on.
 static int pcg_chunk_graph(tsl_ctx* c, int chunk) {
-  const long key = ((long)(mg_active(c) ? 1 : 0) << 40) | ((long)c->nc << 8) | ((long)(c->prof_enable ? 1 : 0) << 7) | (long)chunk | ((long)c->mg_nu << 44) | ((long)c->mg_coarse_sweeps << 48) | ((long)(c->pc_separate ? 1 : 0) << 41) | ((long)((body_active(c) && c->bd_valid) ? 1 : 0) << 42) | ((long)(c->mg_fuse ? 1 : 0) << 43) | ((long)(c->mg_fuse_restrict ? 1 : 0) << 36) | ((long)(c->pcg_body_fold ? 1 : 0) << 37) | ((long)(c->mg_st_f32 ? 1 : 0) << 22) | ((long)c->mg_max_levels << 52) | ((long)(c->mg_coarse_exact ? 1 : 0) << 39) | ((long)((c->mg_f32 && c->vals32_valid) ? 1 : 0) << 38) | ((long)(c->mg_dense_nodes & 0xfff) << 24);
+  const long key = (solver_graph_key(c) << 6) | (long)chunk;   // chunk <= 32
   if (c->pcg_graph && c->pcg_graph_key == key) return 0;
   if (c->pcg_graph) { (void)hipGraphExecDestroy(c->pcg_graph); c->pcg_graph = nullptr; }
   hipGraph_t g = nullptr;
@@ -1432,7 +1377,7 @@ static int forward_spd_pc(tsl_ctx* c) {
   std::swap(c->vals.p, c->vals_pc.p);
   if (c->nc > 0) std::swap(c->c_H.p, c->c_H_pc.p);
   const int rc = assemble(c, c->st_pos, c->st_prev, c->st_vel, c->st_ref, 2, nullptr);
-  c->mg_omega_valid = false; c->mg_cinv_valid = false;  // damping factors and dense body blocks of THIS matrix (the lagged ones may be indefinite)
+  c->mg_omega_valid = false;  // damping factors and dense body blocks of THIS matrix (the lagged ones may be indefinite)
   c->bd_valid = false;
   int rc2 = 0;
   if (!rc) {
@@ -1461,282 +1406,6 @@ static int ds_flow_lost(tsl_ctx* c, bool suspect, int note[8]) {
   for (int k = 0; k < 8; k++) note[k] = 0;
   (void)hipMemcpy(note, d.bad.p + DS_BAD_NOTE, 8 * sizeof(int), hipMemcpyDeviceToHost);
   return 1;
-}
-
-// Solve with rhs already in v_b (permuted); result in v_x (permuted).  first (scene group): the first pass of the factorised solve is in place
-// and was not accepted (ir_pass_verdict); its statistics -- the solve goes on from the second pass, as direct_refine would after its own first pass.
-static int solve_perm(tsl_ctx* c, tsl_solve_stats* st, const tsl_solve_stats* first) {
-  hipStream_t s = c->stream;
-  const int NV = c->NV;
-  const size_t n3 = 3 * (size_t)NV;
-  const int gb = nblk(NV, 256);
-  st->iters = 0; st->restarts = 0; st->flag = 0; st->rel_residual = 0; st->method = 0; st->attained = 0; st->backward_error = 0;
-  c->last_xmax_valid = false;
-  if (direct_enabled(c) && !c->ds_suspended) {
-    // primary path on refined cloths: multifrontal LU of the operator (like the reference's spsolve) + GMRES refinement
-    // against the operator product; the iterative hierarchy below only runs if that fails.
-    DirectSolver& d = c->ds;
-    // "direct" = -1 (auto): easy systems stay with the iterative hierarchy -- the contact-free 224 x 224 drape needs 26 multigrid-PCG
-    // iterations per solve (46 ms per step) against one 6 ms factorisation per solve (86 ms per step).  A solve first probes the
-    // hierarchy with a cap of `probe_cap` iterations (the cost of one factorisation); the first failure marks the scene hard and
-    // the following `probe_every` time steps go straight to the factorisation.
-    // Scenes with FEM bodies or active contacts skip the probe (round 4): it never succeeded on them (cfg3 / cfg4: 60 wasted iterations every
-    // 16 steps), and the hierarchy's f64-atomic reductions are the one part of the step that is not bit-reproducible.
-    if (!first && d.enable < 0 && !d.hard && c->n_tet == 0 && c->nc == 0) {
-      c->ds_suspended = true; c->ds_probe = true;
-      const int maxit_keep = c->cg_maxit;
-      c->cg_maxit = std::min(c->cg_maxit, d.probe_cap);
-      tsl_solve_stats s2;
-      const int rc = solve_perm(c, &s2);
-      c->cg_maxit = maxit_keep;
-      c->ds_suspended = false; c->ds_probe = false;
-      if (rc) return rc;
-      if (s2.flag == 0) { *st = s2; return 0; }
-      d.hard = true; d.hard_steps = 0;
-      st->iters = s2.iters;   // counted with the solve that follows
-    }
-    tsl_solve_stats sd = first ? *first : *st;
-    // Set-up failures of the direct path (arena or GMRES-basis allocation, an inconsistent plan): with "direct" = 1 they are errors;
-    // in the automatic mode the solve falls through to the iterative hierarchy, which needs none of that memory, and after three
-    // such failures the context stops trying ("direct" = 0).
-    auto direct_try = [&]() -> int {
-      if (!d.numeric_valid) {
-        TSL_TRY(direct_plan(c));
-        TSL_TRY(direct_factor(c, -1, nullptr, c->v_b.p, c->v_x.p));   // (the first pass of direct_refine applies the factors to v_b -> v_x)
-      }
-      // plain refinement first; systems it does not settle go through the flexible GMRES from scratch
-      int rc_g = direct_refine(c, &sd, first != nullptr);
-      if (rc_g == 0 && sd.flag != 1) { const int it0 = sd.iters; sd = *st; c->last_xmax_valid = false; rc_g = gmres(c, &sd, true); sd.iters += it0; }
-      if (rc_g) return -1;
-      int note[8];
-      const int lost = ds_flow_lost(c, sd.flag != 1, note);
-      if (lost < 0) return -1;
-      if (lost) {   // a dataflow launch that lost a flag leaves garbage factors: say so, go back to the launch-per-block-step path
-        // The first loss of a context that runs the look-ahead takes the LOOK-AHEAD away (the one known cause inside a process is side-stream work arriving while a launch is
-        // still being dispatched) and keeps the dataflow path; a loss without it -- or a second one -- takes the dataflow path.  Either way this system is
-        // refactorised on the launch-per-block-step path.
-        const bool blame_la = (d.lookahead & 1) != 0 && d.n_flow_abort == 0 && d.dbg != 21;
-        fprintf(stderr, "[tsl] k_ds_gj_flow: a workgroup waited in vain for a flag (launch not resident as a whole?): %s disabled for this context, refactorising "
-                "(workgroup %d of %d gave up; %d of the %d workgroups of the factorisation's dataflow launches had started; flag value %d, epoch %d)\n",
-                blame_la ? "\"direct_lookahead\"" : "\"direct_flow\"", note[2], note[1], note[0], d.flow_wgs_last, note[3], note[4]);
-        const int flow_keep = d.flow;
-        d.flow = 0; d.n_flow_abort++;
-        if (blame_la) d.lookahead = 0;
-        d.numeric_valid = false; d.have_factor = false;   // the factors in place are garbage: direct_factor must not return early
-        if (d.prezero_pending) { HIP_OK(hipStreamWaitEvent(c->stream, d.ev_zero, 0)); d.prezero_pending = false; }
-        TSL_TRY(direct_factor(c));
-        if (blame_la) d.flow = flow_keep;
-        sd = *st; c->last_xmax_valid = false;
-        TSL_TRY(direct_refine(c, &sd));
-        if (sd.flag != 1) { const int it0 = sd.iters; sd = *st; c->last_xmax_valid = false; TSL_TRY(gmres(c, &sd, true)); sd.iters += it0; }
-      }
-      return 0;
-    };
-    if (direct_try() != 0) {
-      if (d.enable == 1) return -1;
-      (void)hipGetLastError();   // an out-of-memory allocation leaves a sticky-looking but recoverable error code
-      d.numeric_valid = false; d.have_factor = false; d.plan_valid = false;
-      fprintf(stderr, "[tsl] direct solver set-up failed (%s): this solve runs on the iterative hierarchy%s\n", tsl_last_error(),
-              ++d.n_setup_fail >= 3 ? "; direct path disabled for this context" : "");
-      if (d.n_setup_fail >= 3) d.enable = 0;
-      c->ds_suspended = true;
-      const int rc = solve_perm(c, st);
-      c->ds_suspended = false;
-      if (rc == 0 && st->flag == 0) st->flag = 1;   // reported as a fallback
-      return rc;
-    }
-    if (sd.flag == 1) { *st = sd; st->flag = 0; st->method = 4; return 0; }
-    if (c->verbose) {
-      int nb[4] = {0, 0, 0, 0};
-      (void)hipMemcpy(nb, d.bad.p, sizeof(nb), hipMemcpyDeviceToHost);
-      fprintf(stderr, "[tsl] direct factorisation + GMRES did not converge (rel_residual %.2e, backward error %.2e after %d iterations, perturbed pivots %d / %d / %d in fronts of <= 128 / <= 512 / more pivots, nc %d): iterative fallback\n",
-              sd.rel_residual, sd.backward_error, sd.iters, nb[1], nb[2], nb[3], c->nc);
-      if (c->verbose > 1) {
-        std::vector<int> lg(DS_BAD_NOTE);
-        (void)hipMemcpy(lg.data(), d.bad.p, lg.size() * sizeof(int), hipMemcpyDeviceToHost);
-        const int nl = std::min(lg[4], DS_BADLOG);
-        static int n_dump = 0;
-        if (const char* dir = getenv("TSL_DUMP_DIR")) if (nl > 0 && n_dump < 3) {
-          char path[512];
-          snprintf(path, sizeof(path), "%s/front_%d.bin", dir, n_dump++);
-          d.numeric_valid = false;
-          TSL_TRY(direct_factor(c, lg[8] >> 6, path));
-        }
-        for (int i = 0; i < nl; i++) {
-          const int* L = &lg[8 + 4 * i];
-          const int sn = L[0] >> 6, kt = L[0] & 63;
-          const DsFrontDesc& f = d.plan.fr[sn];
-          float am; memcpy(&am, L + 3, 4);
-          const unsigned mask = (unsigned)L[1];
-          const int first = __builtin_ctz(mask | 0x80000000u), row = kt * DS_T + first;
-          const int vtx = row < f.p ? d.plan.vtx[f.vtx_off + row / 3] : -1;
-          fprintf(stderr, "[tsl]   perturbed pivots: front %d (level %d, p %d, b %d, own verts %d) tile %d rows mask %08x, first row %d (vertex %d dof %d%s), tile max %.3e\n",
-                  sn, d.plan.sym.level[sn], f.p, f.b, f.nv_own, kt, mask, row, vtx, row % 3, vtx >= 0 && d.plan.sym.body_of[vtx] >= 0 ? ", body" : "", am);
-        }
-      }
-    }
-    // Where the refined factorisation stalls, the iterative hierarchy does not do better (it needs 1e4..1e5 iterations on the
-    // systems the factorisation is for, and the stalls seen are operators with entries of 1e15 beside 1e3 -- an element of a pad
-    // crushed flat late in a rollout): an answer within 1e-3 is returned as it is, flagged not converged; only a broken
-    // factorisation (residual above that) is worth a bounded attempt of the hierarchy.
-    if (sd.rel_residual <= 1e-3) { *st = sd; st->flag = 3; st->method = 4; return 0; }
-    c->ds_suspended = true;
-    tsl_solve_stats s2;
-    const int maxit_keep = c->cg_maxit;
-    c->cg_maxit = std::min(c->cg_maxit, d.fallback_cap);
-    HIP_OK(hipMemcpyAsync(c->v_t4.p, c->v_x.p, 3 * (size_t)c->NV * sizeof(double), hipMemcpyDeviceToDevice, c->stream));  // the refined direct solution
-    const int rc = solve_perm(c, &s2);
-    c->cg_maxit = maxit_keep;
-    c->ds_suspended = false;
-    // keep the better of the two answers, flagged as not converged.  A non-finite residual never wins: a factorisation that produced
-    // Inf / NaN (element entries of 1e15 on a crushed pad) must not overwrite a finite iterate, and two non-finite answers are an error.
-    const bool sd_ok = std::isfinite(sd.rel_residual), s2_ok = rc == 0 && std::isfinite(s2.rel_residual);
-    if (rc == 0 && s2.flag == 3 && !sd_ok && !s2_ok) return tsl_fail("linear solve: factorisation and iterative fallback both ended with a non-finite residual");
-    if (rc == 0 && s2.flag == 3 && sd_ok && (!s2_ok || !(s2.rel_residual < sd.rel_residual))) {
-      HIP_OK(hipMemcpyAsync(c->v_x.p, c->v_t4.p, 3 * (size_t)c->NV * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-      *st = sd; st->iters = sd.iters + s2.iters; st->flag = 3; st->method = 4;
-      return 0;
-    }
-    st->iters = sd.iters + s2.iters; st->restarts = s2.restarts + 1; st->rel_residual = s2.rel_residual; st->method = s2.method; st->attained = s2.attained;
-    st->flag = s2.flag == 0 ? 1 : s2.flag;
-    return rc;
-  }
-  TSL_TRY(block_jacobi_ensure(c));   // (skipped by an assembly that expected the factorisation to take this solve)
-  const bool warm = false;   // (a warm start from the previous Newton direction was measured: -4 % iterations on one cfg4 window, none on another, +2 % time on drape; gone)
-  if (!warm) HIP_OK(hipMemsetAsync(c->v_x.p, 0, n3 * sizeof(double), s));
-  HIP_OK(hipMemsetAsync(c->scal.p, 0, sizeof(SolverScalars), s));
-  hipLaunchKernelGGL(k_dot, dim3(DOT_BLOCKS), dim3(256), 0, s, n3, c->v_b.p, c->v_b.p, &SC(c)->bb, DOT_SCRATCH(c));
-  TSL_TRY(read_scal(c));
-  const double bb = HSC(c)->bb;
-  if (!(bb > 0)) return 0;  // zero rhs -> x = 0
-  const double tol2 = c->cg_tol * c->cg_tol * bb;
-  bool need_fallback = false, indefinite = false;
-  int total_it = 0;
-  const int ncb = c->nc > 0 ? nblk(c->nc, 64) : 0;
-  if (body_active(c) && !c->bd_valid) TSL_TRY(body_build_inverse(c));
-  const bool bd = body_active(c) && c->bd_valid;
-  const int n_rz = gb + (bd ? c->bd_wg : 0);
-  double rr_prev_outer = 1e300;
-  for (int outer = 0; outer < 20; outer++) {
-    PcgScal hs;
-    memset(&hs, 0, sizeof(hs));
-    hs.bb = bb; hs.thresh2 = 0.25 * tol2; hs.n_part1 = c->n_slices; hs.n_part2 = n_rz;
-    HIP_OK(hipMemcpyAsync(c->scal.p, &hs, sizeof(PcgScal), hipMemcpyHostToDevice, s));
-    if (outer > 0 || warm) launch_spmv(c, c->vals.p, c->v_x.p, c->v_Ap.p, -1, 0);
-    // true residual, z = M^-1 r, partial r.z / r.r
-    hipLaunchKernelGGL(k_pcg_update, dim3(gb + (pcg_fold(c) ? c->bd_wg : 0)), dim3(256), 0, s, NV, (const double*)nullptr, (const double*)nullptr, c->Dinv.p, c->v_x.p, c->v_r.p,
-                       c->v_z.p, c->part_pAp.p, c->part_rz.p, c->part_rr.p, PSC(c), 0, c->v_b.p, (outer > 0 || warm) ? c->v_Ap.p : (const double*)nullptr, mg_active(c) ? 0 : 1,
-                       (const double*)nullptr, gb, c->bd_args, c->bd_Binv.p, pcg_fold(c) ? c->bd_rb.p : (double*)nullptr, c->bd_scr_n);
-    hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(256), 0, s, c->part_rr.p, gb, &PSC(c)->rr_last);
-    if (outer > 0) {  // verification of a converged recurrence: the true residual decides before a V-cycle is spent on it
-      TSL_TRY(read_scal(c));
-      const double rr1 = HPSC(c)->rr_last;
-      st->rel_residual = sqrt(rr1 / bb);
-      if (rr1 <= tol2) { need_fallback = false; break; }
-      // attainable accuracy: when a restart no longer halves the true residual the solve has reached what fp64 allows for
-      // this conditioning (a direct solver has the same backward error); accept if within 1e2 of the requested tolerance (reported: attained)
-      if (rr1 > 0.25 * rr_prev_outer && rr1 <= 1e4 * tol2) { need_fallback = false; st->attained = 1; break; }
-    }
-    if (mg_active(c)) {
-      if (!c->mg_ops_valid) TSL_TRY(mg_setup_operators(c));
-      mg_vcycle(c, c->v_r.p, c->v_z.p, c->part_rz.p);
-    } else if (bd) body_apply(c, 0, c->v_r.p, nullptr, c->v_z.p, c->v_r.p, c->part_rz.p + gb);
-    hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(256), 0, s, c->part_rz.p, n_rz, &PSC(c)->rz_last);
-    TSL_TRY(read_scal(c));
-    const double rr0 = HPSC(c)->rr_last;
-    st->rel_residual = sqrt(rr0 / bb);
-    if (rr0 <= tol2) { need_fallback = false; break; }
-    rr_prev_outer = rr0;
-    if (!(HPSC(c)->rz_last > 0)) { need_fallback = true; break; }
-    if (outer > 0) st->restarts++;
-    need_fallback = true;
-    int flag = 0, it = 0;
-    const auto tm0 = std::chrono::steady_clock::now();
-    // iteration 0 (beta = 0) eagerly, then graph replays of `chunk` iterations (parities 1,0,...)
-    launch_pcg_iteration(c, 0, 1, nullptr);
-    it++; total_it++; c->prof_launches++;
-    // iterations per graph replay / host convergence read: eight on long solves (the previous time step needed more than 150 per
-    // solve: cfg4 1.56 -> 1.53 s per step), four otherwise (the idle launches after convergence cost drape 4 % with eight)
-    const int mgc = c->mg_chunk > 0 ? c->mg_chunk : (c->last_step_iters_per_solve > 150.0 ? 8 : 4);
-    int chunk = mg_active(c) ? std::min(c->cg_check, mgc) : c->cg_check;
-    chunk = std::max(2, chunk & ~1);
-    const bool graph = c->use_graph != 0;
-    if (graph) TSL_TRY(pcg_chunk_graph(c, chunk));
-    int n_chunks = 0;
-    // (a second chunk kept in flight behind the one whose convergence record the host waits for was measured and dropped: the time per iteration
-    // does not change -- the gaps are between dependent kernels inside the graph, not host round trips -- and the idle chunk cost ~0.2 ms per solve.)
-    // A chunk whose device-clock stamps are sampled for the profile gets no successor until read.
-    int inflight = 0, head = 0;
-    bool sampled[2] = {false, false};
-    auto launch_chunk = [&]() -> int {
-      const int sl = (head + inflight) & 1;
-      // every 32nd chunk of a profiled run is launched kernel by kernel so that one K1 can be timed with hipEvents
-      const bool ev_chunk = graph && c->prof_enable && (c->prof_chunks++ % 32 == 16);
-      if (graph && !ev_chunk) HIP_OK(hipGraphLaunch(c->pcg_graph, s));
-      else {
-        c->ev_sample_next = ev_chunk;
-        for (int i = 0; i < chunk; i++) launch_pcg_iteration(c, (i & 1) ^ 1, 0, nullptr);
-        hipLaunchKernelGGL(k_pcg_check, dim3(1), dim3(256), 0, s, c->part_rr.p, PSC(c));
-      }
-      HIP_OK(hipMemcpyAsync(&c->h_scal2[sl], c->scal.p, sizeof(CgScal), hipMemcpyDeviceToHost, s));
-      HIP_OK(hipEventRecord(c->rb_event[sl], s));
-      sampled[sl] = graph && !ev_chunk && c->prof_enable && (n_chunks++ % 8 == 0);
-      inflight++; it += chunk; total_it += chunk; c->prof_launches += chunk;
-      return 0;
-    };
-    while (true) {
-      while (inflight < 1 && total_it < c->cg_maxit && !(inflight == 1 && sampled[head])) TSL_TRY(launch_chunk());
-      if (inflight == 0) break;  // iteration cap
-      HIP_OK(hipEventSynchronize(c->rb_event[head]));
-      if (sampled[head]) TSL_TRY(prof_sample_graph(c));
-      memcpy(c->h_scal, &c->h_scal2[head], sizeof(CgScal));
-      inflight--; head ^= 1;
-      flag = HPSC(c)->flag;
-      if (flag) break;
-    }
-    if (inflight) HIP_OK(hipStreamSynchronize(s));
-    if (c->prof_enable) prof_collect(c);
-    c->tm_loop += std::chrono::duration<double>(std::chrono::steady_clock::now() - tm0).count();
-    if (flag) total_it = total_it - it + HPSC(c)->iters;  // iterations actually executed before the kernels went idle
-    if (flag == 1) { indefinite = true; c->mg_omega_valid = false; c->mg_cinv_valid = false; }
-    if (flag != 2) break;  // breakdown or iteration cap
-  }
-  st->iters = total_it;
-  if (!need_fallback) { st->flag = 0; c->warm_valid = c->in_step; return 0; }
-  c->warm_valid = false;
-  if (c->ds_probe) { st->flag = 3; return 0; }   // probe of the iterative hierarchy failed: the caller factorises
-  if (mg_active(c) && !indefinite) {
-    // multigrid-PCG stalled: retry with plain block-Jacobi PCG (an indefinite H goes straight to BiCGStab)
-    c->mg_suspended = true;
-    tsl_solve_stats st2;
-    const int rc = solve_perm(c, &st2);
-    c->mg_suspended = false;
-    st->iters += st2.iters; st->restarts += st2.restarts + 1; st->flag = st2.flag == 0 ? 1 : st2.flag; st->rel_residual = st2.rel_residual; st->method = st2.method; st->attained = st2.attained;
-    return rc;
-  }
-  if (c->verbose) fprintf(stderr, "[tsl] PCG gave up: iters %d restarts %d rel_residual %.2e indefinite %d\n", st->iters, st->restarts, st->rel_residual, (int)indefinite);
-  if (indefinite && c->use_minres && c->fwd_spd_pc) {
-    const int rcp = forward_spd_pc(c);
-    if (rcp < 0) return -1;
-    if (c->verbose && rcp == 0) fprintf(stderr, "[tsl] forward system indefinite: preconditioner rebuilt from the fully projected assembly\n");
-  }
-  if (c->use_minres) {  // symmetric indefinite: short recurrences
-    tsl_solve_stats st2 = *st;
-    TSL_TRY(minres(c, &st2));
-    if (c->verbose) fprintf(stderr, "[tsl] MINRES: flag %d iters %d restarts %d rel_residual %.2e\n", st2.flag, st2.iters - st->iters, st2.restarts, st2.rel_residual);
-    st->iters = st2.iters; st->restarts = st2.restarts; st->rel_residual = st2.rel_residual; st->attained = st2.attained;
-    if (st2.flag == 1) { st->flag = 1; st->method = 1; return 0; }
-  }
-  if (c->use_gmres) {
-    const int it0 = st->iters;
-    TSL_TRY(gmres(c, st));
-    if (c->verbose) fprintf(stderr, "[tsl] GMRES: flag %d iters %d rel_residual %.2e\n", st->flag, st->iters - it0, st->rel_residual);
-    if (st->flag == 1) { st->method = 2; return 0; }
-    st->method = 3;
-    return bicgstab(c, st);  // last resort
-  }
-  st->method = 3;
-  return bicgstab(c, st);
 }
 
 // Preconditioned MINRES for symmetric indefinite H with an SPD preconditioner (adjoint systems: un-projected H, preconditioner
@@ -1775,11 +1444,6 @@ static void launch_minres_iteration(tsl_ctx* c, const MrBufs& B, int j) {
   hipLaunchKernelGGL(k_mr_seal, dim3(1), dim3(1), 0, s, sc);
 }
 
-static long solver_graph_key(tsl_ctx* c) {
-  return ((long)(mg_active(c) ? 1 : 0) << 40) | ((long)c->nc << 8) | ((long)(c->prof_enable ? 1 : 0) << 7) | ((long)c->mg_nu << 44) | ((long)c->mg_coarse_sweeps << 48) |
-         ((long)(c->pc_separate ? 1 : 0) << 41) | ((long)((body_active(c) && c->bd_valid) ? 1 : 0) << 42) | ((long)(c->mg_fuse ? 1 : 0) << 43) | ((long)(c->mg_fuse_restrict ? 1 : 0) << 36) | ((long)(c->pcg_body_fold ? 1 : 0) << 37) | ((long)(c->mg_st_f32 ? 1 : 0) << 22) | ((long)c->mg_max_levels << 52) | ((long)(c->mg_coarse_exact ? 1 : 0) << 39) | ((long)((c->mg_f32 && c->vals32_valid) ? 1 : 0) << 38) | ((long)(c->mg_dense_nodes & 0xfff) << 24);
-}
-
 static int minres_graph(tsl_ctx* c, const MrBufs& B) {
   const long key = solver_graph_key(c);
   if (c->mr_graph && c->mr_graph_key == key) return 0;
@@ -1794,7 +1458,7 @@ static int minres_graph(tsl_ctx* c, const MrBufs& B) {
   return 0;
 }
 
-static int minres(tsl_ctx* c, tsl_solve_stats* st) {
+static int minres(tsl_ctx* c, tsl_solve_stats* st, int cap) {
   hipStream_t s = c->stream;
   const int NV = c->NV;
   const size_t n3 = 3 * (size_t)NV;
@@ -1834,10 +1498,9 @@ static int minres(tsl_ctx* c, tsl_solve_stats* st) {
   const double tol = c->cg_tol * sqrt(bb);
   HIP_OK(hipMemsetAsync(x, 0, n3 * sizeof(double), s));
   HIP_OK(hipMemcpyAsync(B.V[1], c->v_b.p, n3 * sizeof(double), hipMemcpyDeviceToDevice, s));
-  const bool graph = c->use_graph != 0;
   double true_prev = 1e300;
   int total = 0;
-  for (int cycle = 0; cycle < 40 && total < c->cg_maxit; cycle++) {
+  for (int cycle = 0; cycle < 40 && total < cap; cycle++) {
     // (re)start from the true residual held in V[1]
     double rr, g2;
     precond(B.V[1], B.Z[0]);
@@ -1853,17 +1516,16 @@ static int minres(tsl_ctx* c, tsl_solve_stats* st) {
     MrScal hs;
     memset(&hs, 0, sizeof(hs));
     hs.gamma = sqrt(g2); hs.gamma_prev = 1.0; hs.eta = hs.gamma; hs.c_prev = 1.0; hs.c_cur = 1.0;
-    hs.thresh_eta = c->mr_eta * (tol / rnorm0) * hs.gamma;  // |eta| is the residual in the M^-1 norm, scaled by the start of the cycle
+    hs.thresh_eta = 0.3 * (tol / rnorm0) * hs.gamma;  // the recurrence cycle stops at |eta| <= 0.3 tol: |eta| is the residual in the M^-1 norm, scaled by the start of the cycle; the true residual decides afterwards
     HIP_OK(hipMemcpyAsync(d, &hs, sizeof(MrScal), hipMemcpyHostToDevice, s));
     HIP_OK(hipMemsetAsync(B.V[0], 0, n3 * sizeof(double), s));
     HIP_OK(hipMemsetAsync(B.W[0], 0, n3 * sizeof(double), s));
     HIP_OK(hipMemsetAsync(B.W[1], 0, n3 * sizeof(double), s));
-    if (graph) TSL_TRY(minres_graph(c, B));
+    TSL_TRY(minres_graph(c, B));
     int flag = 0;
     const int base = total;
-    while (total < c->cg_maxit) {
-      if (graph) HIP_OK(hipGraphLaunch(c->mr_graph, s));
-      else for (int j = 0; j < 6; j++) launch_minres_iteration(c, B, j);
+    while (total < cap) {
+      HIP_OK(hipGraphLaunch(c->mr_graph, s));
       HIP_OK(hipMemcpyAsync(h, d, sizeof(MrScal), hipMemcpyDeviceToHost, s));
       HIP_OK(hipStreamSynchronize(s));
       flag = h->flag;
@@ -1893,7 +1555,7 @@ static int minres(tsl_ctx* c, tsl_solve_stats* st) {
 // minimal residual over the Krylov space, so it cannot diverge the way BiCGStab does on strongly indefinite matrices.
 // Preconditioner: multigrid V-cycle (+ dense body blocks) when available, else block Jacobi.  Classical Gram-Schmidt applied
 // twice with the coefficients kept on the device; one host read (h, h2, |w|^2) per iteration for the Givens rotations.
-static int gmres(tsl_ctx* c, tsl_solve_stats* st, bool direct) {
+static int gmres(tsl_ctx* c, tsl_solve_stats* st, int cap, bool direct = false) {
   hipStream_t s = c->stream;
   const int NV = c->NV;
   const size_t n3 = 3 * (size_t)NV;
@@ -1946,7 +1608,7 @@ static int gmres(tsl_ctx* c, tsl_solve_stats* st, bool direct) {
   std::vector<double> H((size_t)(m + 1) * m), cs(m), sn(m), g(m + 1), y(m);
   int total = 0;
   double beta_prev = 1e300;
-  for (int cycle = 0; cycle < 1000 && total < c->cg_maxit; cycle++) {
+  for (int cycle = 0; cycle < 1000 && total < cap; cycle++) {
     hipLaunchKernelGGL(k_axpby, dim3(gv), dim3(256), 0, s, n3, 1.0 / beta, r, 0.0, V);
     std::fill(g.begin(), g.end(), 0.0);
     g[0] = beta;
@@ -2098,7 +1760,7 @@ static int ir_pass_verdict(tsl_ctx* c, tsl_solve_stats* st, bool first) {
 // |b - Hx| <= cg_tol |b|, or -- when a step no longer halves the residual -- a normwise backward error below 1e-12 ("attained").
 // first_done: the first pass is in place and judged already, its norms in h_ir and its counts in st (scene group: the merged application
 // of the factors of every member, group_solve); the refinement goes on from the second pass.
-static int direct_refine(tsl_ctx* c, tsl_solve_stats* st, bool first_done) {
+static int direct_refine(tsl_ctx* c, tsl_solve_stats* st, bool first_done = false) {
   hipStream_t s = c->stream;
   const size_t n3 = 3 * (size_t)c->NV;
   double *x = c->v_x.p, *r = c->v_r.p, *z = c->v_z.p;
@@ -2130,7 +1792,7 @@ static int direct_refine(tsl_ctx* c, tsl_solve_stats* st, bool first_done) {
 }
 
 // Block-Jacobi BiCGStab on H (used when PCG breaks down: un-projected adjoint Hessians can be indefinite)
-static int bicgstab(tsl_ctx* c, tsl_solve_stats* st) {
+static int bicgstab(tsl_ctx* c, tsl_solve_stats* st, int cap) {
   hipStream_t s = c->stream;
   const int NV = c->NV;
   const size_t n3 = 3 * (size_t)NV;
@@ -2177,7 +1839,7 @@ static int bicgstab(tsl_ctx* c, tsl_solve_stats* st) {
     st->restarts++;
     return 0;
   };
-  for (int it = 0; it < c->cg_maxit; it++) {
+  for (int it = 0; it < cap; it++) {
     double rho_new;
     TSL_TRY(dots(r0, r, nullptr, nullptr, &rho_new, nullptr));
     if (fabs(rho_new) < 1e-300 || omega == 0 || !std::isfinite(rho_new)) {
@@ -2226,6 +1888,299 @@ static int bicgstab(tsl_ctx* c, tsl_solve_stats* st) {
     }
   }
   return 0;
+}
+
+// ------------------------------------------------------------------------------------------------ linear solve
+// Right-hand side in v_b (permuted), result in v_x (permuted).  solve_perm sends a solve to the factorisation (solve_direct) or to the iterative
+// hierarchy (hierarchy_solve: pcg_restarts, then hierarchy_fallback).  solve_direct runs the hierarchy as its probe and as its fallback; every
+// run of the hierarchy is told its iteration cap and its mode by the caller.
+enum HierMode { HIER_FULL, HIER_PROBE };   // HIER_PROBE: a PCG that does not converge within the cap ends the run with flag 3 (no fallback solvers)
+static int hierarchy_solve(tsl_ctx* c, tsl_solve_stats* st, int cap, HierMode mode);
+
+static void solve_stats_reset(tsl_ctx* c, tsl_solve_stats* st) {
+  st->iters = 0; st->restarts = 0; st->flag = 0; st->rel_residual = 0; st->method = 0; st->attained = 0; st->backward_error = 0;
+  c->last_xmax_valid = false;
+}
+
+struct PcgOutcome { bool need_fallback = false, indefinite = false; };
+
+// Multigrid- or block-Jacobi-preconditioned CG, restarted from the true residual (at most 20 times); st->iters counts at most `cap` iterations
+// (to the chunk).  out->need_fallback: not converged; out->indefinite: the recurrence met a direction of non-positive curvature.
+static int pcg_restarts(tsl_ctx* c, tsl_solve_stats* st, int cap, PcgOutcome* out) {
+  hipStream_t s = c->stream;
+  const int NV = c->NV;
+  const size_t n3 = 3 * (size_t)NV;
+  const int gb = nblk(NV, 256);
+  TSL_TRY(block_jacobi_ensure(c));   // (skipped by an assembly that expected the factorisation to take this solve)
+  HIP_OK(hipMemsetAsync(c->v_x.p, 0, n3 * sizeof(double), s));
+  HIP_OK(hipMemsetAsync(c->scal.p, 0, sizeof(SolverScalars), s));
+  hipLaunchKernelGGL(k_dot, dim3(DOT_BLOCKS), dim3(256), 0, s, n3, c->v_b.p, c->v_b.p, &SC(c)->bb, DOT_SCRATCH(c));
+  TSL_TRY(read_scal(c));
+  const double bb = HSC(c)->bb;
+  if (!(bb > 0)) return 0;  // zero rhs -> x = 0
+  const double tol2 = c->cg_tol * c->cg_tol * bb;
+  int total_it = 0;
+  if (body_active(c) && !c->bd_valid) TSL_TRY(body_build_inverse(c));
+  const bool bd = body_active(c) && c->bd_valid;
+  const int n_rz = gb + (bd ? c->bd_wg : 0);
+  double rr_prev_outer = 1e300;
+  for (int outer = 0; outer < 20; outer++) {
+    PcgScal hs;
+    memset(&hs, 0, sizeof(hs));
+    hs.bb = bb; hs.thresh2 = 0.25 * tol2; hs.n_part1 = c->n_slices; hs.n_part2 = n_rz;
+    HIP_OK(hipMemcpyAsync(c->scal.p, &hs, sizeof(PcgScal), hipMemcpyHostToDevice, s));
+    if (outer > 0) launch_spmv(c, c->vals.p, c->v_x.p, c->v_Ap.p, -1, 0);
+    // true residual, z = M^-1 r, partial r.z / r.r
+    hipLaunchKernelGGL(k_pcg_update, dim3(gb + (pcg_fold(c) ? c->bd_wg : 0)), dim3(256), 0, s, NV, (const double*)nullptr, (const double*)nullptr, c->Dinv.p, c->v_x.p, c->v_r.p,
+                       c->v_z.p, c->part_pAp.p, c->part_rz.p, c->part_rr.p, PSC(c), 0, c->v_b.p, outer > 0 ? c->v_Ap.p : (const double*)nullptr, mg_active(c) ? 0 : 1,
+                       (const double*)nullptr, gb, c->bd_args, c->bd_Binv.p, pcg_fold(c) ? c->bd_rb.p : (double*)nullptr, c->bd_scr_n);
+    hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(256), 0, s, c->part_rr.p, gb, &PSC(c)->rr_last);
+    if (outer > 0) {  // verification of a converged recurrence: the true residual decides before a V-cycle is spent on it
+      TSL_TRY(read_scal(c));
+      const double rr1 = HPSC(c)->rr_last;
+      st->rel_residual = sqrt(rr1 / bb);
+      if (rr1 <= tol2) { out->need_fallback = false; break; }
+      // attainable accuracy: when a restart no longer halves the true residual the solve has reached what fp64 allows for
+      // this conditioning (a direct solver has the same backward error); accept if within 1e2 of the requested tolerance (reported: attained)
+      if (rr1 > 0.25 * rr_prev_outer && rr1 <= 1e4 * tol2) { out->need_fallback = false; st->attained = 1; break; }
+    }
+    if (mg_active(c)) {
+      if (!c->mg_ops_valid) TSL_TRY(mg_setup_operators(c));
+      mg_vcycle(c, c->v_r.p, c->v_z.p, c->part_rz.p);
+    } else if (bd) body_apply(c, 0, c->v_r.p, nullptr, c->v_z.p, c->v_r.p, c->part_rz.p + gb);
+    hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(256), 0, s, c->part_rz.p, n_rz, &PSC(c)->rz_last);
+    TSL_TRY(read_scal(c));
+    const double rr0 = HPSC(c)->rr_last;
+    st->rel_residual = sqrt(rr0 / bb);
+    if (rr0 <= tol2) { out->need_fallback = false; break; }
+    rr_prev_outer = rr0;
+    if (!(HPSC(c)->rz_last > 0)) { out->need_fallback = true; break; }
+    if (outer > 0) st->restarts++;
+    out->need_fallback = true;
+    int flag = 0, it = 0;
+    const auto tm0 = std::chrono::steady_clock::now();
+    // iteration 0 (beta = 0) eagerly, then graph replays of `chunk` iterations (parities 1,0,...)
+    launch_pcg_iteration(c, 0, 1, nullptr);
+    it++; total_it++; c->prof_launches++;
+    // iterations per graph replay / host convergence read.  With multigrid: eight on long solves (the previous time step needed more than 150 per
+    // solve: cfg4 1.56 -> 1.53 s per step), four otherwise (the idle launches after convergence cost drape 4 % with eight).  Block-Jacobi PCG: 32.
+    const int chunk = mg_active(c) ? (c->last_step_iters_per_solve > 150.0 ? 8 : 4) : 32;
+    TSL_TRY(pcg_chunk_graph(c, chunk));
+    int n_chunks = 0;
+    // (a second chunk kept in flight behind the one whose convergence record the host waits for was measured and dropped: the time per iteration
+    // does not change -- the gaps are between dependent kernels inside the graph, not host round trips -- and the idle chunk cost ~0.2 ms per solve.)
+    // A chunk whose device-clock stamps are sampled for the profile gets no successor until read.
+    int inflight = 0, head = 0;
+    bool sampled[2] = {false, false};
+    auto launch_chunk = [&]() -> int {
+      const int sl = (head + inflight) & 1;
+      // every 32nd chunk of a profiled run is launched kernel by kernel so that one K1 can be timed with hipEvents
+      const bool ev_chunk = c->prof_enable && (c->prof_chunks++ % 32 == 16);
+      if (!ev_chunk) HIP_OK(hipGraphLaunch(c->pcg_graph, s));
+      else {
+        c->ev_sample_next = ev_chunk;
+        for (int i = 0; i < chunk; i++) launch_pcg_iteration(c, (i & 1) ^ 1, 0, nullptr);
+        hipLaunchKernelGGL(k_pcg_check, dim3(1), dim3(256), 0, s, c->part_rr.p, PSC(c));
+      }
+      HIP_OK(hipMemcpyAsync(&c->h_scal2[sl], c->scal.p, sizeof(CgScal), hipMemcpyDeviceToHost, s));
+      HIP_OK(hipEventRecord(c->rb_event[sl], s));
+      sampled[sl] = !ev_chunk && c->prof_enable && (n_chunks++ % 8 == 0);
+      inflight++; it += chunk; total_it += chunk; c->prof_launches += chunk;
+      return 0;
+    };
+    while (true) {
+      while (inflight < 1 && total_it < cap && !(inflight == 1 && sampled[head])) TSL_TRY(launch_chunk());
+      if (inflight == 0) break;  // iteration cap
+      HIP_OK(hipEventSynchronize(c->rb_event[head]));
+      if (sampled[head]) TSL_TRY(prof_sample_graph(c));
+      memcpy(c->h_scal, &c->h_scal2[head], sizeof(CgScal));
+      inflight--; head ^= 1;
+      flag = HPSC(c)->flag;
+      if (flag) break;
+    }
+    if (inflight) HIP_OK(hipStreamSynchronize(s));
+    if (c->prof_enable) prof_collect(c);
+    c->tm_loop += std::chrono::duration<double>(std::chrono::steady_clock::now() - tm0).count();
+    if (flag) total_it = total_it - it + HPSC(c)->iters;  // iterations actually executed before the kernels went idle
+    if (flag == 1) { out->indefinite = true; c->mg_omega_valid = false; }
+    if (flag != 2) break;  // breakdown or iteration cap
+  }
+  st->iters = total_it;
+  return 0;
+}
+
+// What follows a PCG that did not converge: plain block-Jacobi PCG where the multigrid-PCG stalled; else (indefinite operator, or block-Jacobi PCG
+// failed too) MINRES -- behind a preconditioner rebuilt from the fully projected assembly if the operator is indefinite --, GMRES, BiCGStab.
+static int hierarchy_fallback(tsl_ctx* c, tsl_solve_stats* st, int cap, bool indefinite) {
+  if (mg_active(c) && !indefinite) {
+    // multigrid-PCG stalled: retry with plain block-Jacobi PCG (an indefinite H goes straight to MINRES)
+    Suspend no_mg(c->mg_suspended);
+    tsl_solve_stats st2;
+    const int rc = hierarchy_solve(c, &st2, cap, HIER_FULL);
+    st->iters += st2.iters; st->restarts += st2.restarts + 1; st->flag = st2.flag == 0 ? 1 : st2.flag; st->rel_residual = st2.rel_residual; st->method = st2.method; st->attained = st2.attained;
+    return rc;
+  }
+  if (c->verbose) fprintf(stderr, "[tsl] PCG gave up: iters %d restarts %d rel_residual %.2e indefinite %d\n", st->iters, st->restarts, st->rel_residual, (int)indefinite);
+  if (indefinite) {
+    const int rcp = forward_spd_pc(c);
+    if (rcp < 0) return -1;
+    if (c->verbose && rcp == 0) fprintf(stderr, "[tsl] forward system indefinite: preconditioner rebuilt from the fully projected assembly\n");
+  }
+  {  // symmetric indefinite: short recurrences
+    tsl_solve_stats st2 = *st;
+    TSL_TRY(minres(c, &st2, cap));
+    if (c->verbose) fprintf(stderr, "[tsl] MINRES: flag %d iters %d restarts %d rel_residual %.2e\n", st2.flag, st2.iters - st->iters, st2.restarts, st2.rel_residual);
+    st->iters = st2.iters; st->restarts = st2.restarts; st->rel_residual = st2.rel_residual; st->attained = st2.attained;
+    if (st2.flag == 1) { st->flag = 1; st->method = 1; return 0; }
+  }
+  const int it0 = st->iters;
+  TSL_TRY(gmres(c, st, cap));
+  if (c->verbose) fprintf(stderr, "[tsl] GMRES: flag %d iters %d rel_residual %.2e\n", st->flag, st->iters - it0, st->rel_residual);
+  if (st->flag == 1) { st->method = 2; return 0; }
+  st->method = 3;
+  return bicgstab(c, st, cap);  // last resort
+}
+
+// One run of the iterative hierarchy with at most `cap` iterations per solver.  flag 0: PCG converged, 1: a fallback solver did, 3: nothing did.
+static int hierarchy_solve(tsl_ctx* c, tsl_solve_stats* st, int cap, HierMode mode) {
+  solve_stats_reset(c, st);
+  PcgOutcome pcg;
+  TSL_TRY(pcg_restarts(c, st, cap, &pcg));
+  if (!pcg.need_fallback) { st->flag = 0; return 0; }
+  if (mode == HIER_PROBE) { st->flag = 3; return 0; }   // probe of the iterative hierarchy failed: the caller factorises
+  return hierarchy_fallback(c, st, cap, pcg.indefinite);
+}
+
+// Primary path on refined cloths: multifrontal LU of the operator (like the reference's spsolve) + GMRES refinement against the operator product;
+// the iterative hierarchy only runs as the probe of the automatic mode, or if the factorisation fails.  While it does, ds_suspended is set:
+// direct_takes_solve must answer "no" to the assembly nested in forward_spd_pc, which has to form the block-Jacobi inverse and the contact diagonal.
+// first (scene group): the first pass of the factorised solve is in place and was not accepted (ir_pass_verdict); its statistics -- the solve
+// goes on from the second pass, as direct_refine would after its own first pass.
+static int solve_direct(tsl_ctx* c, tsl_solve_stats* st, const tsl_solve_stats* first) {
+  solve_stats_reset(c, st);
+  DirectSolver& d = c->ds;
+  // "direct" = -1 (auto): easy systems stay with the iterative hierarchy -- the contact-free 224 x 224 drape needs 26 multigrid-PCG
+  // iterations per solve (46 ms per step) against one 6 ms factorisation per solve (86 ms per step).  A solve first probes the
+  // hierarchy with a cap of `probe_cap` iterations (the cost of one factorisation); the first failure marks the scene hard and
+  // the following `probe_every` time steps go straight to the factorisation.
+  // Scenes with FEM bodies or active contacts skip the probe (round 4): it never succeeded on them (cfg3 / cfg4: 60 wasted iterations every
+  // 16 steps), and the hierarchy's f64-atomic reductions are the one part of the step that is not bit-reproducible.
+  if (!first && d.enable < 0 && !d.hard && c->n_tet == 0 && c->nc == 0) {
+    tsl_solve_stats s2;
+    int rc;
+    { Suspend hierarchy_runs(c->ds_suspended); rc = hierarchy_solve(c, &s2, std::min(c->cg_maxit, d.probe_cap), HIER_PROBE); }
+    if (rc) return rc;
+    if (s2.flag == 0) { *st = s2; return 0; }
+    d.hard = true; d.hard_steps = 0;
+    st->iters = s2.iters;   // counted with the solve that follows
+  }
+  tsl_solve_stats sd = first ? *first : *st;
+  // Set-up failures of the direct path (arena or GMRES-basis allocation, an inconsistent plan): with "direct" = 1 they are errors;
+  // in the automatic mode the solve falls through to the iterative hierarchy, which needs none of that memory, and after three
+  // such failures the context stops trying ("direct" = 0).
+  auto direct_try = [&]() -> int {
+    if (!d.numeric_valid) {
+      TSL_TRY(direct_plan(c));
+      TSL_TRY(direct_factor(c, -1, nullptr, c->v_b.p, c->v_x.p));   // (the first pass of direct_refine applies the factors to v_b -> v_x)
+    }
+    // plain refinement first; systems it does not settle go through the flexible GMRES from scratch
+    int rc_g = direct_refine(c, &sd, first != nullptr);
+    if (rc_g == 0 && sd.flag != 1) { const int it0 = sd.iters; sd = *st; c->last_xmax_valid = false; rc_g = gmres(c, &sd, c->cg_maxit, true); sd.iters += it0; }
+    if (rc_g) return -1;
+    int note[8];
+    const int lost = ds_flow_lost(c, sd.flag != 1, note);
+    if (lost < 0) return -1;
+    if (lost) {   // a dataflow launch that lost a flag leaves garbage factors: say so, go back to the launch-per-block-step path
+      // The first loss of a context that runs the look-ahead takes the LOOK-AHEAD away (the one known cause inside a process is side-stream work arriving while a launch is
+      // still being dispatched) and keeps the dataflow path; a loss without it -- or a second one -- takes the dataflow path.  Either way this system is
+      // refactorised on the launch-per-block-step path.
+      const bool blame_la = (d.lookahead & 1) != 0 && d.n_flow_abort == 0 && d.dbg != 21;
+      fprintf(stderr, "[tsl] k_ds_gj_flow: a workgroup waited in vain for a flag (launch not resident as a whole?): %s disabled for this context, refactorising "
+              "(workgroup %d of %d gave up; %d of the %d workgroups of the factorisation's dataflow launches had started; flag value %d, epoch %d)\n",
+              blame_la ? "\"direct_lookahead\"" : "\"direct_flow\"", note[2], note[1], note[0], d.flow_wgs_last, note[3], note[4]);
+      const int flow_keep = d.flow;
+      d.flow = 0; d.n_flow_abort++;
+      if (blame_la) d.lookahead = 0;
+      d.numeric_valid = false; d.have_factor = false;   // the factors in place are garbage: direct_factor must not return early
+      if (d.prezero_pending) { HIP_OK(hipStreamWaitEvent(c->stream, d.ev_zero, 0)); d.prezero_pending = false; }
+      TSL_TRY(direct_factor(c));
+      if (blame_la) d.flow = flow_keep;
+      sd = *st; c->last_xmax_valid = false;
+      TSL_TRY(direct_refine(c, &sd));
+      if (sd.flag != 1) { const int it0 = sd.iters; sd = *st; c->last_xmax_valid = false; TSL_TRY(gmres(c, &sd, c->cg_maxit, true)); sd.iters += it0; }
+    }
+    return 0;
+  };
+  if (direct_try() != 0) {
+    if (d.enable == 1) return -1;
+    (void)hipGetLastError();   // an out-of-memory allocation leaves a sticky-looking but recoverable error code
+    d.numeric_valid = false; d.have_factor = false; d.plan_valid = false;
+    fprintf(stderr, "[tsl] direct solver set-up failed (%s): this solve runs on the iterative hierarchy%s\n", tsl_last_error(),
+            ++d.n_setup_fail >= 3 ? "; direct path disabled for this context" : "");
+    if (d.n_setup_fail >= 3) d.enable = 0;
+    Suspend hierarchy_runs(c->ds_suspended);
+    const int rc = hierarchy_solve(c, st, c->cg_maxit, HIER_FULL);
+    if (rc == 0 && st->flag == 0) st->flag = 1;   // reported as a fallback
+    return rc;
+  }
+  if (sd.flag == 1) { *st = sd; st->flag = 0; st->method = 4; return 0; }
+  if (c->verbose) {
+    int nb[4] = {0, 0, 0, 0};
+    (void)hipMemcpy(nb, d.bad.p, sizeof(nb), hipMemcpyDeviceToHost);
+    fprintf(stderr, "[tsl] direct factorisation + GMRES did not converge (rel_residual %.2e, backward error %.2e after %d iterations, perturbed pivots %d / %d / %d in fronts of <= 128 / <= 512 / more pivots, nc %d): iterative fallback\n",
+            sd.rel_residual, sd.backward_error, sd.iters, nb[1], nb[2], nb[3], c->nc);
+    if (c->verbose > 1) {
+      std::vector<int> lg(DS_BAD_NOTE);
+      (void)hipMemcpy(lg.data(), d.bad.p, lg.size() * sizeof(int), hipMemcpyDeviceToHost);
+      const int nl = std::min(lg[4], DS_BADLOG);
+      static int n_dump = 0;
+      if (const char* dir = getenv("TSL_DUMP_DIR")) if (nl > 0 && n_dump < 3) {
+        char path[512];
+        snprintf(path, sizeof(path), "%s/front_%d.bin", dir, n_dump++);
+        d.numeric_valid = false;
+        TSL_TRY(direct_factor(c, lg[8] >> 6, path));
+      }
+      for (int i = 0; i < nl; i++) {
+        const int* L = &lg[8 + 4 * i];
+        const int sn = L[0] >> 6, kt = L[0] & 63;
+        const DsFrontDesc& f = d.plan.fr[sn];
+        float am; memcpy(&am, L + 3, 4);
+        const unsigned mask = (unsigned)L[1];
+        const int first = __builtin_ctz(mask | 0x80000000u), row = kt * DS_T + first;
+        const int vtx = row < f.p ? d.plan.vtx[f.vtx_off + row / 3] : -1;
+        fprintf(stderr, "[tsl]   perturbed pivots: front %d (level %d, p %d, b %d, own verts %d) tile %d rows mask %08x, first row %d (vertex %d dof %d%s), tile max %.3e\n",
+                sn, d.plan.sym.level[sn], f.p, f.b, f.nv_own, kt, mask, row, vtx, row % 3, vtx >= 0 && d.plan.sym.body_of[vtx] >= 0 ? ", body" : "", am);
+      }
+    }
+  }
+  // Where the refined factorisation stalls, the iterative hierarchy does not do better (it needs 1e4..1e5 iterations on the
+  // systems the factorisation is for, and the stalls seen are operators with entries of 1e15 beside 1e3 -- an element of a pad
+  // crushed flat late in a rollout): an answer within 1e-3 is returned as it is, flagged not converged; only a broken
+  // factorisation (residual above that) is worth a bounded attempt of the hierarchy.
+  if (sd.rel_residual <= 1e-3) { *st = sd; st->flag = 3; st->method = 4; return 0; }
+  tsl_solve_stats s2;
+  int rc;
+  {
+    Suspend hierarchy_runs(c->ds_suspended);
+    HIP_OK(hipMemcpyAsync(c->v_t4.p, c->v_x.p, 3 * (size_t)c->NV * sizeof(double), hipMemcpyDeviceToDevice, c->stream));  // the refined direct solution
+    rc = hierarchy_solve(c, &s2, std::min(c->cg_maxit, d.fallback_cap), HIER_FULL);
+  }
+  // keep the better of the two answers, flagged as not converged.  A non-finite residual never wins: a factorisation that produced
+  // Inf / NaN (element entries of 1e15 on a crushed pad) must not overwrite a finite iterate, and two non-finite answers are an error.
+  const bool sd_ok = std::isfinite(sd.rel_residual), s2_ok = rc == 0 && std::isfinite(s2.rel_residual);
+  if (rc == 0 && s2.flag == 3 && !sd_ok && !s2_ok) return tsl_fail("linear solve: factorisation and iterative fallback both ended with a non-finite residual");
+  if (rc == 0 && s2.flag == 3 && sd_ok && (!s2_ok || !(s2.rel_residual < sd.rel_residual))) {
+    HIP_OK(hipMemcpyAsync(c->v_x.p, c->v_t4.p, 3 * (size_t)c->NV * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+    *st = sd; st->iters = sd.iters + s2.iters; st->flag = 3; st->method = 4;
+    return 0;
+  }
+  st->iters = sd.iters + s2.iters; st->restarts = s2.restarts + 1; st->rel_residual = s2.rel_residual; st->method = s2.method; st->attained = s2.attained;
+  st->flag = s2.flag == 0 ? 1 : s2.flag;
+  return rc;
+}
+
+static int solve_perm(tsl_ctx* c, tsl_solve_stats* st, const tsl_solve_stats* first = nullptr) {
+  return direct_enabled(c) ? solve_direct(c, st, first) : hierarchy_solve(c, st, c->cg_maxit, HIER_FULL);
 }
 
 static int solve_orig(tsl_ctx* c, const double* rhs, double* x, tsl_solve_stats* st) {
@@ -2497,7 +2452,7 @@ static int newton_step(const std::vector<StepMember>& m, GroupPool* pool, tsl_ct
     tsl_ctx* c = m[i].c;
     memset(&st[i], 0, sizeof(tsl_step_stats));
     fact0[i] = c->ds.n_factor; plans0[i] = c->ds.n_plans;
-    c->in_step = true; c->warm_valid = false; c->mg_omega_valid = false; c->mg_cinv_valid = false; c->tm_loop = 0;
+    c->in_step = true; c->mg_omega_valid = false; c->tm_loop = 0;
     // level solved exactly by the multigrid cycle: a dense inverse per assembly pays for a ~840-node level (2.5k unknowns, some ms
     // per inversion) only when the solves are long -- decided from the previous time step (cfg4: 300 -> 220 iterations per solve
     // at +4.5 ms per assembly; the scaled scene with ~100 iterations per solve keeps the 225-node level)
@@ -2844,7 +2799,7 @@ extern "C" int tsl_matrix_import(tsl_ctx* c, const double* vals) {
   HIP_OK(hipMemcpy(c->vals.p, hv.data(), hv.size() * sizeof(double), hipMemcpyHostToDevice));
   c->ds.numeric_valid = false; c->ds.anorm_valid = false;
   c->mg_ops_valid = false; c->pc_separate = false;
-  c->bd_valid = false; c->mg_omega_valid = false; c->mg_cinv_valid = false;
+  c->bd_valid = false; c->mg_omega_valid = false;
   return 0;
 }
 
@@ -3177,9 +3132,9 @@ static int adjoint_pre(tsl_ctx* c, const AdjArgs& a, double** rhs) {
   // below is the un-projected H, which may be indefinite, and smoothers / coarse operators built from it are not safe
   const bool have_mg = !c->mg.empty() && c->mg_enable != 0;
   // the direct path factorises the un-projected operator itself; its auto mode may still probe the hierarchy first (not marked hard)
-  const bool spd_pc = c->adj_spd_pc && (have_mg || body_active(c)) && !(direct_enabled(c) && (c->ds.enable == 1 || c->ds.hard || c->n_tet > 0 || c->nc > 0));   // (no probe of the hierarchy: see solve_perm)
+  const bool spd_pc = c->adj_spd_pc && (have_mg || body_active(c)) && !(direct_enabled(c) && (c->ds.enable == 1 || c->ds.hard || c->n_tet > 0 || c->nc > 0));   // (no probe of the hierarchy: see solve_direct)
   c->bd_valid = false;
-  c->mg_omega_valid = false; c->mg_cinv_valid = false;
+  c->mg_omega_valid = false;
   if (spd_pc) {
     TSL_TRY(assemble(c, x_s, x_prev, x_prev, ref_prev, 1, nullptr));
     if (body_active(c)) TSL_TRY(body_build_inverse(c));
