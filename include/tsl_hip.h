@@ -170,6 +170,34 @@ int tsl_set_handle_targets(tsl_ctx* ctx, const double* targets_host);
 int tsl_handle_force(tsl_ctx* ctx, const double* pos_dev, double* out_host);
 int tsl_handle_grad(tsl_ctx* ctx, const double* p_dev, double* out_host);
 
+/* Rigid frames for the handles (no reference counterpart): handle i may belong to frame f_i in [0, n_frame) with a local point r_i; f_i = -1 is a
+ * free handle with a world target, as above.  Frame j has a pose (c_j, q_j), q = (s, x, y, z) in the convention of quat_to_rotmat
+ * (engine/gripper_single.py), and the target of a framed handle is t_i = c_j + R(q_j) r_i.  Frames only rewrite rows of the target buffer: energy,
+ * gradient, matrix, "k_handle", tsl_handle_force and tsl_handle_grad read the targets as before, and no frame kernel runs inside tsl_step,
+ * tsl_energy, tsl_assemble or tsl_adjoint_step.  Conventions of tsl_set_handles: host pointers, the stream is synchronised, the lists are copied.
+ *   tsl_set_handle_frames: frame_of_handle_host (n_handle), local_host (n_handle x 3; rows of free handles are not read), n_frame; n_frame = 0
+ *     removes all frames and reads no list.  Fails, naming the offender, for a frame index outside [-1, n_frame), a non-finite local point of a
+ *     framed handle, frames asked for while there are no handles.  Poses start at the identity at the origin, and the framed rows of the targets
+ *     are written at once (t_i = r_i).  tsl_set_handles removes all frames: the handle list changed.
+ *   tsl_set_frame_poses: pos_host (n_frame x 3), quat_host (n_frame x 4).  Every quaternion is normalised on the host; a zero or non-finite one
+ *     (or a non-finite position) fails and names the frame.  Rewrites the rows of the targets that belong to framed handles; rows of free handles
+ *     keep their value.  tsl_set_handle_targets on a context with frames uploads all rows and rewrites the framed ones again, so the targets do
+ *     not depend on the order of the two calls.
+ *   tsl_handle_targets: out_host (n_handle x 3) = the targets as they stand.
+ *   tsl_frame_wrench: out_host (n_frame x 6) = (sum_i f_i, sum_i (t_i - c_j) x f_i) over the handles of frame j, f_i the row of tsl_handle_force:
+ *     force and moment about c_j that the frame's handles apply to the cloth, = dE_h / d(c_j, theta_j).  Frozen dofs are NOT masked.
+ *   tsl_frame_grad: the contribution of one reverse step to d(loss)/d(c_j) and d(loss)/d(theta_j), theta_j a world-frame rotation vector applied on
+ *     the left (R <- exp([d theta]x) R): out_host (n_frame x 6) = (sum_i g_i, sum_i (R r_i) x g_i), g_i the row of tsl_handle_grad (k_handle w_i
+ *     p_{v_i} on free dofs, 0 on frozen ones), sign of tsl_param_grad_keys; p_dev == NULL: the solution of the last tsl_adjoint_step.  Like
+ *     tsl_handle_grad it belongs to the targets as last set: set the poses of step s before the reverse step s.
+ *   Both read-outs: one workgroup per frame, a fixed order of additions (the same bits run to run); a frame without handles reads six zeros; with
+ *     k_handle = 0 both read zeros and launch nothing; without frames both do nothing. */
+int tsl_set_handle_frames(tsl_ctx* ctx, const int32_t* frame_of_handle_host, const double* local_host, int32_t n_frame);
+int tsl_set_frame_poses(tsl_ctx* ctx, const double* pos_host, const double* quat_host);
+int tsl_handle_targets(tsl_ctx* ctx, double* out_host);
+int tsl_frame_wrench(tsl_ctx* ctx, const double* pos_dev, double* out_host);
+int tsl_frame_grad(tsl_ctx* ctx, const double* p_dev, double* out_host);
+
 /* BaseScene.compute_energy (BaseScene.py:427-451) at the given state, constraints as last detected. */
 int tsl_energy(tsl_ctx* ctx, const double* pos_dev, const double* prev_pos_dev, const double* vel_dev,
                const double* ref_angle_dev, double* energy_host);

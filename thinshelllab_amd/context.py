@@ -118,6 +118,7 @@ class TslContext:
         assert w is None or w.shape == v.shape, (v.shape, w.shape)
         check(self.L.tsl_set_handles(self.h, v.ctypes.data if len(v) else None, None if w is None or not len(v) else w.ctypes.data, len(v)), "tsl_set_handles")
         self.n_handle = len(v)
+        self.n_frame = 0   # (the library drops the frames with the handle list)
 
     def set_handle_targets(self, targets):
         t = _np(targets, np.float64)
@@ -138,6 +139,50 @@ class TslContext:
         self.refresh_stream()
         out = np.zeros((getattr(self, "n_handle", 0), 3))
         check(self.L.tsl_handle_grad(self.h, _ptr(p), out.ctypes.data), "tsl_handle_grad")
+        return out
+
+    # ---- rigid frames of the handles (tsl_set_handle_frames)
+    def set_handle_frames(self, frame_of_handle, local_points, n_frame):
+        """frame of every handle (-1: free) and its local point (n_handle, 3); n_frame = 0 removes all frames.  Poses start at the identity."""
+        n_frame = int(n_frame)
+        if n_frame == 0:
+            check(self.L.tsl_set_handle_frames(self.h, None, None, 0), "tsl_set_handle_frames")
+        else:
+            f = _np(frame_of_handle, np.int32).reshape(-1)
+            r = _np(local_points, np.float64)
+            assert f.shape == (getattr(self, "n_handle", 0),) and r.shape == (len(f), 3), (f.shape, r.shape)
+            check(self.L.tsl_set_handle_frames(self.h, f.ctypes.data if len(f) else None, r.ctypes.data if len(f) else None, n_frame), "tsl_set_handle_frames")
+        self.n_frame = n_frame
+
+    def set_frame_poses(self, pos, quat):
+        """positions (n_frame, 3) and quaternions (n_frame, 4) = (s, x, y, z), normalised by the library; rewrites the targets of the framed handles"""
+        c = _np(pos, np.float64)
+        q = _np(quat, np.float64)
+        assert c.shape == (getattr(self, "n_frame", 0), 3) and q.shape == (len(c), 4), (c.shape, q.shape)
+        if len(c):
+            self.refresh_stream()
+            check(self.L.tsl_set_frame_poses(self.h, c.ctypes.data, q.ctypes.data), "tsl_set_frame_poses")
+
+    def handle_targets(self):
+        """(n, 3) the targets as they stand: what was set for free handles, c + R r for framed ones"""
+        self.refresh_stream()
+        out = np.zeros((getattr(self, "n_handle", 0), 3))
+        check(self.L.tsl_handle_targets(self.h, out.ctypes.data), "tsl_handle_targets")
+        return out
+
+    def frame_wrench(self, pos):
+        """(n_frame, 6) force and moment about the frame's position that its handles apply to the cloth at the state pos (frozen dofs not masked)"""
+        self.refresh_stream()
+        out = np.zeros((getattr(self, "n_frame", 0), 6))
+        check(self.L.tsl_frame_wrench(self.h, _ptr(pos), out.ctypes.data), "tsl_frame_wrench")
+        return out
+
+    def frame_grad(self, p=None):
+        """(n_frame, 6) contribution of one reverse step to d(loss)/d(position) and d(loss)/d(world rotation vector applied on the left) of every
+        frame; p None: the solution of the last adjoint_step, else a 3 * tot_NV device vector"""
+        self.refresh_stream()
+        out = np.zeros((getattr(self, "n_frame", 0), 6))
+        check(self.L.tsl_frame_grad(self.h, _ptr(p), out.ctypes.data), "tsl_frame_grad")
         return out
 
     # ---- engine calls

@@ -259,6 +259,11 @@ struct tsl_ctx {
   double k_handle = 0.0;
   DevBuf<int> hd_v;
   DevBuf<double> hd_w, hd_t, hd_out;   // n, n x 3, n x 3 (read-outs of tsl_handle_force / tsl_handle_grad)
+  // rigid frames of the handles (tsl_set_handle_frames, k_frame.hpp): frame and local point of each handle, the handles of every frame as a CSR,
+  // the poses as (c, R); k_frame_targets writes the framed rows of hd_t.  tsl_set_handles resets n_frame to 0
+  int n_frame = 0;
+  DevBuf<int> fr_of, fr_ptr, fr_idx;              // n_handle, n_frame + 1, number of framed handles
+  DevBuf<double> fr_local, fr_c, fr_R, fr_out;    // n_handle x 3, n_frame x 3, n_frame x 9, n_frame x 6 (read-outs of tsl_frame_wrench / tsl_frame_grad)
 
   // ---- matrix (SELL-64 of 3x3 blocks, rows permuted by length)
   int n_slices = 0;

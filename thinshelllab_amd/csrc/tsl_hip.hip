@@ -14,10 +14,12 @@
 #include "k_cloth.hpp"
 #include "k_contact.hpp"
 #include "k_fem.hpp"
+#include "k_frame.hpp"
 #include "k_handle.hpp"
 #include "k_mg.hpp"
 #include "k_param.hpp"
 #include "k_solver.hpp"
+#include "frame_host.hpp"
 #include "handle_host.hpp"
 #include "tsl_ctx.hpp"
 
@@ -580,6 +582,18 @@ extern "C" int tsl_set_gravity(tsl_ctx* c, const double* g) {
   return 0;
 }
 
+// Rigid frames of the handles (k_frame.hpp), used by the handle entry points below and defined behind them
+static void frames_release(tsl_ctx* c) {
+  c->n_frame = 0;
+  c->fr_of.release(); c->fr_ptr.release(); c->fr_idx.release(); c->fr_local.release(); c->fr_c.release(); c->fr_R.release(); c->fr_out.release();
+}
+static FrameArgs frame_args(tsl_ctx* c) { return FrameArgs{c->n_frame, c->fr_of.p, c->fr_local.p, c->fr_c.p, c->fr_R.p, c->fr_ptr.p, c->fr_idx.p}; }
+// the framed rows of the target buffer from the poses as they stand (nothing without frames); the caller synchronises
+static void frame_targets_launch(tsl_ctx* c) {
+  if (c->n_frame == 0 || c->n_handle == 0) return;
+  hipLaunchKernelGGL(k_frame_targets, dim3(nblk(c->n_handle, 256)), dim3(256), 0, c->stream, c->n_handle, frame_args(c), c->hd_t.p);
+}
+
 // Soft handles (k_handle.hpp): the lists are checked on the host (handle_host.hpp) and copied into buffers of the context; targets start at zero
 extern "C" int tsl_set_handles(tsl_ctx* c, const int32_t* verts, const double* weights, int32_t n) {
   Scope scope(c);
@@ -589,6 +603,7 @@ extern "C" int tsl_set_handles(tsl_ctx* c, const int32_t* verts, const double* w
   c->mg_omega_valid = false;
   c->ds.anorm_valid = false;   // (the scale of the operator may change: |H|_inf is formed again when a refinement asks for it)
   c->n_handle = 0;
+  frames_release(c);   // (the handle list changed: the frames went with it)
   if (n == 0) { c->hd_v.release(); c->hd_w.release(); c->hd_t.release(); c->hd_out.release(); return 0; }
   std::vector<int> hv(verts, verts + n);
   std::vector<double> hw(n, 1.0);
@@ -606,6 +621,11 @@ extern "C" int tsl_set_handle_targets(tsl_ctx* c, const double* targets) {
   if (c->n_handle == 0) return 0;
   if (!targets) return tsl_fail("tsl_set_handle_targets: null targets for %d handles", c->n_handle);
   HIP_OK(hipMemcpy(c->hd_t.p, targets, 3 * (size_t)c->n_handle * sizeof(double), hipMemcpyHostToDevice));
+  if (c->n_frame > 0) {   // the rows of framed handles follow their frame, whichever of the targets and the poses was set last
+    frame_targets_launch(c);
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipStreamSynchronize(c->stream));
+  }
   return 0;
 }
 // read-outs, one value per handle and axis: the kernel writes hd_out, one copy to the host, one synchronisation
@@ -629,6 +649,80 @@ extern "C" int tsl_handle_grad(tsl_ctx* c, const double* p_dev, double* out_host
   hipLaunchKernelGGL(k_handle_backprop, dim3(nblk(c->n_handle, 256)), dim3(256), 0, c->stream, handle_args(c), p_dev ? p_dev : (const double*)c->pdir.p,
                      (const int*)c->frozen.p, c->hd_out.p);
   return handle_readout(c, out_host);
+}
+
+// Rigid frames for the handles (k_frame.hpp): lists checked and the CSR built on the host (frame_host.hpp), copies the context owns; conventions of
+// tsl_set_handles.  Poses start at the identity at the origin
+extern "C" int tsl_set_handle_frames(tsl_ctx* c, const int32_t* frame_of, const double* local, int32_t n_frame) {
+  Scope scope(c);
+  (void)hipStreamSynchronize(c->stream);
+  std::string err;
+  if (frame_validate(c->n_handle, frame_of, local, n_frame, err)) return tsl_fail("tsl_set_handle_frames: %s", err.c_str());
+  frames_release(c);
+  if (n_frame == 0) return 0;
+  const size_t n = (size_t)c->n_handle;
+  std::vector<int> ptr, idx;
+  frame_csr(c->n_handle, frame_of, n_frame, ptr, idx);
+  std::vector<double> hl(local, local + 3 * n), hR(9 * (size_t)n_frame, 0.0);
+  for (size_t i = 0; i < n; i++)
+    if (frame_of[i] < 0) hl[3 * i] = hl[3 * i + 1] = hl[3 * i + 2] = 0.0;   // (never read; keeps what is uploaded finite)
+  for (int j = 0; j < n_frame; j++) hR[9 * (size_t)j] = hR[9 * (size_t)j + 4] = hR[9 * (size_t)j + 8] = 1.0;
+  TSL_TRY(c->fr_of.upload(std::vector<int>(frame_of, frame_of + n)));
+  TSL_TRY(c->fr_local.upload(hl));
+  TSL_TRY(c->fr_ptr.upload(ptr));
+  TSL_TRY(c->fr_idx.upload(idx));
+  TSL_TRY(c->fr_c.upload(std::vector<double>(3 * (size_t)n_frame, 0.0)));
+  TSL_TRY(c->fr_R.upload(hR));
+  TSL_TRY(c->fr_out.alloc(6 * (size_t)n_frame));
+  c->n_frame = n_frame;
+  frame_targets_launch(c);
+  HIP_OK(hipGetLastError());
+  HIP_OK(hipStreamSynchronize(c->stream));
+  return 0;
+}
+extern "C" int tsl_set_frame_poses(tsl_ctx* c, const double* pos, const double* quat) {
+  Scope scope(c);
+  (void)hipStreamSynchronize(c->stream);
+  if (c->n_frame == 0) return 0;
+  std::string err;
+  std::vector<double> hc, hR;
+  if (frame_pose_matrices(pos, quat, c->n_frame, hc, hR, err)) return tsl_fail("tsl_set_frame_poses: %s", err.c_str());
+  HIP_OK(hipMemcpy(c->fr_c.p, hc.data(), hc.size() * sizeof(double), hipMemcpyHostToDevice));
+  HIP_OK(hipMemcpy(c->fr_R.p, hR.data(), hR.size() * sizeof(double), hipMemcpyHostToDevice));
+  frame_targets_launch(c);
+  HIP_OK(hipGetLastError());
+  HIP_OK(hipStreamSynchronize(c->stream));
+  return 0;
+}
+extern "C" int tsl_handle_targets(tsl_ctx* c, double* out_host) {
+  Scope scope(c);
+  if (c->n_handle == 0) return 0;
+  if (!out_host) return tsl_fail("tsl_handle_targets: null argument");
+  HIP_OK(hipMemcpyAsync(out_host, c->hd_t.p, 3 * (size_t)c->n_handle * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIP_OK(hipStreamSynchronize(c->stream));
+  return 0;
+}
+// read-outs, six values per frame: one workgroup per frame writes fr_out, one copy to the host, one synchronisation; k_handle = 0: zeros, no launch
+template <int MODE>
+static int frame_readout(tsl_ctx* c, const double* vec, double* out_host) {
+  if (c->k_handle == 0.0) { std::fill(out_host, out_host + 6 * (size_t)c->n_frame, 0.0); return 0; }
+  hipLaunchKernelGGL(k_frame_reduce<MODE>, dim3(c->n_frame), dim3(256), 0, c->stream, handle_args(c), frame_args(c), vec, (const int*)c->frozen.p, c->fr_out.p);
+  HIP_OK(hipGetLastError());
+  HIP_OK(hipMemcpyAsync(out_host, c->fr_out.p, 6 * (size_t)c->n_frame * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIP_OK(hipStreamSynchronize(c->stream));
+  return 0;
+}
+extern "C" int tsl_frame_wrench(tsl_ctx* c, const double* pos, double* out_host) {
+  Scope scope(c);
+  if (c->n_frame == 0) return 0;
+  if (!pos || !out_host) return tsl_fail("tsl_frame_wrench: null argument");
+  return frame_readout<FRAME_WRENCH>(c, pos, out_host);
+}
+extern "C" int tsl_frame_grad(tsl_ctx* c, const double* p_dev, double* out_host) {
+  Scope scope(c);
+  if (c->n_frame == 0) return 0;
+  if (!out_host) return tsl_fail("tsl_frame_grad: null argument");
+  return frame_readout<FRAME_GRAD>(c, p_dev ? p_dev : (const double*)c->pdir.p, out_host);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -16,6 +16,8 @@ import torch
 
 from . import gripper_single
 from .field import Field, ScalarField
+from .frames import compose, frame_targets, validate_frames, validate_poses
+from .gripper_single import quat_to_rotmat
 from .gripper_tactile import gripper
 from .model_elastic_offset import Elastic
 from .model_elastic_tactile import Elastic as tactile
@@ -110,6 +112,11 @@ class BaseScene:
         self._handle_w = None
         self._handle_t = np.zeros((0, 3))
         self.k_handle = 0.0
+        # rigid frames of the handles (set_handle_frames): frame and local point of every handle, position and unit quaternion of every frame
+        self._frame_of = np.zeros(0, np.int32)
+        self._frame_local = np.zeros((0, 3))
+        self._frame_pos = np.zeros((0, 3))
+        self._frame_quat = np.zeros((0, 4))
 
         self.init_scene_parameters()
         if self.effector_cnt == -1:
@@ -384,8 +391,13 @@ class BaseScene:
         if self._dirty:
             if "handles" in self._dirty:
                 self._push_handles()
-            elif "handle_targets" in self._dirty:
-                self._ctx.set_handle_targets(self._handle_t)
+            else:
+                if "handle_targets" in self._dirty:
+                    self._ctx.set_handle_targets(self._handle_t)
+                if "handle_frames" in self._dirty:
+                    self._push_frames()
+                elif "frame_poses" in self._dirty:
+                    self._ctx.set_frame_poses(self._frame_pos, self._frame_quat)
             if "frozen" in self._dirty:
                 self._ctx.set_frozen(self.frozen.to_numpy())
             if "border" in self._dirty:
@@ -431,6 +443,8 @@ class BaseScene:
             raise ValueError(f"set_handles: k_handle must be finite and >= 0 (got {k:g})")
         self._handle_v, self._handle_w, self.k_handle = v, w, k
         self._handle_t = np.zeros((len(v), 3))
+        self._frame_of, self._frame_local = np.zeros(0, np.int32), np.zeros((0, 3))   # (the handle list changed: the frames go with it)
+        self._frame_pos, self._frame_quat = np.zeros((0, 3)), np.zeros((0, 4))
         self._dirty.add("handles")
 
     def set_handle_targets(self, targets):
@@ -438,7 +452,7 @@ class BaseScene:
         t = np.array(targets.detach().cpu().numpy() if isinstance(targets, torch.Tensor) else targets, dtype=np.float64)
         if t.shape != (self.n_handle, 3):
             raise ValueError(f"set_handle_targets: targets of shape {t.shape} for {self.n_handle} handles (expected ({self.n_handle}, 3))")
-        self._handle_t = t
+        self._handle_t = self._framed(t)
         self._dirty.add("handle_targets")
 
     def handle_force(self):
@@ -449,6 +463,70 @@ class BaseScene:
         self._ctx.set_handles(self._handle_v, self._handle_w)
         self._ctx.set_param("k_handle", self.k_handle)
         self._ctx.set_handle_targets(self._handle_t)
+        self._push_frames()
+
+    # ------------------------------------------------------------------ rigid frames for the handles (no counterpart in the reference)
+    @property
+    def n_frame(self):
+        return len(self._frame_pos)
+
+    def set_handle_frames(self, frame_ids, local_points=None, n_frames=None):
+        """Put handles on rigid frames: handle i belongs to frame frame_ids[i] in [0, n_frames) with the local point local_points[i], or stays a free
+        handle with a world target (frame id -1).  The target of a framed handle is c + R(q) r_i with the frame's pose (c, q) (set_frame_poses,
+        move_frames).  n_frames None: largest id + 1; n_frames = 0 (or all ids -1 with n_frames None) removes the frames.  local_points None grasps
+        the handled vertices where they are: r_i = R^T (x_{v_i} - c) at the current poses.  Poses are kept when the number of frames stays, and
+        start at the identity at the origin otherwise.  The lists are checked here, before any library call."""
+        f = np.asarray(frame_ids)
+        if n_frames is None:
+            n_frames = int(f.max()) + 1 if f.ndim == 1 and f.size and np.issubdtype(f.dtype, np.integer) else 0
+        if int(n_frames) != self.n_frame:
+            pos, quat = np.zeros((int(max(n_frames, 0)), 3)), np.tile([1.0, 0.0, 0.0, 0.0], (int(max(n_frames, 0)), 1))
+        else:
+            pos, quat = self._frame_pos, self._frame_quat
+        if local_points is None:
+            local_points = np.zeros((self.n_handle, 3))
+            if f.shape == (self.n_handle,) and self.n_handle:
+                x = self.pos.to_numpy()[self._handle_v]
+                for i, fi in enumerate(f.tolist()):
+                    if 0 <= fi < len(pos):
+                        local_points[i] = quat_to_rotmat(quat[fi]).T @ (x[i] - pos[fi])
+        f, r = validate_frames(self.n_handle, f, local_points, n_frames)
+        self._frame_of, self._frame_local, self._frame_pos, self._frame_quat = f, r, pos, quat
+        self._handle_t = self._framed(self._handle_t)
+        self._dirty.add("handle_frames")
+
+    def set_frame_poses(self, pos, quat):
+        """position (n_frame, 3) and quaternion (n_frame, 4) = (s, x, y, z) of every frame, in the convention of gripper_single.quat_to_rotmat; the
+        quaternions are normalised, a zero or non-finite one raises.  Moves the targets of the framed handles for the next energy, assembly, time
+        step or reverse step; the engine context receives the poses at its next use."""
+        self._frame_pos, self._frame_quat = validate_poses(self.n_frame, pos, quat)
+        self._handle_t = self._framed(self._handle_t)
+        self._dirty.add("frame_poses")
+
+    def frame_poses(self):
+        """(positions (n_frame, 3), unit quaternions (n_frame, 4)), copies"""
+        return self._frame_pos.copy(), self._frame_quat.copy()
+
+    def move_frames(self, delta_pos, delta_theta):
+        """c <- c + delta_pos, q <- exp(delta_theta / 2) (x) q renormalised, per frame: delta_theta (n_frame, 3) is a world-frame rotation vector
+        applied on the left, the variable of the rotation block of frame_grad"""
+        dp, dt = np.asarray(delta_pos, dtype=np.float64), np.asarray(delta_theta, dtype=np.float64)
+        if dp.shape != (self.n_frame, 3) or dt.shape != (self.n_frame, 3):
+            raise ValueError(f"move_frames: steps of shape {dp.shape} and {dt.shape} for {self.n_frame} frames (expected ({self.n_frame}, 3) twice)")
+        self.set_frame_poses(*compose(self._frame_pos, self._frame_quat, dp, dt))
+
+    def frame_wrench(self):
+        """(n_frame, 6): force and moment about the frame's position that the handles of every frame apply to the cloth at the current positions"""
+        return self._ensure_ctx().frame_wrench(self.pos.t)
+
+    def _framed(self, t):
+        """the targets t with the rows of framed handles at c + R r (the host's copy of what k_frame_targets writes)"""
+        return frame_targets(t, self._frame_of, self._frame_local, self._frame_pos, self._frame_quat) if self.n_frame else t
+
+    def _push_frames(self):
+        if self.n_frame or getattr(self._ctx, "n_frame", 0):
+            self._ctx.set_handle_frames(self._frame_of, self._frame_local, self.n_frame)
+            self._ctx.set_frame_poses(self._frame_pos, self._frame_quat)
 
     def set_frozen_kernel(self):
         # BaseScene.py:1445-1463

@@ -14,23 +14,54 @@ from .field import Field
 
 # ---- soft handles on the tape (BaseScene.set_handles; shared with analytic_grad_system.Grad and SceneGroup.transfer_grad)
 def handle_tape_init(grad, sys, T):
-    """handle_targets / handle_grad (T, n, 3) when the scene has handles; nothing otherwise"""
+    """handle_targets / handle_grad (T, n, 3) when the scene has handles, frame_pos / frame_quat / frame_grad (T, n_frame, 3 / 4 / 6) when it has
+    frames; nothing otherwise"""
     grad.n_handle = getattr(sys, "n_handle", 0)
     if grad.n_handle:
         grad.handle_targets = Field(torch.zeros((T, grad.n_handle, 3), dtype=torch.float64))
         grad.handle_grad = Field(torch.zeros((T, grad.n_handle, 3), dtype=torch.float64))
+    # rigid frames of the handles (BaseScene.set_handle_frames): the poses of every step and d(loss)/d(position, world rotation vector on the left)
+    grad.n_frame = getattr(sys, "n_frame", 0)
+    if grad.n_frame:
+        grad.frame_pos = Field(torch.zeros((T, grad.n_frame, 3), dtype=torch.float64))
+        grad.frame_quat = Field(torch.zeros((T, grad.n_frame, 4), dtype=torch.float64))
+        grad.frame_grad = Field(torch.zeros((T, grad.n_frame, 6), dtype=torch.float64))
+
+
+def handle_tape_reset(grad):
+    if grad.n_handle:
+        grad.handle_targets.fill(0)
+        grad.handle_grad.fill(0)
+    if grad.n_frame:
+        grad.frame_pos.fill(0)
+        grad.frame_quat.fill(0)
+        grad.frame_grad.fill(0)
+
+
+def handle_tape_record(grad, sys, step):
+    """the targets (framed rows at c + R r) and the frame poses of step `step` onto the tape"""
+    if grad.n_handle:
+        grad.handle_targets.t[step] = torch.as_tensor(sys._handle_t)
+    if grad.n_frame:
+        grad.frame_pos.t[step] = torch.as_tensor(sys._frame_pos)
+        grad.frame_quat.t[step] = torch.as_tensor(sys._frame_quat)
 
 
 def handle_tape_push(grad, sys, step):
-    """the targets of step `step` back into the scene: the reverse step re-assembles at x_step and reads them"""
-    if grad.n_handle:
+    """the targets and the frame poses of step `step` back into the scene: the reverse step re-assembles at x_step and reads them"""
+    # (with every handle on a frame the poses say it all: 7 numbers per frame go to the device, not n x 3 rows)
+    if grad.n_handle and not (grad.n_frame and (sys._frame_of >= 0).all()):
         sys.set_handle_targets(grad.handle_targets.t[step].numpy())
+    if grad.n_frame:
+        sys.set_frame_poses(grad.frame_pos.t[step].numpy(), grad.frame_quat.t[step].numpy())
 
 
 def handle_tape_pull(grad, ctx, step):
-    """handle_grad[step] += d(loss)/d(targets of step `step`) of the reverse step just taken"""
+    """handle_grad[step] += d(loss)/d(targets of step `step`) of the reverse step just taken, frame_grad[step] += the same reduced to the frames"""
     if grad.n_handle:
         grad.handle_grad.t[step] += torch.as_tensor(ctx.handle_grad())
+    if grad.n_frame:
+        grad.frame_grad.t[step] += torch.as_tensor(ctx.frame_grad())
 
 
 class Grad:
@@ -65,9 +96,7 @@ class Grad:
         self.pos_buffer.fill(0)
         self.pos_grad.fill(0)
         self.angleref_grad.fill(0)
-        if self.n_handle:
-            self.handle_targets.fill(0)
-            self.handle_grad.fill(0)
+        handle_tape_reset(self)
 
     def init_mass(self, sys):
         self.mass.copy_from(sys.mass)
@@ -76,8 +105,7 @@ class Grad:
     def copy_pos(self, sys, step):
         self.pos_buffer.t[step].copy_(sys.pos.t)
         self.ref_angle_buffer.t[step].view(-1, 3).copy_(sys._ref_angle[: self.cloth_cnt * self.NF])
-        if self.n_handle:
-            self.handle_targets.t[step] = torch.as_tensor(sys._handle_t)
+        handle_tape_record(self, sys, step)
         if self.n_part > 0 and hasattr(sys, "gripper"):
             self.gripper_pos_buffer.t[step].copy_(sys.gripper.pos.t)
             self.gripper_rot_buffer.t[step].copy_(sys.gripper.rot.t)

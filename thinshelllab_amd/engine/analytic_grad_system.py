@@ -13,7 +13,7 @@ Beyond the reference: ``param_keys`` names further scalars, spelled as ``tsl_set
 """
 import torch
 
-from .analytic_grad_single import handle_tape_init, handle_tape_pull, handle_tape_push
+from .analytic_grad_single import handle_tape_init, handle_tape_pull, handle_tape_push, handle_tape_record, handle_tape_reset
 from .field import Field, ScalarField
 
 
@@ -60,9 +60,7 @@ class Grad:
         self.grad_friction_coef[None] = 0
         self.grad_kb[None] = 0
         self.grad_params = {}
-        if self.n_handle:
-            self.handle_targets.fill(0)
-            self.handle_grad.fill(0)
+        handle_tape_reset(self)
 
     def init_mass(self, sys):  # :41-44
         self.mass.copy_from(sys.mass)
@@ -70,8 +68,7 @@ class Grad:
     def copy_pos(self, sys, step):  # :46-59
         self.pos_buffer.t[step].copy_(sys.pos.t)
         self.ref_angle_buffer.t[step].view(-1, 3).copy_(sys._ref_angle[: self.cloth_cnt * self.NF])
-        if self.n_handle:
-            self.handle_targets.t[step] = torch.as_tensor(sys._handle_t)
+        handle_tape_record(self, sys, step)
         if self.n_part > 0 and hasattr(sys, "gripper"):
             self.gripper_pos_buffer.t[step].copy_(sys.gripper.pos.t)
             self.gripper_rot_buffer.t[step].copy_(sys.gripper.rot.t)
