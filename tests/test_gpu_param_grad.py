@@ -385,6 +385,10 @@ def test_errors_name_the_key():
         with pytest.raises(TslError, match=re.escape(k)):
             ctx.param_grads(pos, ref, ["cloth0.Kl", k])
     assert ctx.param_grads(pos, ref, []) == {}
+    # tsl_set_param reads the same keys through the same parser: a malformed or out-of-range index and an unknown field fail, naming the key
+    for k in ("cloth+0.Kl", "cloth 0.Kl", "cloth1.Kl", "cloth0.nope"):
+        with pytest.raises(TslError, match=re.escape(k)):
+            ctx.set_param(k, 1.0)
 
 
 def test_edge_edge_slots_fail_the_keys_they_would_need():

@@ -27,52 +27,61 @@ def _ptr(t):
     return C.c_void_p(t.ctypes.data)
 
 
+def scene_desc(*, tot_NV, dt, mass, gravity, frozen, cloths=(), elastics=(), faces=None, bodies=(), pairs=(),
+               k_contact=1000.0, eps_contact=1e-3, eps_v=0.01, damping=1.0, max_n_constraints=10000, grid_h=0.003, device=None):
+    """The ``SceneDesc`` that tsl_ctx_create reads, and the list of objects its pointers refer to (keep it alive as long as the description is used).
+    Host work only: neither a GPU nor the library is needed (`device` is accepted and ignored, so that the arguments are those of TslContext).
+    cloths: dicts with N, M, NV, NF, v_offset, dx, mass, Kl, Ka, Kb, k_angle, f2v, counter_face, counter_point, rest_area, rest_len
+    elastics: dicts with kind, n_verts, n_cells, v_offset, mu, lam, alpha, tets, B, W
+    bodies: (v_start, v_end, f_start, f_end); pairs: (b_idx, v_start, v_end, mu or None[, factor on mu_cloth_elastic])"""
+    keep = []
+    cl = (ClothDesc * max(len(cloths), 1))()
+    for i, c in enumerate(cloths):
+        arrs = [_np(c["f2v"], np.int32), _np(c["counter_face"], np.int32), _np(c["counter_point"], np.int32),
+                _np(c["rest_area"], np.float64), _np(c["rest_len"], np.float64)]
+        keep += arrs
+        cl[i] = ClothDesc(c["N"], c["M"], c["NV"], c["NF"], c["v_offset"], c["dx"], c["mass"], c["Kl"], c["Ka"], c["Kb"], c["k_angle"],
+                          *[a.ctypes.data for a in arrs])
+    el = (ElasticDesc * max(len(elastics), 1))()
+    for i, e in enumerate(elastics):
+        arrs = [_np(e["tets"], np.int32), _np(e["B"], np.float64), _np(e["W"], np.float64)]
+        keep += arrs
+        el[i] = ElasticDesc(e["kind"], e["n_verts"], e["n_cells"], e["v_offset"], e["mu"], e["lam"], e["alpha"], *[a.ctypes.data for a in arrs])
+    bd = (Body * max(len(bodies), 1))()
+    for i, b in enumerate(bodies):
+        bd[i] = Body(*[int(x) for x in b])
+    pr = (ContactPair * max(len(pairs), 1))()
+    for i, p in enumerate(pairs):
+        mu = p[3]   # float: fixed; None: live mu_cloth_elastic; "cloth_cloth": live mu_cloth_cloth
+        factor = float(p[4]) if len(p) > 4 else 0.0
+        kind = 0 if isinstance(mu, (int, float)) else (2 if mu == "cloth_cloth" else 1)
+        pr[i] = ContactPair(int(p[0]), int(p[1]), int(p[2]), kind, float(mu) if kind == 0 else factor)
+    faces = _np(faces if faces is not None else np.zeros((0, 3)), np.int32)
+    mass = _np(mass, np.float64); gravity = _np(gravity, np.float64); frozen = _np(frozen, np.int32)
+    assert mass.shape == (tot_NV,) and gravity.shape == (tot_NV, 3) and frozen.shape == (3 * tot_NV,)
+    d = SceneDesc(tot_NV, len(faces), dt, k_contact, eps_contact, eps_v, damping, int(max_n_constraints),
+                  len(cloths), cl, len(elastics), el, len(bodies), bd, len(pairs), pr,
+                  mass.ctypes.data, gravity.ctypes.data, faces.ctypes.data, frozen.ctypes.data, grid_h)
+    keep += [cl, el, bd, pr, faces, mass, gravity, frozen]
+    return d, keep
+
+
 class TslContext:
-    def __init__(self, *, tot_NV, dt, mass, gravity, frozen, cloths=(), elastics=(), faces=None, bodies=(), pairs=(),
-                 k_contact=1000.0, eps_contact=1e-3, eps_v=0.01, damping=1.0, max_n_constraints=10000, grid_h=0.003, device="cuda:0"):
-        """cloths: dicts with N, M, NV, NF, v_offset, dx, mass, Kl, Ka, Kb, k_angle, f2v, counter_face, counter_point, rest_area, rest_len
-        elastics: dicts with kind, n_verts, n_cells, v_offset, mu, lam, alpha, tets, B, W
-        bodies: (v_start, v_end, f_start, f_end); pairs: (b_idx, v_start, v_end, mu or None[, factor on mu_cloth_elastic])"""
+    def __init__(self, *, device="cuda:0", **scene):
+        """scene: the keyword arguments of scene_desc (tot_NV, dt, mass, gravity, frozen, cloths, elastics, faces, bodies, pairs and the scalars)"""
         self.L = _lib.load()
         if not torch.cuda.is_available():
             raise _lib.TslLibraryError("no HIP device visible: thinshelllab_amd has no CPU path")
         self.device = torch.device(device)
         torch.cuda.set_device(self.device)
-        self.tot_NV = int(tot_NV)
-        self._keep = []
-        cl = (ClothDesc * max(len(cloths), 1))()
-        for i, c in enumerate(cloths):
-            arrs = [_np(c["f2v"], np.int32), _np(c["counter_face"], np.int32), _np(c["counter_point"], np.int32),
-                    _np(c["rest_area"], np.float64), _np(c["rest_len"], np.float64)]
-            self._keep += arrs
-            cl[i] = ClothDesc(c["N"], c["M"], c["NV"], c["NF"], c["v_offset"], c["dx"], c["mass"], c["Kl"], c["Ka"], c["Kb"], c["k_angle"],
-                              *[a.ctypes.data for a in arrs])
-        el = (ElasticDesc * max(len(elastics), 1))()
-        for i, e in enumerate(elastics):
-            arrs = [_np(e["tets"], np.int32), _np(e["B"], np.float64), _np(e["W"], np.float64)]
-            self._keep += arrs
-            el[i] = ElasticDesc(e["kind"], e["n_verts"], e["n_cells"], e["v_offset"], e["mu"], e["lam"], e["alpha"], *[a.ctypes.data for a in arrs])
-        bd = (Body * max(len(bodies), 1))()
-        for i, b in enumerate(bodies):
-            bd[i] = Body(*[int(x) for x in b])
-        pr = (ContactPair * max(len(pairs), 1))()
-        for i, p in enumerate(pairs):
-            mu = p[3]   # float: fixed; None: live mu_cloth_elastic; "cloth_cloth": live mu_cloth_cloth
-            factor = float(p[4]) if len(p) > 4 else 0.0
-            kind = 0 if isinstance(mu, (int, float)) else (2 if mu == "cloth_cloth" else 1)
-            pr[i] = ContactPair(int(p[0]), int(p[1]), int(p[2]), kind, float(mu) if kind == 0 else factor)
-        faces = _np(faces if faces is not None else np.zeros((0, 3)), np.int32)
-        mass = _np(mass, np.float64); gravity = _np(gravity, np.float64); frozen = _np(frozen, np.int32)
-        assert mass.shape == (tot_NV,) and gravity.shape == (tot_NV, 3) and frozen.shape == (3 * tot_NV,)
-        d = SceneDesc(tot_NV, len(faces), dt, k_contact, eps_contact, eps_v, damping, int(max_n_constraints),
-                      len(cloths), cl, len(elastics), el, len(bodies), bd, len(pairs), pr,
-                      mass.ctypes.data, gravity.ctypes.data, faces.ctypes.data, frozen.ctypes.data, grid_h)
+        d, self._keep = scene_desc(**scene)
+        self.tot_NV = int(d.tot_NV)
         self.h = C.c_void_p()
         check(self.L.tsl_ctx_create(C.byref(d), C.byref(self.h)), "tsl_ctx_create")
-        self.n_body = len(bodies)
-        self.n_cface = sum(c["NF"] for c in cloths)
-        self.dt = dt
-        self.max_n_constraints = int(max_n_constraints)
+        self.n_body = d.n_body
+        self.n_cface = sum(d.cloths[i].NF for i in range(d.n_cloth))
+        self.dt = scene["dt"]
+        self.max_n_constraints = d.max_n_constraints
         self.L.tsl_set_stream(self.h, C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream))
         # solver switches for A/B runs of unchanged drivers: TSL_PARAMS="key=value,key=value" (keys of tsl_set_param)
         for kv in os.environ.get("TSL_PARAMS", "").split(","):

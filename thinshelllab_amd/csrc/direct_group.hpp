@@ -422,12 +422,7 @@ tsl_group::~tsl_group() {
   pool.reset();
   if (g) {
     ds_flow_token_release(g->ds);
-    DirectSolver& gd = g->ds;
-    if (gd.zstream) (void)hipStreamDestroy(gd.zstream);
-    for (int k = 0; k < DS_NSIDE; k++) if (gd.fstream[k]) (void)hipStreamDestroy(gd.fstream[k]);
-    if (gd.pin) (void)hipHostFree(gd.pin);
-    if (g->stream) (void)hipStreamDestroy(g->stream);
-    delete g;
+    delete g;   // (its streams, events and pinned arena go with it: ~tsl_ctx, ~DirectSolver)
     g = nullptr;
   }
   for (hipEvent_t e : ev_m) if (e) (void)hipEventDestroy(e);

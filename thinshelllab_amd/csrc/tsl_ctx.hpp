@@ -15,6 +15,7 @@
 #include "../../include/tsl_hip.h"
 #include "k_body.hpp"
 #include "direct_plan.hpp"
+#include "scene_tables.hpp"   // ClothDev, ElasticDev (the per-cloth / per-body constants the kernels read) and the host tables of a scene
 
 #define TSL_SLICE 64  // rows per SELL slice == wavefront width on gfx950
 
@@ -61,16 +62,6 @@ struct DevBuf {
   DevBuf(const DevBuf&) = delete;
   DevBuf& operator=(const DevBuf&) = delete;
   ~DevBuf() { release(); }
-};
-
-// per-cloth constants read by the kernels (device copy)
-struct ClothDev {
-  int face_start, NF, v_offset, NV;
-  double dx, mass, Kl, Ka, Kb, k_angle;
-};
-struct ElasticDev {
-  int kind, cell_start, n_cells, v_offset, n_verts;
-  double mu, lam, alpha;
 };
 
 // device scalars shared by the solver / Newton kernels: one 256-B record, viewed as CgScal (k_solver.hpp)
@@ -196,6 +187,20 @@ struct DirectSolver {
   int anorm_spd = -1;         // projection mode of the assembly the norm belongs to (the adjoint's un-projected operator gets its own)
   DevBuf<double> anorm_dev;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  DirectSolver() = default;
+  DirectSolver(const DirectSolver&) = delete;
+  DirectSolver& operator=(const DirectSolver&) = delete;
+  // streams, events and pinned buffers the solver created (direct_host.hpp), each side stream after its last launch has ended; the device buffers go
+  // with the members behind this body
+  ~DirectSolver() {
+    for (int k = 0; k < DS_NSIDE; k++) if (fstream[k]) { (void)hipStreamSynchronize(fstream[k]); (void)hipEventDestroy(ev_fjoin[k]); (void)hipStreamDestroy(fstream[k]); }
+    if (ev_ffork) (void)hipEventDestroy(ev_ffork);
+    for (int k = 0; k < 5; k++) if (ev_la[k]) (void)hipEventDestroy(ev_la[k]);
+    if (lastream) { (void)hipStreamSynchronize(lastream); (void)hipStreamDestroy(lastream); }
+    if (h_anorm) (void)hipHostFree(h_anorm);
+    if (pin) (void)hipHostFree(pin);
+    if (zstream) { (void)hipStreamSynchronize(zstream); (void)hipEventDestroy(ev_zfork); (void)hipEventDestroy(ev_zero); (void)hipStreamDestroy(zstream); }
+  }
 };
 
 struct tsl_group;
@@ -411,7 +416,24 @@ struct tsl_ctx {
   bool ds_suspended = false;  // set (Suspend) while the iterative hierarchy runs as the probe or the fallback of the direct solve: read by direct_takes_solve
   // stats
   tsl_step_stats step_stats{};
-  ~tsl_ctx() { for (auto* m : mg) delete m; }
+  tsl_ctx() = default;
+  tsl_ctx(const tsl_ctx&) = delete;
+  tsl_ctx& operator=(const tsl_ctx&) = delete;
+  // Everything the context created, whether tsl_ctx_create got to its end or not: pinned buffers, graph execs, events and streams here (a null check per
+  // handle), then -- behind this body -- the members: the solver's streams (~DirectSolver) and the device buffers.  The caller has synchronised the device.
+  ~tsl_ctx() {
+    if (h_scal) (void)hipHostFree(h_scal);
+    if (h_scal2) (void)hipHostFree(h_scal2);
+    if (h_ir) (void)hipHostFree(h_ir);
+    if (pcg_graph) (void)hipGraphExecDestroy(pcg_graph);
+    if (mr_graph) (void)hipGraphExecDestroy(mr_graph);
+    for (hipEvent_t e : {rb_event[0], rb_event[1], ev_in, ev_out, ev_fork, ev_fork0, ev_g2, ev_hh, ev_gf, ev_join, ev_join2})
+      if (e) (void)hipEventDestroy(e);
+    for (auto& e : ev_pool) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
+    for (hipStream_t s : {side, side2, stream})
+      if (s) (void)hipStreamDestroy(s);
+    for (auto* m : mg) delete m;
+  }
 };
 
 // Every entry point runs on the context's own stream; Enter/leave order it after / before the caller's stream.

@@ -21,6 +21,7 @@
 #include "k_solver.hpp"
 #include "frame_host.hpp"
 #include "handle_host.hpp"
+#include "param_keys.hpp"
 #include "tsl_ctx.hpp"
 
 thread_local std::string g_tsl_err;
@@ -51,60 +52,6 @@ int tsl_fail(const char* fmt, ...) {
 #define DOT_BLOCKS 120  // one f64 atomic per wave into a single address: more blocks only add contention (30 us at 600 blocks)
 static inline int nblk(long n, int b) { return (int)((n + b - 1) / b); }
 static inline int gsz(size_t n) { size_t b = (n + 255) / 256; return (int)std::min<size_t>(std::max<size_t>(b, 1), 4096); }
-
-// ------------------------------------------------------------------------------------------------
-struct Pattern {
-  std::vector<std::vector<int>> rows;  // original order
-  std::vector<int> perm, rowpos, slice_off, slice_len, colidx, diag_perm;
-  long n_slots = 0;
-  int n_slices = 0;
-  int lookup(int vi, int vj) const {
-    const auto& r = rows[vi];
-    auto it = std::lower_bound(r.begin(), r.end(), vj);
-    if (it == r.end() || *it != vj) return -1;
-    const int k = (int)(it - r.begin());
-    const int p = rowpos[vi], s = p >> 6, lane = p & 63;
-    return (int)(((long)slice_off[s] + 64L * k) * 9 + lane);
-  }
-};
-
-static void build_pattern(int NV, const std::vector<std::vector<int>>& cliques, Pattern& P) {
-  P.rows.assign(NV, {});
-  for (int i = 0; i < NV; i++) P.rows[i].push_back(i);
-  for (const auto& c : cliques)
-    for (int a : c)
-      for (int b : c) P.rows[a].push_back(b);
-  for (auto& r : P.rows) { std::sort(r.begin(), r.end()); r.erase(std::unique(r.begin(), r.end()), r.end()); }
-  P.perm.resize(NV);
-  for (int i = 0; i < NV; i++) P.perm[i] = i;
-  std::stable_sort(P.perm.begin(), P.perm.end(), [&](int a, int b) { return P.rows[a].size() > P.rows[b].size(); });
-  P.rowpos.resize(NV);
-  for (int p = 0; p < NV; p++) P.rowpos[P.perm[p]] = p;
-  P.n_slices = (NV + 63) / 64;
-  P.slice_off.assign(P.n_slices + 1, 0);
-  P.slice_len.assign(P.n_slices, 0);
-  long off = 0;
-  for (int s = 0; s < P.n_slices; s++) {
-    int len = 0;
-    for (int l = 0; l < 64 && s * 64 + l < NV; l++) len = std::max(len, (int)P.rows[P.perm[s * 64 + l]].size());
-    P.slice_len[s] = len;
-    P.slice_off[s] = (int)off;
-    off += 64L * len;
-  }
-  P.slice_off[P.n_slices] = (int)off;
-  P.n_slots = off;
-  P.colidx.assign(off, 0);
-  P.diag_perm.assign(NV, 0);
-  for (int p = 0; p < NV; p++) {
-    const int v = P.perm[p], s = p >> 6, lane = p & 63;
-    const auto& r = P.rows[v];
-    // padded slots (k >= row length) hold zero blocks; their column must not be the row itself, otherwise the
-    // frozen-diagonal rule of k_mask_matrix would hit them
-    const int pad_col = (p == 0) ? (NV > 1 ? 1 : 0) : 0;
-    for (int k = 0; k < P.slice_len[s]; k++) P.colidx[P.slice_off[s] + 64 * k + lane] = (k < (int)r.size()) ? P.rowpos[r[k]] : pad_col;
-    P.diag_perm[p] = P.lookup(v, v);
-  }
-}
 
 // ------------------------------------------------------------------------------------------------
 static int mg_build(tsl_ctx* c, const tsl_scene_desc* d);
@@ -163,203 +110,44 @@ extern "C" int tsl_ctx_create(const tsl_scene_desc* d, tsl_ctx** out) {
   if (!d || !out) return tsl_fail("tsl_ctx_create: null argument");
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return tsl_fail("tsl_ctx_create: no HIP device (this engine has no CPU path)");
-  tsl_ctx* c = new tsl_ctx();
-  if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess || hipEventCreateWithFlags(&c->ev_in, hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&c->ev_out, hipEventDisableTiming) != hipSuccess) { delete c; return tsl_fail("stream / event creation failed"); }
+  std::unique_ptr<tsl_ctx> owner(new tsl_ctx());   // every failure exit below releases what exists by then (~tsl_ctx)
+  tsl_ctx* c = owner.get();
+  const auto no_stream = [](hipStream_t* s) { return hipStreamCreateWithFlags(s, hipStreamNonBlocking) != hipSuccess; };
+  const auto no_event = [](hipEvent_t* e) { return hipEventCreateWithFlags(e, hipEventDisableTiming) != hipSuccess; };
+  if (no_stream(&c->stream) || no_event(&c->ev_in) || no_event(&c->ev_out)) return tsl_fail("stream / event creation failed");
   c->NV = d->tot_NV; c->NF = d->tot_NF;
   c->dt = d->dt; c->k_contact = d->k_contact; c->eps_contact = d->eps_contact; c->eps_v = d->eps_v; c->damping = d->damping;
   c->max_n_constraints = d->max_n_constraints > 0 ? d->max_n_constraints : 10000;
   c->grid_h = d->grid_h > 0 ? d->grid_h : 0.003;
   const int NV = c->NV;
-  std::vector<std::vector<int>> cliques;
 
-  // ---- cloth tables (global ids)
-  std::vector<int> f2v, cf, cp, cid, hinfo, hv;
-  std::vector<double> V, li;
-  int face_start = 0;
-  for (int ci = 0; ci < d->n_cloth; ci++) {
-    const tsl_cloth_desc& cd = d->cloths[ci];
-    ClothDev cdv{face_start, cd.NF, cd.v_offset, cd.NV, cd.dx, cd.mass, cd.Kl, cd.Ka, cd.Kb, cd.k_angle};
-    c->h_cloth.push_back(cdv);
-    if ((cd.N + 1) * (cd.M + 1) == cd.NV) c->ds.grids.push_back(DsGrid{cd.v_offset, cd.N, cd.M});
-    for (int i = 0; i < cd.NF; i++) {
-      for (int k = 0; k < 3; k++) {
-        f2v.push_back(cd.f2v_host[3 * i + k] + cd.v_offset);
-        const int nb = cd.counter_face_host[3 * i + k];
-        cf.push_back(nb < 0 ? -1 : nb + face_start);
-        cp.push_back(cd.counter_point_host[3 * i + k]);
-        li.push_back(cd.rest_len_host[3 * i + k]);
-      }
-      cid.push_back(ci);
-      V.push_back(cd.rest_area_host[i]);
-      cliques.push_back({cd.f2v_host[3 * i] + cd.v_offset, cd.f2v_host[3 * i + 1] + cd.v_offset, cd.f2v_host[3 * i + 2] + cd.v_offset});
-    }
-    for (int i = 0; i < cd.NF; i++)
-      for (int l = 0; l < 3; l++) {
-        const int nb = cd.counter_face_host[3 * i + l];
-        if (nb > i) {
-          const int p4 = cd.counter_point_host[3 * i + l];
-          const int p11 = (l + 1) % 3;
-          int p21 = (p4 + 1) % 3;
-          if (cd.f2v_host[3 * i + p11] != cd.f2v_host[3 * nb + p21]) p21 = (p4 + 2) % 3;
-          const int a = cd.f2v_host[3 * i + l] + cd.v_offset, b = cd.f2v_host[3 * i + (l + 1) % 3] + cd.v_offset;
-          const int cc = cd.f2v_host[3 * i + (l + 2) % 3] + cd.v_offset, dd = cd.f2v_host[3 * nb + p4] + cd.v_offset;
-          const int info[8] = {i + face_start, l, nb + face_start, p4, p21, 0, 0, 0};
-          hinfo.insert(hinfo.end(), info, info + 8);
-          hv.push_back(a); hv.push_back(b); hv.push_back(cc); hv.push_back(dd);
-          cliques.push_back({a, b, cc, dd});
-        }
-      }
-    face_start += cd.NF;
-  }
-  c->n_cface = face_start;
-  c->n_hinge = (int)hv.size() / 4;
-  {
-    // Hinges sorted by stencil class (the offsets of their four vertices relative to the first), then by first vertex: the lanes of
-    // a wave then add into CONSECUTIVE matrix rows (same block slot, neighbouring SELL lanes) -- 144 coalesced atomics per lane
-    // instead of scattered ones.  Every hinge-indexed quantity is addressed through (face, edge), so the order is free.
-    const int nh = c->n_hinge;
-    std::map<std::array<int, 3>, int> cls;
-    std::vector<int> key(nh), idx(nh);
-    for (int h = 0; h < nh; h++) {
-      const std::array<int, 3> t{hv[4 * h + 1] - hv[4 * h], hv[4 * h + 2] - hv[4 * h], hv[4 * h + 3] - hv[4 * h]};
-      auto it = cls.find(t);
-      if (it == cls.end()) it = cls.emplace(t, (int)cls.size()).first;
-      key[h] = it->second; idx[h] = h;
-    }
-    std::stable_sort(idx.begin(), idx.end(), [&](int x, int y) { return key[x] != key[y] ? key[x] < key[y] : hv[4 * x] < hv[4 * y]; });
-    std::vector<int> hinfo2(hinfo.size()), hv2(hv.size());
-    for (int h = 0; h < nh; h++) {
-      std::copy(hinfo.begin() + 8 * (size_t)idx[h], hinfo.begin() + 8 * (size_t)idx[h] + 8, hinfo2.begin() + 8 * (size_t)h);
-      std::copy(hv.begin() + 4 * (size_t)idx[h], hv.begin() + 4 * (size_t)idx[h] + 4, hv2.begin() + 4 * (size_t)h);
-    }
-    hinfo.swap(hinfo2); hv.swap(hv2);
-  }
-  c->h_cf_f2v = f2v; c->h_cf_cf = cf; c->h_cf_cp = cp;
-
-  // ---- tets
-  std::vector<int> tv, tel;
-  std::vector<double> tB, tW;
-  int cell_start = 0;
-  for (int ei = 0; ei < d->n_elastic; ei++) {
-    const tsl_elastic_desc& ed = d->elastics[ei];
-    ElasticDev edv{ed.kind, cell_start, ed.n_cells, ed.v_offset, ed.n_verts, ed.mu, ed.lam, ed.alpha};
-    c->h_el.push_back(edv);
-    c->ds.blocks.push_back(DsBlock{ed.v_offset, ed.n_verts});
-    for (int t = 0; t < ed.n_cells; t++) {
-      std::vector<int> cl;
-      for (int k = 0; k < 4; k++) { tv.push_back(ed.tets_host[4 * t + k] + ed.v_offset); cl.push_back(ed.tets_host[4 * t + k] + ed.v_offset); }
-      tel.push_back(ei);
-      for (int k = 0; k < 9; k++) tB.push_back(ed.B_host[9 * t + k]);
-      tW.push_back(ed.W_host[t]);
-      cliques.push_back(cl);
-    }
-    cell_start += ed.n_cells;
-  }
-  c->n_tet = cell_start;
-
-  // ---- matrix pattern
-  Pattern P;
-  build_pattern(NV, cliques, P);
+  // ---- host tables (scene_tables.hpp): the counts and the copies the context keeps
+  SceneTables T;
+  std::string err;
+  if (build_scene_tables(d, T, err)) return tsl_fail("%s", err.c_str());
+  const Pattern& P = T.P;
+  c->h_cloth = T.h_cloth; c->h_el = T.h_el; c->ds.grids = T.grids; c->ds.blocks = T.blocks;
+  c->n_cface = T.n_cface; c->n_hinge = T.n_hinge; c->n_tet = T.n_tet;
+  c->h_cf_f2v = T.f2v; c->h_cf_cf = T.cf; c->h_cf_cp = T.cp;
   c->h_rows = P.rows; c->h_perm = P.perm; c->h_rowpos = P.rowpos; c->h_slice_off = P.slice_off; c->h_slice_len = P.slice_len; c->h_colidx = P.colidx;
-  c->n_slices = P.n_slices; c->n_slots = P.n_slots;
-  c->nnzb = 0;
-  for (auto& r : P.rows) c->nnzb += (long)r.size();
-  if (P.n_slots * 9 >= (1L << 31)) { delete c; return tsl_fail("matrix too large for 32-bit slot offsets (%ld slots)", P.n_slots); }
-  std::vector<int> cfblk((size_t)c->n_cface * 9), hgblk((size_t)c->n_hinge * 16), tetblk((size_t)c->n_tet * 16), dblk(NV);
-  for (int f = 0; f < c->n_cface; f++)
-    for (int l = 0; l < 3; l++)
-      for (int m = 0; m < 3; m++) cfblk[(size_t)f * 9 + l * 3 + m] = P.lookup(f2v[3 * f + l], f2v[3 * f + m]);
-  for (int h = 0; h < c->n_hinge; h++)
-    for (int j = 0; j < 4; j++)
-      for (int k = 0; k < 4; k++) hgblk[(size_t)h * 16 + j * 4 + k] = P.lookup(hv[4 * h + j], hv[4 * h + k]);
-  for (int t = 0; t < c->n_tet; t++)
-    for (int j = 0; j < 4; j++)
-      for (int k = 0; k < 4; k++) tetblk[(size_t)t * 16 + j * 4 + k] = P.lookup(tv[4 * t + j], tv[4 * t + k]);
-  for (int v = 0; v < NV; v++) dblk[v] = P.lookup(v, v);
-#define UP(buf, vec) do { if (c->buf.upload(vec)) { delete c; return -1; } } while (0)
-  UP(d_cloth, c->h_cloth); UP(cf_f2v, f2v); UP(cf_cf, cf); UP(cf_cp, cp); UP(cf_cloth, cid); UP(cf_V, V); UP(cf_li, li);
-  std::vector<int> forder(c->n_cface);
-  {
-    std::map<std::array<int, 3>, int> cls;
-    std::vector<int> key(c->n_cface);
-    for (int f = 0; f < c->n_cface; f++) {
-      const std::array<int, 3> t{f2v[3 * f + 1] - f2v[3 * f], f2v[3 * f + 2] - f2v[3 * f], 0};
-      auto it = cls.find(t);
-      if (it == cls.end()) it = cls.emplace(t, (int)cls.size()).first;
-      key[f] = it->second; forder[f] = f;
-    }
-    std::stable_sort(forder.begin(), forder.end(), [&](int x, int y) { return key[x] != key[y] ? key[x] < key[y] : f2v[3 * x] < f2v[3 * y]; });
-  }
-  UP(cf_order, forder);
-  // gather assembly of the cloth Hessian (k_cloth_gather): per matrix block the list of (element, local vertex pair) that add to it
-  std::vector<int> cg_base, cg_ptr;
-  std::vector<unsigned> cg_ent;
-  {
-    std::vector<std::pair<int, unsigned>> tup;
-    tup.reserve((size_t)c->n_cface * 9 + (size_t)c->n_hinge * 16);
-    std::vector<int> fpos(c->n_cface);   // face -> its processing index (the face kernel writes its record there)
-    for (int t = 0; t < c->n_cface; t++) fpos[forder[t]] = t;
-    for (int f = 0; f < c->n_cface; f++)
-      for (int e = 0; e < 9; e++) tup.emplace_back(cfblk[(size_t)f * 9 + e], ((unsigned)fpos[f] << 4) | (unsigned)e);
-    for (int h = 0; h < c->n_hinge; h++)
-      for (int e = 0; e < 16; e++) tup.emplace_back(hgblk[(size_t)h * 16 + e], 0x80000000u | ((unsigned)h << 4) | (unsigned)e);
-    for (int t = 0; t < c->n_tet; t++)   // the element blocks of the FEM bodies take the same road (bit 30)
-      for (int e = 0; e < 16; e++) tup.emplace_back(tetblk[(size_t)t * 16 + e], 0x40000000u | ((unsigned)t << 4) | (unsigned)e);
-    // blocks of the cloth first, blocks of the FEM bodies behind them (a block belongs to one kind: the two gathers run on different streams)
-    auto is_tet = [](unsigned e) { return (e >> 30) == 1u; };
-    std::sort(tup.begin(), tup.end(), [&](const std::pair<int, unsigned>& x, const std::pair<int, unsigned>& y) {
-      if (is_tet(x.second) != is_tet(y.second)) return is_tet(y.second);
-      return x < y;
-    });
-    cg_ent.reserve(tup.size());
-    c->n_cgblk_cloth = 0;
-    for (size_t i = 0; i < tup.size(); i++) {
-      if (i == 0 || tup[i].first != tup[i - 1].first || is_tet(tup[i].second) != is_tet(tup[i - 1].second)) {
-        cg_base.push_back(tup[i].first); cg_ptr.push_back((int)i);
-        if (!is_tet(tup[i].second)) c->n_cgblk_cloth++;
-      }
-      cg_ent.push_back(tup[i].second);
-    }
-    cg_ptr.push_back((int)tup.size());
-    c->n_cgblk = (int)cg_base.size();
-    if (c->n_cface >= (1 << 26) || c->n_hinge >= (1 << 26) || c->n_tet >= (1 << 26)) { delete c; return tsl_fail("mesh too large for the packed gather lists"); }
-  }
-  // vertex -> staging slots of the element gradients (k_vertex_gather): faces (3 f + l), hinges (+ 4 h + j), tets (+ 4 t + j), ascending
-  std::vector<int> vg_ptr(NV + 1, 0), vg_idx;
-  {
-    c->vg_hinge0 = 3 * c->n_cface; c->vg_tet0 = c->vg_hinge0 + 4 * c->n_hinge; c->vg_ns = c->vg_tet0 + 4 * c->n_tet;
-    for (int v : f2v) vg_ptr[v + 1]++;
-    for (int v : hv) vg_ptr[v + 1]++;
-    for (int v : tv) vg_ptr[v + 1]++;
-    for (int v = 0; v < NV; v++) vg_ptr[v + 1] += vg_ptr[v];
-    vg_idx.resize(vg_ptr[NV]);
-    std::vector<int> cur(vg_ptr.begin(), vg_ptr.end() - 1);
-    for (size_t i = 0; i < f2v.size(); i++) vg_idx[cur[f2v[i]]++] = (int)i;
-    for (size_t i = 0; i < hv.size(); i++) vg_idx[cur[hv[i]]++] = c->vg_hinge0 + (int)i;
-    for (size_t i = 0; i < tv.size(); i++) vg_idx[cur[tv[i]]++] = c->vg_tet0 + (int)i;
-  }
-
-  UP(cf_blk, cfblk); UP(hg_info, hinfo); UP(hg_v, hv); UP(hg_blk, hgblk);
-  if (c->n_cgblk > 0) { UP(cg_base, cg_base); UP(cg_ptr, cg_ptr); UP(cg_ent, cg_ent); }
-  UP(vg_ptr, vg_ptr); if (!vg_idx.empty()) UP(vg_idx, vg_idx);
-  {   // slot of block (r, c) -> address of the transposed block (c, r) (k_zfrozen_gather); -1 on the padding of a slice
-    std::vector<int> trans((size_t)P.n_slots, -1);
-    for (int v = 0; v < NV; v++) {
-      const int pr = P.rowpos[v], sl = pr >> 6, lane = pr & 63;
-      for (int k = 0; k < (int)P.rows[v].size(); k++) trans[(size_t)P.slice_off[sl] + 64 * (size_t)k + lane] = P.lookup(P.rows[v][k], v);
-    }
-    UP(trans, trans);
-  }
-  UP(d_el, c->h_el); UP(tet_v, tv); UP(tet_el, tel); UP(tet_blk, tetblk); UP(tet_B, tB); UP(tet_W, tW);
-  UP(diag_blk, dblk); UP(rowpos, P.rowpos); UP(perm, P.perm); UP(slice_off, P.slice_off); UP(slice_len, P.slice_len); UP(colidx, P.colidx);
-  UP(diag_perm, P.diag_perm);
+  c->n_slices = P.n_slices; c->n_slots = P.n_slots; c->nnzb = T.nnzb;
+  c->n_cgblk = T.n_cgblk; c->n_cgblk_cloth = T.n_cgblk_cloth;
+  c->vg_hinge0 = T.vg_hinge0; c->vg_tet0 = T.vg_tet0; c->vg_ns = T.vg_ns;
   c->h_mass.assign(d->mass_host, d->mass_host + NV);
-  std::vector<double> grav(d->gravity_host, d->gravity_host + 3 * (size_t)NV), fext(3 * (size_t)NV, 0.0);
-  UP(mass, c->h_mass); UP(grav, grav); UP(fext, fext);
   c->h_frozen.assign(d->frozen_host, d->frozen_host + 3 * (size_t)NV);
-  if (upload_frozen(c)) { delete c; return -1; }
-#undef UP
+  const std::vector<double> grav(d->gravity_host, d->gravity_host + 3 * (size_t)NV), fext(3 * (size_t)NV, 0.0);
+
+  // ---- uploads (a failed one has set the error)
+  if (c->d_cloth.upload(c->h_cloth) || c->cf_f2v.upload(T.f2v) || c->cf_cf.upload(T.cf) || c->cf_cp.upload(T.cp) || c->cf_cloth.upload(T.cid) || c->cf_V.upload(T.V) ||
+      c->cf_li.upload(T.li) || c->cf_order.upload(T.forder) || c->cf_blk.upload(T.cfblk) || c->hg_info.upload(T.hinfo) || c->hg_v.upload(T.hv) || c->hg_blk.upload(T.hgblk)) return -1;
+  if (c->n_cgblk > 0 && (c->cg_base.upload(T.cg_base) || c->cg_ptr.upload(T.cg_ptr) || c->cg_ent.upload(T.cg_ent))) return -1;
+  if (c->vg_ptr.upload(T.vg_ptr) || (!T.vg_idx.empty() && c->vg_idx.upload(T.vg_idx)) || c->trans.upload(T.trans)) return -1;
+  if (c->d_el.upload(c->h_el) || c->tet_v.upload(T.tv) || c->tet_el.upload(T.tel) || c->tet_blk.upload(T.tetblk) || c->tet_B.upload(T.tB) || c->tet_W.upload(T.tW)) return -1;
+  if (c->diag_blk.upload(T.dblk) || c->rowpos.upload(P.rowpos) || c->perm.upload(P.perm) || c->slice_off.upload(P.slice_off) || c->slice_len.upload(P.slice_len) ||
+      c->colidx.upload(P.colidx) || c->diag_perm.upload(P.diag_perm)) return -1;
+  if (c->mass.upload(c->h_mass) || c->grav.upload(grav) || c->fext.upload(fext) || upload_frozen(c)) return -1;
+
+  // ---- allocations
   int rc = 0;
   rc |= c->norm_dir.alloc((size_t)std::max(c->n_cface, 1) * 3);
   // (the element records of the gather assembly -- 81 doubles per face, 65 MB at 100k triangles -- are allocated at the first deterministic assembly)
@@ -374,26 +162,22 @@ extern "C" int tsl_ctx_create(const tsl_scene_desc* d, tsl_ctx** out) {
   rc |= c->F.alloc(n3); rc |= c->pdir.alloc(n3); rc |= c->x1.alloc(n3);
   rc |= c->scal.alloc(1);
   rc |= c->part_pAp.alloc((size_t)P.n_slices + (size_t)(c->max_n_constraints + 63) / 64 + 8); rc |= c->part_rz.alloc((size_t)NV / 256 + 8 + 1024); rc |= c->part_rr.alloc((size_t)NV / 256 + 8 + 1024);
-  if (rc) { delete c; return -1; }
-  if (hipHostMalloc((void**)&c->h_scal, sizeof(SolverScalars) > sizeof(CgScal) ? sizeof(SolverScalars) : sizeof(CgScal)) != hipSuccess) { delete c; return tsl_fail("hipHostMalloc failed"); }
-  if (hipHostMalloc((void**)&c->h_scal2, 2 * sizeof(SolverScalars)) != hipSuccess) { delete c; return tsl_fail("hipHostMalloc failed"); }
-  for (int i = 0; i < 2; i++)
-    if (hipEventCreateWithFlags(&c->rb_event[i], hipEventDisableTiming) != hipSuccess) { delete c; return tsl_fail("hipEventCreate failed"); }
-  if (hipStreamCreateWithFlags(&c->side, hipStreamNonBlocking) != hipSuccess || hipStreamCreateWithFlags(&c->side2, hipStreamNonBlocking) != hipSuccess ||
-      hipEventCreateWithFlags(&c->ev_join2, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&c->ev_fork0, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&c->ev_g2, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&c->ev_hh, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&c->ev_gf, hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming) != hipSuccess) { delete c; return tsl_fail("side stream / event creation failed"); }
+  if (rc) return -1;
+  if (hipHostMalloc((void**)&c->h_scal, sizeof(SolverScalars) > sizeof(CgScal) ? sizeof(SolverScalars) : sizeof(CgScal)) != hipSuccess ||
+      hipHostMalloc((void**)&c->h_scal2, 2 * sizeof(SolverScalars)) != hipSuccess) return tsl_fail("hipHostMalloc failed");
+  if (no_event(&c->rb_event[0]) || no_event(&c->rb_event[1])) return tsl_fail("hipEventCreate failed");
+  if (no_stream(&c->side) || no_stream(&c->side2) || no_event(&c->ev_join2) || no_event(&c->ev_fork) || no_event(&c->ev_fork0) || no_event(&c->ev_g2) || no_event(&c->ev_hh) ||
+      no_event(&c->ev_gf) || no_event(&c->ev_join)) return tsl_fail("side stream / event creation failed");
   c->vals.zero(); c->vals_full.zero(); c->scal.zero(); c->part_rz.zero(); c->part_rr.zero();
 
-  // ---- contact tables
+  // ---- contact tables, multigrid hierarchy, dense body blocks
   c->n_body = d->n_body; c->n_pair = d->n_pair;
   if (d->n_body > 0) c->h_bodies.assign(d->bodies, d->bodies + d->n_body);
   if (d->n_pair > 0) c->h_pairs.assign(d->pairs, d->pairs + d->n_pair);
-  if (contact_alloc(c, d)) { delete c; return -1; }
-  if (mg_build(c, d)) { delete c; return -1; }
-  if (body_dense_setup(c)) { delete c; return -1; }
+  if (contact_alloc(c, d) || mg_build(c, d) || body_dense_setup(c)) return -1;
   (void)hipDeviceSynchronize();
   (void)hipGetDevice(&c->ds.device);
-  *out = c;
+  *out = owner.release();
   return 0;
 }
 
@@ -403,33 +187,7 @@ extern "C" void tsl_ctx_destroy(tsl_ctx* c) {
   if (c->group) group_unregister_and_destroy(c->group);   // (a member that goes takes the group with it: the others get buffers of their own again)
   (void)hipDeviceSynchronize();
   ds_flow_token_release(c->ds);   // (after the last launch of the context has ended)
-  if (c->h_scal) (void)hipHostFree(c->h_scal);
-  if (c->h_scal2) (void)hipHostFree(c->h_scal2);
-  for (int i = 0; i < 2; i++) if (c->rb_event[i]) (void)hipEventDestroy(c->rb_event[i]);
-  if (c->pcg_graph) (void)hipGraphExecDestroy(c->pcg_graph);
-  if (c->mr_graph) (void)hipGraphExecDestroy(c->mr_graph);
-  if (c->ev_in) (void)hipEventDestroy(c->ev_in);
-  if (c->ev_out) (void)hipEventDestroy(c->ev_out);
-  for (int k = 0; k < DS_NSIDE; k++) if (c->ds.fstream[k]) { (void)hipStreamSynchronize(c->ds.fstream[k]); (void)hipEventDestroy(c->ds.ev_fjoin[k]); (void)hipStreamDestroy(c->ds.fstream[k]); }
-  if (c->ds.ev_ffork) (void)hipEventDestroy(c->ds.ev_ffork);
-  for (int k = 0; k < 5; k++) if (c->ds.ev_la[k]) (void)hipEventDestroy(c->ds.ev_la[k]);
-  if (c->ds.lastream) { (void)hipStreamSynchronize(c->ds.lastream); (void)hipStreamDestroy(c->ds.lastream); }
-  if (c->ds.h_anorm) (void)hipHostFree(c->ds.h_anorm);
-  if (c->ds.pin) (void)hipHostFree(c->ds.pin);
-  if (c->h_ir) (void)hipHostFree(c->h_ir);
-  if (c->ds.zstream) { (void)hipStreamSynchronize(c->ds.zstream); (void)hipEventDestroy(c->ds.ev_zfork); (void)hipEventDestroy(c->ds.ev_zero); (void)hipStreamDestroy(c->ds.zstream); }
-  if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
-  if (c->ev_fork0) (void)hipEventDestroy(c->ev_fork0);
-  if (c->ev_g2) (void)hipEventDestroy(c->ev_g2);
-  if (c->ev_hh) (void)hipEventDestroy(c->ev_hh);
-  if (c->ev_gf) (void)hipEventDestroy(c->ev_gf);
-  if (c->ev_join) (void)hipEventDestroy(c->ev_join);
-  if (c->side) (void)hipStreamDestroy(c->side);
-  if (c->ev_join2) (void)hipEventDestroy(c->ev_join2);
-  if (c->side2) (void)hipStreamDestroy(c->side2);
-  if (c->stream) (void)hipStreamDestroy(c->stream);
-  for (auto& e : c->ev_pool) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
-  delete c;
+  delete c;   // (~tsl_ctx, ~DirectSolver: whatever the context owns)
 }
 
 extern "C" int tsl_set_stream(tsl_ctx* c, void* s) { c->user_stream = (hipStream_t)s; return 0; }
@@ -468,6 +226,37 @@ static int stvk_set(tsl_ctx* c, const char* key, long idx, const std::string& f,
   c->n_stvk = 0;
   for (int i = 0; i < n_cloth; i++) c->n_stvk += c->h_stvk[4 * i] != 0.0;
   HIP_OK(hipMemcpy(c->d_stvk.p, c->h_stvk.data(), c->h_stvk.size() * sizeof(double), hipMemcpyHostToDevice));
+  return 0;
+}
+
+// "self_contact<body>" (geometry_self.projection_query(self_contact=[...])), "cloth<i>.Kb|Kl|Ka|k_angle|membrane|stvk_mu|stvk_lam",
+// "elastic<i>.mu|lam|alpha" (0-d field writes after the context exists): one parser (param_keys.hpp), one table from field to member per family
+static int set_indexed_param(tsl_ctx* c, const char* key, double v) {
+  static const std::pair<const char*, double ClothDev::*> cloth_fields[] = {{"Kb", &ClothDev::Kb}, {"Kl", &ClothDev::Kl}, {"Ka", &ClothDev::Ka}, {"k_angle", &ClothDev::k_angle}};
+  static const std::pair<const char*, double ElasticDev::*> elastic_fields[] = {{"mu", &ElasticDev::mu}, {"lam", &ElasticDev::lam}, {"alpha", &ElasticDev::alpha}};
+  IndexedKey ik;
+  if (parse_indexed_key(key, ik)) return tsl_fail("tsl_set_param: bad index in %s", key);
+  const long idx = ik.index;
+  const std::string& f = ik.field;
+  if (ik.family == IndexedKey::SelfContact) {
+    if (idx < 0 || idx >= c->n_body) return tsl_fail("tsl_set_param: bad body index in %s", key);
+    if ((long)c->self_contact.size() < c->n_body) c->self_contact.assign(c->n_body, 0);
+    c->self_contact[idx] = (v != 0.0);
+  } else if (ik.family == IndexedKey::Cloth) {
+    if (idx < 0 || idx >= (long)c->h_cloth.size()) return tsl_fail("tsl_set_param: bad cloth index in %s", key);
+    if (f == "membrane" || f == "stvk_mu" || f == "stvk_lam") return stvk_set(c, key, idx, f, v);
+    const auto* m = field_find(cloth_fields, f);
+    if (!m) return tsl_fail("tsl_set_param: unknown key %s", key);
+    c->h_cloth[idx].*(*m) = v;
+    HIP_OK(hipMemcpy(c->d_cloth.p, c->h_cloth.data(), c->h_cloth.size() * sizeof(ClothDev), hipMemcpyHostToDevice));
+  } else if (ik.family == IndexedKey::Elastic) {
+    if (idx < 0 || idx >= (long)c->h_el.size()) return tsl_fail("tsl_set_param: bad elastic index in %s", key);
+    const auto* m = field_find(elastic_fields, f);
+    if (!m) return tsl_fail("tsl_set_param: unknown key %s", key);
+    c->h_el[idx].*(*m) = v;
+    HIP_OK(hipMemcpy(c->d_el.p, c->h_el.data(), c->h_el.size() * sizeof(ElasticDev), hipMemcpyHostToDevice));
+    c->bd_valid = false;
+  } else return tsl_fail("tsl_set_param: unknown key %s", key);
   return 0;
 }
 
@@ -523,39 +312,9 @@ extern "C" int tsl_set_param(tsl_ctx* c, const char* key, double v) {
   else if (k == "gmres_m") c->gmres_m = (int)v;
   else if (k == "body_inv") { c->bd_enable = (int)v; c->bd_valid = false; }
   else if (k == "mg") c->mg_enable = (int)v;
-  else if (k.rfind("self_contact", 0) == 0 && k.size() > 12) {   // "self_contact<body>" (geometry_self.projection_query(self_contact=[...]))
-    char* endp = nullptr;
-    const long b = strtol(k.c_str() + 12, &endp, 10);
-    if (*endp != 0 || b < 0 || b >= c->n_body) return tsl_fail("tsl_set_param: bad body index in %s", key);
-    if ((long)c->self_contact.size() < c->n_body) c->self_contact.assign(c->n_body, 0);
-    c->self_contact[b] = (v != 0.0);
-  }
   else if (k == "mg_coarse_exact") { c->mg_coarse_exact = (int)v; c->mg_ops_valid = false; }   // (the hierarchy may end at another level)
   else if (k == "mg_dense_nodes") { c->mg_dense_auto = v < 0; if (v >= 0) c->mg_dense_nodes = (int)v; c->mg_ops_valid = false; }
-  else if ((k.rfind("cloth", 0) == 0 || k.rfind("elastic", 0) == 0) && k.find('.') != std::string::npos) {
-    // "cloth<i>.Kb|Kl|Ka|k_angle|membrane|stvk_mu|stvk_lam", "elastic<i>.mu|lam|alpha" (0-d field writes after the context exists)
-    const bool is_cloth = k[0] == 'c';
-    const size_t p0 = is_cloth ? 5 : 7, dot = k.find('.');
-    char* endp = nullptr;
-    const long idx = strtol(k.c_str() + p0, &endp, 10);
-    if (endp != k.c_str() + dot || dot == p0) return tsl_fail("tsl_set_param: bad index in %s", key);
-    const std::string f = k.substr(dot + 1);
-    if (is_cloth) {
-      if (idx < 0 || idx >= (long)c->h_cloth.size()) return tsl_fail("tsl_set_param: bad cloth index in %s", key);
-      ClothDev& cd = c->h_cloth[idx];
-      if (f == "membrane" || f == "stvk_mu" || f == "stvk_lam") return stvk_set(c, key, idx, f, v);
-      if (f == "Kb") cd.Kb = v; else if (f == "Kl") cd.Kl = v; else if (f == "Ka") cd.Ka = v; else if (f == "k_angle") cd.k_angle = v;
-      else return tsl_fail("tsl_set_param: unknown key %s", key);
-      HIP_OK(hipMemcpy(c->d_cloth.p, c->h_cloth.data(), c->h_cloth.size() * sizeof(ClothDev), hipMemcpyHostToDevice));
-    } else {
-      if (idx < 0 || idx >= (long)c->h_el.size()) return tsl_fail("tsl_set_param: bad elastic index in %s", key);
-      ElasticDev& ed = c->h_el[idx];
-      if (f == "mu") ed.mu = v; else if (f == "lam") ed.lam = v; else if (f == "alpha") ed.alpha = v;
-      else return tsl_fail("tsl_set_param: unknown key %s", key);
-      HIP_OK(hipMemcpy(c->d_el.p, c->h_el.data(), c->h_el.size() * sizeof(ElasticDev), hipMemcpyHostToDevice));
-      c->bd_valid = false;
-    }
-  } else return tsl_fail("tsl_set_param: unknown key %s", key);
+  else return set_indexed_param(c, key, v);
   return 0;
 }
 
@@ -834,6 +593,28 @@ static void cloth_grad_face_launch(tsl_ctx* c, hipStream_t s, const ClothArgs& C
   if (c->n_stvk > 0) hipLaunchKernelGGL(k_cloth_grad_face<true>, dim3(nblk(c->n_cface, 256)), dim3(256), 0, s, CA, pos, stvk_args(c));
   else hipLaunchKernelGGL(k_cloth_grad_face<false>, dim3(nblk(c->n_cface, 256)), dim3(256), 0, s, CA, pos, stvk_args(c));
 }
+// The gathers of the element staging slots and records, and the checks around them: each spelled once, for every assembly, read-out and reverse step
+static int ensure_vg_stage(tsl_ctx* c) {   // the staging slots of the element gradients exist (allocated at the first use)
+  const size_t n = 3 * (size_t)std::max(c->vg_ns, 1);
+  if (c->vg_stage.n < n && c->vg_stage.alloc(n)) return tsl_fail("out of device memory (gradient staging)");
+  return 0;
+}
+// out[v] += the three-vectors of v's staging slots in [lo, hi), ascending; stage: where slot 0 of the staging array is (or would be)
+static void vertex_gather_launch(tsl_ctx* c, hipStream_t s, const double* stage, int lo, int hi, double* out) {
+  hipLaunchKernelGGL(k_vertex_gather, dim3(nblk(c->NV, 256)), dim3(256), 0, s, c->NV, (const int*)c->vg_ptr.p, (const int*)c->vg_idx.p, stage, lo, hi, out);
+}
+// the element records summed into the matrix blocks [first_block, first_block + n_blocks) of the gather lists (cloth blocks first, body blocks behind them)
+static void cloth_gather_launch(tsl_ctx* c, hipStream_t s, int first_block, int n_blocks) {
+  hipLaunchKernelGGL(k_cloth_gather, dim3(nblk(n_blocks, CG_BPW)), dim3(256), 0, s, n_blocks, c->cg_base.p + first_block, c->cg_ptr.p + first_block, (const unsigned*)c->cg_ent.p,
+                     c->n_hinge, c->n_cface, (const double*)c->cg_hrec.p, (const double*)c->cg_frec.p, (const double*)c->cg_trec.p, c->vals_full.p);
+}
+// The tail of both assembly schedules.  The block-Jacobi inverse belongs to the iterative hierarchy: a solve that goes to the factorisation never reads it
+// (9 us + one dependent launch per Newton iteration of the direct path); solve_perm forms it when the hierarchy runs after all (block_jacobi_ensure)
+static int block_jacobi_after_assembly(tsl_ctx* c) {
+  if (c->pc_frozen) return 0;
+  if (direct_takes_solve(c)) { c->dinv_valid = false; return 0; }
+  return block_jacobi_refresh(c);
+}
 static void cloth_hess_face_launch(tsl_ctx* c, hipStream_t s, const ClothArgs& CA, const double* pos, const double* ref, int spd) {
   const dim3 g(nblk(c->n_cface, 128)), b(128);
   const StvkArgs S = stvk_args(c);
@@ -885,21 +666,14 @@ static int assemble_enqueue(tsl_ctx* c, const double* pos, const double* prev, c
     cloth_hess_face_launch(c, s, CA, pos, ref, spd);
   }
   if (c->n_hinge) hipLaunchKernelGGL(k_cloth_hess_hinge, dim3(nblk(c->n_hinge, 256)), dim3(256), 0, s, CA, pos, c->cg_hrec.p);
-  if (c->n_cgblk_cloth > 0)
-    hipLaunchKernelGGL(k_cloth_gather, dim3(nblk(c->n_cgblk_cloth, CG_BPW)), dim3(256), 0, s, c->n_cgblk_cloth, c->cg_base.p, c->cg_ptr.p, (const unsigned*)c->cg_ent.p, c->n_hinge, c->n_cface,
-                       (const double*)c->cg_hrec.p, (const double*)c->cg_frec.p, (const double*)c->cg_trec.p, c->vals_full.p);
+  if (c->n_cgblk_cloth > 0) cloth_gather_launch(c, s, 0, c->n_cgblk_cloth);
   if (grad) {
-    hipLaunchKernelGGL(k_vertex_gather, dim3(nblk(NV, 256)), dim3(256), 0, s, NV, (const int*)c->vg_ptr.p, (const int*)c->vg_idx.p, (const double*)c->vg_stage.p, 0, c->vg_ns, grad);
+    vertex_gather_launch(c, s, c->vg_stage.p, 0, c->vg_ns, grad);
     hipLaunchKernelGGL(k_mask_vec, dim3(gsz(3 * (size_t)NV)), dim3(256), 0, s, 3 * (size_t)NV, c->frozen.p, grad);
   }
   hipLaunchKernelGGL(k_mask_matrix, dim3(c->n_slices), dim3(256), 0, s, c->n_slices, c->slice_off.p, c->slice_len.p, c->colidx.p, c->fzmask.p, c->mdt2.p,
                      c->vals_full.p, c->vals.p, NV);
-  if (!c->pc_frozen) {
-    // the block-Jacobi inverse belongs to the iterative hierarchy: a solve that goes to the factorisation never reads it (9 us + one dependent launch per
-    // Newton iteration of the direct path); solve_perm forms it when the hierarchy runs after all (block_jacobi_ensure)
-    if (direct_takes_solve(c)) c->dinv_valid = false;
-    else TSL_TRY(block_jacobi_refresh(c));
-  }
+  TSL_TRY(block_jacobi_after_assembly(c));
   HIP_OK(hipGetLastError());
   return 0;
 }
@@ -968,8 +742,7 @@ static int assemble_enqueue_early(tsl_ctx* c, const double* pos, const double* p
   if (c->n_hinge && !hh_side) hipLaunchKernelGGL(k_cloth_hess_hinge, dim3(nblk(c->n_hinge, 256)), dim3(256), 0, s, CA, pos, c->cg_hrec.p);
   const int nt_blk = c->n_cgblk - c->n_cgblk_cloth;
   if (c->n_tet && nt_blk > 0)   // the element records of the bodies -> their matrix blocks (the blocks of the bodies and of the cloth are disjoint)
-    hipLaunchKernelGGL(k_cloth_gather, dim3(nblk(nt_blk, CG_BPW)), dim3(256), 0, stt, nt_blk, c->cg_base.p + c->n_cgblk_cloth, c->cg_ptr.p + c->n_cgblk_cloth, (const unsigned*)c->cg_ent.p,
-                       c->n_hinge, c->n_cface, (const double*)c->cg_hrec.p, (const double*)c->cg_frec.p, (const double*)c->cg_trec.p, c->vals_full.p);
+    cloth_gather_launch(c, stt, c->n_cgblk_cloth, nt_blk);
   HIP_OK(hipEventRecord(c->ev_join2, stt));   // body blocks
   // contact stream, second part: hinge gradients (staging slots); the face gradients behind the body blocks on the element stream
   if (grad) {
@@ -982,9 +755,7 @@ static int assemble_enqueue_early(tsl_ctx* c, const double* pos, const double* p
   }
   // engine stream: cloth blocks (behind the hinge records), then the matrix tail
   if (hh_side && c->n_hinge) HIP_OK(hipStreamWaitEvent(s, c->ev_hh, 0));
-  if (gather && c->n_cgblk_cloth > 0)
-    hipLaunchKernelGGL(k_cloth_gather, dim3(nblk(c->n_cgblk_cloth, CG_BPW)), dim3(256), 0, s, c->n_cgblk_cloth, c->cg_base.p, c->cg_ptr.p, (const unsigned*)c->cg_ent.p, c->n_hinge, c->n_cface,
-                       (const double*)c->cg_hrec.p, (const double*)c->cg_frec.p, (const double*)c->cg_trec.p, c->vals_full.p);
+  if (gather && c->n_cgblk_cloth > 0) cloth_gather_launch(c, s, 0, c->n_cgblk_cloth);
   HIP_OK(hipStreamWaitEvent(s, c->ev_join2, 0));
   hipLaunchKernelGGL(k_mask_matrix, dim3(c->n_slices), dim3(256), 0, s, c->n_slices, c->slice_off.p, c->slice_len.p, c->colidx.p, c->fzmask.p, c->mdt2.p,
                      c->vals_full.p, c->vals.p, NV);
@@ -992,19 +763,14 @@ static int assemble_enqueue_early(tsl_ctx* c, const double* pos, const double* p
   if (grad) {
     if (fork_t && c->n_tet) HIP_OK(hipStreamWaitEvent(st, c->ev_g2, 0));
     if (hh_side && c->n_cface) HIP_OK(hipStreamWaitEvent(st, c->ev_gf, 0));
-    hipLaunchKernelGGL(k_vertex_gather, dim3(nblk(NV, 256)), dim3(256), 0, st, NV, (const int*)c->vg_ptr.p, (const int*)c->vg_idx.p, (const double*)c->vg_stage.p, 0, c->vg_ns, grad);
+    vertex_gather_launch(c, st, c->vg_stage.p, 0, c->vg_ns, grad);
     if (c->nc > 0) hipLaunchKernelGGL(k_contact_row_gather, dim3(nblk((long)NV * 64, 256)), dim3(256), 0, st, NV, (const int*)c->rowpos.p, (const int*)c->cr_ptr.p, (const int*)c->cr_ent.p,
                                       (const double*)c->c_G.p, grad);
     hipLaunchKernelGGL(k_mask_vec, dim3(gsz(3 * (size_t)NV)), dim3(256), 0, st, 3 * (size_t)NV, c->frozen.p, grad);
   }
   HIP_OK(hipEventRecord(c->ev_join, st));
   HIP_OK(hipStreamWaitEvent(s, c->ev_join, 0));   // (contact diagonal for the block-Jacobi inverse, the gradient for whatever follows)
-  if (!c->pc_frozen) {
-    // the block-Jacobi inverse belongs to the iterative hierarchy: a solve that goes to the factorisation never reads it (9 us + one dependent launch per
-    // Newton iteration of the direct path); solve_perm forms it when the hierarchy runs after all (block_jacobi_ensure)
-    if (direct_takes_solve(c)) c->dinv_valid = false;
-    else TSL_TRY(block_jacobi_refresh(c));
-  }
+  TSL_TRY(block_jacobi_after_assembly(c));
   HIP_OK(hipGetLastError());
   return 0;
 }
@@ -1017,7 +783,7 @@ static int assemble_enqueue_early(tsl_ctx* c, const double* pos, const double* p
 static int assemble(tsl_ctx* c, const double* pos, const double* prev, const double* vel, const double* ref, int spd, double* grad) {
   hipStream_t s = c->stream;
   // ---- allocations the launches rely on (staging slots of the gradient, element records of the matrix)
-  if (c->vg_stage.n < 3 * (size_t)std::max(c->vg_ns, 1)) { if (c->vg_stage.alloc(3 * (size_t)std::max(c->vg_ns, 1))) return tsl_fail("out of device memory (gradient staging)"); }
+  TSL_TRY(ensure_vg_stage(c));
   if (c->n_tet > 0 && c->cg_trec.n < 144 * (size_t)c->n_tet) { if (c->cg_trec.alloc(144 * (size_t)c->n_tet)) return tsl_fail("out of device memory (element records)"); }
   if (grad && c->nc > 0 && c->c_G.n < 12 * (size_t)c->max_n_constraints) { if (c->c_G.alloc(12 * (size_t)c->max_n_constraints)) return -1; }
   if (c->n_cgblk > 0 && c->n_cface > 0 && c->cg_frec.n == 0) {
@@ -2307,10 +2073,10 @@ extern "C" int tsl_elastic_force(tsl_ctx* c, const double* pos, double* force) {
   if (c->n_tet) {
     TetArgs TA = tet_args(c);
     // element gradients staged and summed per vertex in a fixed order (as in the assembly)
-    if (c->vg_stage.n < 3 * (size_t)std::max(c->vg_ns, 1)) { if (c->vg_stage.alloc(3 * (size_t)std::max(c->vg_ns, 1))) return tsl_fail("out of device memory (gradient staging)"); }
+    TSL_TRY(ensure_vg_stage(c));
     TA.gstage = c->vg_stage.p + 3 * (size_t)c->vg_tet0;
     hipLaunchKernelGGL(k_tet_grad, dim3(nblk(c->n_tet, 256)), dim3(256), 0, s, TA, pos);
-    hipLaunchKernelGGL(k_vertex_gather, dim3(nblk(c->NV, 256)), dim3(256), 0, s, c->NV, (const int*)c->vg_ptr.p, (const int*)c->vg_idx.p, (const double*)c->vg_stage.p, c->vg_tet0, c->vg_ns, force);
+    vertex_gather_launch(c, s, c->vg_stage.p, c->vg_tet0, c->vg_ns, force);
     for (const ElasticDev& e : c->h_el)
       hipLaunchKernelGGL(k_elastic_force_finish, dim3(nblk(e.n_verts, 256)), dim3(256), 0, s, vert_args(c), e.v_offset, e.v_offset + e.n_verts, force);
   }
@@ -2361,7 +2127,7 @@ extern "C" int tsl_param_grad(tsl_ctx* c, const double* pos, const double* ref, 
   HIP_OK(hipMemsetAsync(acc, 0, 2 * sizeof(double), s));
   // hinge / tet contributions staged per element and summed per vertex in a fixed order, the dot products joined from per-block partials -- two runs of a
   // system-identification sweep give the same bits
-  if (c->vg_stage.n < 3 * (size_t)std::max(c->vg_ns, 1)) { if (c->vg_stage.alloc(3 * (size_t)std::max(c->vg_ns, 1))) return tsl_fail("out of device memory (gradient staging)"); }
+  TSL_TRY(ensure_vg_stage(c));
   // d_kb = -(bending gradient) / Kb per cloth
   if (c->n_hinge) {
     HIP_OK(hipMemsetAsync(tmp, 0, n3 * sizeof(double), s));
@@ -2369,7 +2135,7 @@ extern "C" int tsl_param_grad(tsl_ctx* c, const double* pos, const double* ref, 
     ClothArgs CA = cloth_args(c);
     CA.gstage = c->vg_stage.p;
     hipLaunchKernelGGL(k_cloth_grad_hinge, dim3(nblk(c->n_hinge, 256)), dim3(256), 0, s, CA, pos, ref);
-    hipLaunchKernelGGL(k_vertex_gather, dim3(nblk(NV, 256)), dim3(256), 0, s, NV, (const int*)c->vg_ptr.p, (const int*)c->vg_idx.p, (const double*)c->vg_stage.p, c->vg_hinge0, c->vg_tet0, tmp);
+    vertex_gather_launch(c, s, c->vg_stage.p, c->vg_hinge0, c->vg_tet0, tmp);
     for (const ClothDev& cd : c->h_cloth)
       hipLaunchKernelGGL(k_dot_free, dim3(DOT_BLOCKS), dim3(256), 0, s, 3 * (size_t)cd.v_offset, 3 * (size_t)(cd.v_offset + cd.NV), c->pdir.p, tmp, c->frozen.p, -1.0 / cd.Kb, acc, DOT_SCRATCH(c));
   }
@@ -2381,9 +2147,8 @@ extern "C" int tsl_param_grad(tsl_ctx* c, const double* pos, const double* ref, 
     double *stA = c->vg_stage.p + 3 * (size_t)c->vg_tet0, *stB = c->vg_stage2.p;
     hipLaunchKernelGGL(k_tet_deri_mu, dim3(nblk(c->n_tet, 64)), dim3(64), 0, s, tet_args(c), pos, stA, stB);
     {   // (the second gather reads the same slot numbers from a staging array that holds the tet slots only)
-      hipLaunchKernelGGL(k_vertex_gather, dim3(nblk(NV, 256)), dim3(256), 0, s, NV, (const int*)c->vg_ptr.p, (const int*)c->vg_idx.p, (const double*)c->vg_stage.p, c->vg_tet0, c->vg_ns, tmp);
-      hipLaunchKernelGGL(k_vertex_gather, dim3(nblk(NV, 256)), dim3(256), 0, s, NV, (const int*)c->vg_ptr.p, (const int*)c->vg_idx.p, (const double*)c->vg_stage2.p - 3 * (size_t)c->vg_tet0, c->vg_tet0, c->vg_ns,
-                         c->dmu_accum.p);
+      vertex_gather_launch(c, s, c->vg_stage.p, c->vg_tet0, c->vg_ns, tmp);
+      vertex_gather_launch(c, s, c->vg_stage2.p - 3 * (size_t)c->vg_tet0, c->vg_tet0, c->vg_ns, c->dmu_accum.p);
     }
     hipLaunchKernelGGL(k_dot_free, dim3(DOT_BLOCKS), dim3(256), 0, s, (size_t)0, n3, c->pdir.p, tmp, c->frozen.p, 1.0, acc + 1, DOT_SCRATCH(c));
     hipLaunchKernelGGL(k_dot_free, dim3(DOT_BLOCKS), dim3(256), 0, s, (size_t)0, n3, c->pdir.p, c->dmu_accum.p, c->frozen.p, 1.0, acc + 1, DOT_SCRATCH(c));
@@ -2421,26 +2186,16 @@ extern "C" int tsl_param_grad_keys(tsl_ctx* c, const double* pos, const double* 
     else if (k == "mu_cloth_elastic") { cls = 3; row = 1; }
     else if (k == "mu_cloth_cloth") { cls = 3; row = 2; }
     else if (k == "k_handle") { cls = 5; row = 0; }
-    else if ((k.rfind("cloth", 0) == 0 || k.rfind("elastic", 0) == 0) && k.find('.') != std::string::npos) {
-      const bool is_cloth = k[0] == 'c';
-      const size_t p0 = is_cloth ? 5 : 7, dot = k.find('.');
-      char* endp = nullptr;
-      const long idx = strtol(k.c_str() + p0, &endp, 10);
-      // (an index is a plain decimal number: no sign other than a minus, no blanks -- "cloth+1.Kl", "cloth 1.Kl" are not keys)
-      const char c0 = k[p0];
-      if (endp != k.c_str() + dot || dot == p0 || !(isdigit((unsigned char)c0) || c0 == '-')) return tsl_fail("tsl_param_grad_keys: bad index in %s", keys[j]);
-      const std::string f = k.substr(dot + 1);
-      if (is_cloth) {
-        if (f == "Kl" || f == "Ka") { cls = 0; row = f == "Kl" ? 0 : 1; }
-        else if (f == "Kb") { cls = 1; row = 0; }
-        else if (f == "stvk_mu" || f == "stvk_lam") { cls = 4; row = f == "stvk_mu" ? 0 : 1; }
-        if (cls >= 0 && (idx < 0 || idx >= n_cloth)) return tsl_fail("tsl_param_grad_keys: bad cloth index in %s (%d cloths)", keys[j], n_cloth);
-        if (cls == 0 || cls == 4) row += 2 * (int)idx; else if (cls == 1) row = (int)idx;
-      } else {
-        if (f == "mu" || f == "lam") { cls = 2; row = f == "mu" ? 0 : 1; }
-        if (cls >= 0 && (idx < 0 || idx >= n_el)) return tsl_fail("tsl_param_grad_keys: bad elastic index in %s (%d bodies)", keys[j], n_el);
-        if (cls == 2) row += 2 * (int)idx;
-      }
+    else {   // "cloth<i>.<field>", "elastic<i>.<field>": field -> (class, row among the rows of cloth / body i)
+      static const std::pair<const char*, std::array<int, 2>> cloth_rows[] = {{"Kl", {0, 0}}, {"Ka", {0, 1}}, {"Kb", {1, 0}}, {"stvk_mu", {4, 0}}, {"stvk_lam", {4, 1}}};
+      static const std::pair<const char*, std::array<int, 2>> elastic_rows[] = {{"mu", {2, 0}}, {"lam", {2, 1}}};
+      IndexedKey ik;
+      if (parse_indexed_key(keys[j], ik) && ik.family != IndexedKey::SelfContact) return tsl_fail("tsl_param_grad_keys: bad index in %s", keys[j]);
+      const bool is_cloth = ik.family == IndexedKey::Cloth;
+      const std::array<int, 2>* cr = is_cloth ? field_find(cloth_rows, ik.field) : (ik.family == IndexedKey::Elastic ? field_find(elastic_rows, ik.field) : nullptr);
+      if (cr && is_cloth && (ik.index < 0 || ik.index >= n_cloth)) return tsl_fail("tsl_param_grad_keys: bad cloth index in %s (%d cloths)", keys[j], n_cloth);
+      if (cr && !is_cloth && (ik.index < 0 || ik.index >= n_el)) return tsl_fail("tsl_param_grad_keys: bad elastic index in %s (%d bodies)", keys[j], n_el);
+      if (cr) { cls = (*cr)[0]; row = cls == 1 ? (int)ik.index : (*cr)[1] + 2 * (int)ik.index; }
     }
     if (cls < 0) return tsl_fail("tsl_param_grad_keys: %s is not a differentiated key (supported: %s)", keys[j], supported);
     if (cls == 3) {
@@ -3214,12 +2969,12 @@ static int adjoint_pre(tsl_ctx* c, const AdjArgs& a, double** rhs) {
   if (c->contact_enable) TSL_TRY(tsl_contact_detect(c, x_prev, x_prev, &nc));
   else { c->nc = 0; c->nc_ee = 0; c->ds.cons_checked = false; }
   ClothArgs CA = cloth_args(c);
-  if (c->vg_stage.n < 3 * (size_t)std::max(c->vg_ns, 1)) { if (c->vg_stage.alloc(3 * (size_t)std::max(c->vg_ns, 1))) return tsl_fail("out of device memory (gradient staging)"); }
+  TSL_TRY(ensure_vg_stage(c));
   // pos = x_s, ref_angle = ref_{s-1}: init_folding + ref_angle_backprop_a2ax
   if (c->n_hinge) {
     CA.gstage = c->vg_stage.p;
     hipLaunchKernelGGL(k_adj_a2ax, dim3(nblk(c->n_hinge, 256)), dim3(256), 0, s, CA, x_s, ref_prev, ag_s, ag_prev);
-    hipLaunchKernelGGL(k_vertex_gather, dim3(nblk(NV, 256)), dim3(256), 0, s, NV, (const int*)c->vg_ptr.p, (const int*)c->vg_idx.p, (const double*)c->vg_stage.p, c->vg_hinge0, c->vg_tet0, pg_s);
+    vertex_gather_launch(c, s, c->vg_stage.p, c->vg_hinge0, c->vg_tet0, pg_s);
     CA.gstage = nullptr;
   }
   // preconditioner from the SPD-projected Hessian of the same state (block Jacobi + multigrid hierarchy): the operator
