@@ -170,6 +170,27 @@ int tsl_set_handle_targets(tsl_ctx* ctx, const double* targets_host);
 int tsl_handle_force(tsl_ctx* ctx, const double* pos_dev, double* out_host);
 int tsl_handle_grad(tsl_ctx* ctx, const double* p_dev, double* out_host);
 
+/* Soft handles at barycentric points of faces (no reference counterpart): handle i sits on face faces[i] = (v_0, v_1, v_2) of the scene's global face
+ * table (tsl_scene_desc.faces_host: a cloth face or a surface face of a FEM body) with barycentric coordinates b_i and pulls the point
+ * p_i = sum_a b_a x_{v_a} to its target, E_h = 1/2 k_handle sum_i w_i |p_i - t_i|^2: gradient row v_a: k_handle w_i b_a (p_i - t_i), block (v_a, v_b):
+ * k_handle w_i b_a b_b I_3 -- an outer product times I_3, positive semi-definite as it stands, so every spd mode and "spd_literal" add the same
+ * numbers.  Any number of handles may share a face or a vertex; b = (1, 0, 0) is a vertex handle without the one-per-vertex limit.  The nine blocks
+ * of a face exist in the pattern: the plans of the factorisation and their cache do not depend on the handles.  Frozen dofs follow the mask rule.
+ * One lane per touched vertex (gradient) and per touched block (matrix) adds its entries in a fixed order and writes once: no atomics, the same bits
+ * run to run.  Conventions of tsl_set_handles.
+ *   tsl_set_handles_on_faces: REPLACES the handle list, as tsl_set_handles does: a context holds a vertex list or a face list, either setter drops the
+ *     other kind's list and all frames, and the targets start at zero.  bary_host: n x 3, used as given (not renormalised); weights_host == NULL:
+ *     every weight is 1; n = 0 removes the handles.  Fails, naming the offender, and leaves the previous list in place for a face outside
+ *     [0, tot_NF), a coordinate that is not finite or outside [0, 1], a triple whose sum differs from 1 by more than 1e-9, a negative or non-finite
+ *     weight, a pair of the face's vertices without a block in the pattern (cannot happen for a scene's own faces).
+ *   tsl_handle_points: out_host (n x 3) = the points p_i at the state pos; for a vertex list x_{v_i}.
+ *   Every other handle and frame entry point works on a face list by handle index: tsl_set_handle_targets, tsl_handle_targets, tsl_handle_force
+ *     (k_handle w_i (t_i - p_i), not masked), tsl_handle_grad (component c of row i: k_handle w_i sum_a b_a p_{v_a, c} over the corners whose dof
+ *     (v_a, c) is free), the "k_handle" key (-sum_i w_i sum_a b_a sum_{c free} p_{v_a, c} (p_i - t_i)_c), tsl_set_handle_frames, tsl_set_frame_poses,
+ *     tsl_frame_wrench and tsl_frame_grad (the same six sums over these rows), tsl_energy, tsl_assemble, tsl_step, tsl_adjoint_step, both group steps. */
+int tsl_set_handles_on_faces(tsl_ctx* ctx, const int32_t* faces_host, const double* bary_host, const double* weights_host, int32_t n);
+int tsl_handle_points(tsl_ctx* ctx, const double* pos_dev, double* out_host);
+
 /* Rigid frames for the handles (no reference counterpart): handle i may belong to frame f_i in [0, n_frame) with a local point r_i; f_i = -1 is a
  * free handle with a world target, as above.  Frame j has a pose (c_j, q_j), q = (s, x, y, z) in the convention of quat_to_rotmat
  * (engine/gripper_single.py), and the target of a framed handle is t_i = c_j + R(q_j) r_i.  Frames only rewrite rows of the target buffer: energy,

@@ -129,6 +129,26 @@ class TslContext:
         self.n_handle = len(v)
         self.n_frame = 0   # (the library drops the frames with the handle list)
 
+    def set_handles_on_faces(self, faces, bary, weights=None):
+        """n handles at the barycentric points `bary` (n, 3) of the global face ids `faces` (any number per face or vertex), weights None: all 1; an
+        empty list removes them.  Replaces a vertex list, drops the frames; targets start at zero."""
+        f = _np(faces, np.int32).reshape(-1)
+        b = _np(bary, np.float64).reshape(-1, 3)
+        w = None if weights is None else _np(weights, np.float64).reshape(-1)
+        assert b.shape == (len(f), 3) and (w is None or w.shape == f.shape), (f.shape, b.shape)
+        n = len(f)
+        check(self.L.tsl_set_handles_on_faces(self.h, f.ctypes.data if n else None, b.ctypes.data if n else None,
+                                              None if w is None or not n else w.ctypes.data, n), "tsl_set_handles_on_faces")
+        self.n_handle = n
+        self.n_frame = 0   # (the library drops the frames with the handle list)
+
+    def handle_points(self, pos):
+        """(n, 3) the points the handles act on at the state pos: sum_a b_a x_{v_a} of a face list, x_{v_i} of a vertex list"""
+        self.refresh_stream()
+        out = np.zeros((getattr(self, "n_handle", 0), 3))
+        check(self.L.tsl_handle_points(self.h, _ptr(pos), out.ctypes.data), "tsl_handle_points")
+        return out
+
     def set_handle_targets(self, targets):
         t = _np(targets, np.float64)
         assert t.shape == (getattr(self, "n_handle", 0), 3), t.shape

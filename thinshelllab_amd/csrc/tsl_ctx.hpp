@@ -264,6 +264,13 @@ struct tsl_ctx {
   double k_handle = 0.0;
   DevBuf<int> hd_v;
   DevBuf<double> hd_w, hd_t, hd_out;   // n, n x 3, n x 3 (read-outs of tsl_handle_force / tsl_handle_grad)
+  // handles at barycentric points of faces (tsl_set_handles_on_faces, k_handle_face.hpp): a context holds a vertex list (hd_v) or a face list
+  // (handle_on_faces: hf_fv, hf_b and the gather lists of handle_face_host.hpp); weights, targets, read-outs and frames are shared, by handle index
+  bool handle_on_faces = false;
+  int n_hf_vert = 0, n_hf_blk = 0;   // touched vertices, touched blocks
+  DevBuf<int> hf_fv, hf_vl_v, hf_vl_ptr, hf_vl_ent, hf_bl_addr, hf_bl_ptr, hf_bl_ent;
+  DevBuf<double> hf_b;               // n x 3
+  std::vector<int> h_faces;          // tot_NF x 3, the scene's global face table (host copy)
   // rigid frames of the handles (tsl_set_handle_frames, k_frame.hpp): frame and local point of each handle, the handles of every frame as a CSR,
   // the poses as (c, R); k_frame_targets writes the framed rows of hd_t.  tsl_set_handles resets n_frame to 0
   int n_frame = 0;

@@ -16,10 +16,12 @@
 #include "k_fem.hpp"
 #include "k_frame.hpp"
 #include "k_handle.hpp"
+#include "k_handle_face.hpp"
 #include "k_mg.hpp"
 #include "k_param.hpp"
 #include "k_solver.hpp"
 #include "frame_host.hpp"
+#include "handle_face_host.hpp"
 #include "handle_host.hpp"
 #include "param_keys.hpp"
 #include "tsl_ctx.hpp"
@@ -85,6 +87,11 @@ static TetArgs tet_args(tsl_ctx* c) {
 static HandleArgs handle_args(tsl_ctx* c) { return HandleArgs{c->n_handle, c->hd_v.p, c->hd_w.p, c->hd_t.p, c->k_handle}; }
 // the handle kernels of an energy / assembly / reverse step run only while this holds: without it the launches are the ones they were
 static bool handles_on(const tsl_ctx* c) { return c->n_handle > 0 && c->k_handle != 0.0; }
+// a face list (tsl_set_handles_on_faces, k_handle_face.hpp): the same places, the face kernels
+static FaceHandleArgs hface_args(tsl_ctx* c) { return FaceHandleArgs{c->n_handle, c->hf_fv.p, c->hf_b.p, c->hd_w.p, c->hd_t.p, c->k_handle}; }
+static FaceHandleLists_dev hface_lists(tsl_ctx* c) {
+  return FaceHandleLists_dev{c->n_hf_vert, c->n_hf_blk, c->hf_vl_v.p, c->hf_vl_ptr.p, c->hf_vl_ent.p, c->hf_bl_addr.p, c->hf_bl_ptr.p, c->hf_bl_ent.p};
+}
 static ContactArgs contact_args(tsl_ctx* c) {
   ContactArgs A;
   A.idx = c->c_idx.p; A.w = c->c_w.p; A.n = c->c_n.p; A.dx0 = c->c_dx0.p; A.k = c->c_k.p; A.mu = c->c_mu.p; A.T = c->c_T.p;
@@ -116,6 +123,7 @@ extern "C" int tsl_ctx_create(const tsl_scene_desc* d, tsl_ctx** out) {
   const auto no_event = [](hipEvent_t* e) { return hipEventCreateWithFlags(e, hipEventDisableTiming) != hipSuccess; };
   if (no_stream(&c->stream) || no_event(&c->ev_in) || no_event(&c->ev_out)) return tsl_fail("stream / event creation failed");
   c->NV = d->tot_NV; c->NF = d->tot_NF;
+  if (d->tot_NF > 0 && d->faces_host) c->h_faces.assign(d->faces_host, d->faces_host + 3 * (size_t)d->tot_NF);
   c->dt = d->dt; c->k_contact = d->k_contact; c->eps_contact = d->eps_contact; c->eps_v = d->eps_v; c->damping = d->damping;
   c->max_n_constraints = d->max_n_constraints > 0 ? d->max_n_constraints : 10000;
   c->grid_h = d->grid_h > 0 ? d->grid_h : 0.003;
@@ -353,6 +361,12 @@ static void frame_targets_launch(tsl_ctx* c) {
   hipLaunchKernelGGL(k_frame_targets, dim3(nblk(c->n_handle, 256)), dim3(256), 0, c->stream, c->n_handle, frame_args(c), c->hd_t.p);
 }
 
+static void hface_release(tsl_ctx* c) {
+  c->handle_on_faces = false;
+  c->n_hf_vert = c->n_hf_blk = 0;
+  c->hf_fv.release(); c->hf_b.release(); c->hf_vl_v.release(); c->hf_vl_ptr.release(); c->hf_vl_ent.release();
+  c->hf_bl_addr.release(); c->hf_bl_ptr.release(); c->hf_bl_ent.release();
+}
 // Soft handles (k_handle.hpp): the lists are checked on the host (handle_host.hpp) and copied into buffers of the context; targets start at zero
 extern "C" int tsl_set_handles(tsl_ctx* c, const int32_t* verts, const double* weights, int32_t n) {
   Scope scope(c);
@@ -363,6 +377,7 @@ extern "C" int tsl_set_handles(tsl_ctx* c, const int32_t* verts, const double* w
   c->ds.anorm_valid = false;   // (the scale of the operator may change: |H|_inf is formed again when a refinement asks for it)
   c->n_handle = 0;
   frames_release(c);   // (the handle list changed: the frames went with it)
+  hface_release(c);    // (a context holds a vertex list or a face list)
   if (n == 0) { c->hd_v.release(); c->hd_w.release(); c->hd_t.release(); c->hd_out.release(); return 0; }
   std::vector<int> hv(verts, verts + n);
   std::vector<double> hw(n, 1.0);
@@ -371,6 +386,40 @@ extern "C" int tsl_set_handles(tsl_ctx* c, const int32_t* verts, const double* w
   TSL_TRY(c->hd_w.upload(hw));
   TSL_TRY(c->hd_t.upload(std::vector<double>(3 * (size_t)n, 0.0)));
   TSL_TRY(c->hd_out.alloc(3 * (size_t)n));
+  c->n_handle = n;
+  return 0;
+}
+// Handles at barycentric points of faces (k_handle_face.hpp): the list is checked and the gather lists are built on the host (handle_face_host.hpp)
+// from the pattern the context keeps, before anything of the previous list is touched; conventions of tsl_set_handles
+extern "C" int tsl_set_handles_on_faces(tsl_ctx* c, const int32_t* faces, const double* bary, const double* weights, int32_t n) {
+  Scope scope(c);
+  (void)hipStreamSynchronize(c->stream);
+  std::string err;
+  if (handle_face_validate(c->NV, c->NF, c->h_faces.data(), faces, bary, weights, n, err)) return tsl_fail("tsl_set_handles_on_faces: %s", err.c_str());
+  FaceHandleLists L;
+  if (n > 0) {
+    Pattern P;   // (lookup reads the rows, their positions and the slice offsets)
+    P.rows = c->h_rows; P.rowpos = c->h_rowpos; P.slice_off = c->h_slice_off;
+    if (handle_face_lists(P, c->h_faces.data(), faces, n, L, err)) return tsl_fail("tsl_set_handles_on_faces: %s", err.c_str());
+  }
+  c->mg_omega_valid = false;
+  c->ds.anorm_valid = false;
+  c->n_handle = 0;
+  frames_release(c);
+  hface_release(c);
+  c->hd_v.release();
+  if (n == 0) { c->hd_w.release(); c->hd_t.release(); c->hd_out.release(); return 0; }
+  std::vector<double> hw(n, 1.0);
+  if (weights) hw.assign(weights, weights + n);
+  TSL_TRY(c->hf_fv.upload(L.fv));
+  TSL_TRY(c->hf_b.upload(std::vector<double>(bary, bary + 3 * (size_t)n)));
+  TSL_TRY(c->hf_vl_v.upload(L.vl_v)); TSL_TRY(c->hf_vl_ptr.upload(L.vl_ptr)); TSL_TRY(c->hf_vl_ent.upload(L.vl_ent));
+  TSL_TRY(c->hf_bl_addr.upload(L.bl_addr)); TSL_TRY(c->hf_bl_ptr.upload(L.bl_ptr)); TSL_TRY(c->hf_bl_ent.upload(L.bl_ent));
+  TSL_TRY(c->hd_w.upload(hw));
+  TSL_TRY(c->hd_t.upload(std::vector<double>(3 * (size_t)n, 0.0)));
+  TSL_TRY(c->hd_out.alloc(3 * (size_t)n));
+  c->n_hf_vert = (int)L.vl_v.size(); c->n_hf_blk = (int)L.bl_addr.size();
+  c->handle_on_faces = true;
   c->n_handle = n;
   return 0;
 }
@@ -398,15 +447,25 @@ extern "C" int tsl_handle_force(tsl_ctx* c, const double* pos, double* out_host)
   Scope scope(c);
   if (c->n_handle == 0) return 0;
   if (!pos || !out_host) return tsl_fail("tsl_handle_force: null argument");
-  hipLaunchKernelGGL(k_handle_force, dim3(nblk(c->n_handle, 256)), dim3(256), 0, c->stream, handle_args(c), pos, c->hd_out.p);
+  if (c->handle_on_faces) hipLaunchKernelGGL(k_hface_force, dim3(nblk(c->n_handle, 256)), dim3(256), 0, c->stream, hface_args(c), pos, c->hd_out.p);
+  else hipLaunchKernelGGL(k_handle_force, dim3(nblk(c->n_handle, 256)), dim3(256), 0, c->stream, handle_args(c), pos, c->hd_out.p);
+  return handle_readout(c, out_host);
+}
+extern "C" int tsl_handle_points(tsl_ctx* c, const double* pos, double* out_host) {
+  Scope scope(c);
+  if (c->n_handle == 0) return 0;
+  if (!pos || !out_host) return tsl_fail("tsl_handle_points: null argument");
+  if (c->handle_on_faces) hipLaunchKernelGGL(k_hface_points, dim3(nblk(c->n_handle, 256)), dim3(256), 0, c->stream, hface_args(c), pos, c->hd_out.p);
+  else hipLaunchKernelGGL(k_handle_points, dim3(nblk(c->n_handle, 256)), dim3(256), 0, c->stream, handle_args(c), pos, c->hd_out.p);
   return handle_readout(c, out_host);
 }
 extern "C" int tsl_handle_grad(tsl_ctx* c, const double* p_dev, double* out_host) {
   Scope scope(c);
   if (c->n_handle == 0) return 0;
   if (!out_host) return tsl_fail("tsl_handle_grad: null argument");
-  hipLaunchKernelGGL(k_handle_backprop, dim3(nblk(c->n_handle, 256)), dim3(256), 0, c->stream, handle_args(c), p_dev ? p_dev : (const double*)c->pdir.p,
-                     (const int*)c->frozen.p, c->hd_out.p);
+  const double* p = p_dev ? p_dev : (const double*)c->pdir.p;
+  if (c->handle_on_faces) hipLaunchKernelGGL(k_hface_backprop, dim3(nblk(c->n_handle, 256)), dim3(256), 0, c->stream, hface_args(c), p, (const int*)c->frozen.p, c->hd_out.p);
+  else hipLaunchKernelGGL(k_handle_backprop, dim3(nblk(c->n_handle, 256)), dim3(256), 0, c->stream, handle_args(c), p, (const int*)c->frozen.p, c->hd_out.p);
   return handle_readout(c, out_host);
 }
 
@@ -465,7 +524,8 @@ extern "C" int tsl_handle_targets(tsl_ctx* c, double* out_host) {
 template <int MODE>
 static int frame_readout(tsl_ctx* c, const double* vec, double* out_host) {
   if (c->k_handle == 0.0) { std::fill(out_host, out_host + 6 * (size_t)c->n_frame, 0.0); return 0; }
-  hipLaunchKernelGGL(k_frame_reduce<MODE>, dim3(c->n_frame), dim3(256), 0, c->stream, handle_args(c), frame_args(c), vec, (const int*)c->frozen.p, c->fr_out.p);
+  if (c->handle_on_faces) hipLaunchKernelGGL(k_hface_frame_reduce<MODE>, dim3(c->n_frame), dim3(256), 0, c->stream, hface_args(c), frame_args(c), vec, (const int*)c->frozen.p, c->fr_out.p);
+  else hipLaunchKernelGGL(k_frame_reduce<MODE>, dim3(c->n_frame), dim3(256), 0, c->stream, handle_args(c), frame_args(c), vec, (const int*)c->frozen.p, c->fr_out.p);
   HIP_OK(hipGetLastError());
   HIP_OK(hipMemcpyAsync(out_host, c->fr_out.p, 6 * (size_t)c->n_frame * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   HIP_OK(hipStreamSynchronize(c->stream));
@@ -543,7 +603,8 @@ static int energy_async(tsl_ctx* c, const double* pos, const double* prev, const
   else hipLaunchKernelGGL(k_energy, dim3(nb1), dim3(256), 0, s, vert_args(c), cloth_args(c), tet_args(c), pos, prev, vel, ref, c->e_part.p);
   if (nb2 > 0) hipLaunchKernelGGL(k_contact_energy, dim3(nb2), dim3(64), 0, s, nvf, contact_args(c), pos, c->e_part.p + nb1);
   if (nb3 > 0) hipLaunchKernelGGL(k_ee_energy, dim3(nb3), dim3(64), 0, s, c->nc_ee, ee_args(contact_args(c), nvf), pos, c->e_part.p + nb1 + nb2);
-  if (nb4 > 0) hipLaunchKernelGGL(k_handle_energy, dim3(nb4), dim3(256), 0, s, handle_args(c), pos, c->e_part.p + nb1 + nb2 + nb3);
+  if (nb4 > 0 && c->handle_on_faces) hipLaunchKernelGGL(k_hface_energy, dim3(nb4), dim3(256), 0, s, hface_args(c), pos, c->e_part.p + nb1 + nb2 + nb3);
+  else if (nb4 > 0) hipLaunchKernelGGL(k_handle_energy, dim3(nb4), dim3(256), 0, s, handle_args(c), pos, c->e_part.p + nb1 + nb2 + nb3);
   hipLaunchKernelGGL(k_energy_final, dim3(1), dim3(256), 0, s, nb1 + nb2 + nb3 + nb4, (const double*)c->e_part.p, &SC(c)->energy);
   return 0;
 }
@@ -633,6 +694,13 @@ static void cloth_hess_face_launch(tsl_ctx* c, hipStream_t s, const ClothArgs& C
 // Soft handles in an assembly: their gradient rows and diagonal entries behind the vertex terms on the same stream (nothing while no handle is on)
 static void handle_assemble_launch(tsl_ctx* c, hipStream_t s, const double* pos, double* grad) {
   if (!handles_on(c)) return;
+  if (c->handle_on_faces) {   // one lane per touched vertex / per touched block (k_handle_face.hpp)
+    const FaceHandleArgs FA = hface_args(c);
+    const FaceHandleLists_dev FL = hface_lists(c);
+    if (grad) hipLaunchKernelGGL(k_hface_grad, dim3(nblk(FL.n_vert, 256)), dim3(256), 0, s, FA, FL, pos, grad);
+    hipLaunchKernelGGL(k_hface_hess, dim3(nblk(FL.n_blk, 256)), dim3(256), 0, s, FA, FL, c->vals_full.p);
+    return;
+  }
   const HandleArgs HA = handle_args(c);
   if (grad) hipLaunchKernelGGL(k_handle_grad, dim3(nblk(HA.n, 256)), dim3(256), 0, s, HA, pos, grad);
   hipLaunchKernelGGL(k_handle_hess, dim3(nblk(HA.n, 256)), dim3(256), 0, s, HA, (const int*)c->diag_blk.p, c->vals_full.p);
@@ -2229,7 +2297,8 @@ extern "C" int tsl_param_grad_keys(tsl_ctx* c, const double* pos, const double* 
     if (c->n_stvk > 0) hipLaunchKernelGGL(k_pg_face<true>, dim3(nb[0]), dim3(PG_THREADS), 0, s, cloth_args(c), n_cloth, pos, p, fz, part + off[0], stvk_args(c));
     else hipLaunchKernelGGL(k_pg_face<false>, dim3(nb[0]), dim3(PG_THREADS), 0, s, cloth_args(c), n_cloth, pos, p, fz, part + off[0], stvk_args(c));
   }
-  if (need[5] && nb[5]) hipLaunchKernelGGL(k_pg_handle, dim3(nb[5]), dim3(PG_THREADS), 0, s, handle_args(c), pos, p, fz, part + off[5]);
+  if (need[5] && nb[5] && c->handle_on_faces) hipLaunchKernelGGL(k_pg_hface, dim3(nb[5]), dim3(PG_THREADS), 0, s, hface_args(c), pos, p, fz, part + off[5]);
+  else if (need[5] && nb[5]) hipLaunchKernelGGL(k_pg_handle, dim3(nb[5]), dim3(PG_THREADS), 0, s, handle_args(c), pos, p, fz, part + off[5]);
   if (need[4] && nb[4]) hipLaunchKernelGGL(k_pg_stvk, dim3(nb[4]), dim3(PG_THREADS), 0, s, cloth_args(c), n_cloth, pos, p, fz, part + off[4], stvk_args(c));
   if (need[1] && nb[1]) hipLaunchKernelGGL(k_pg_hinge, dim3(nb[1]), dim3(PG_THREADS), 0, s, cloth_args(c), n_cloth, pos, ref, p, fz, part + off[1]);
   if (need[2] && nb[2]) hipLaunchKernelGGL(k_pg_tet, dim3(nb[2]), dim3(PG_THREADS), 0, s, tet_args(c), n_el, pos, p, fz, part + off[2]);

@@ -56,6 +56,36 @@ def validate_handles(tot_NV, vertex_ids, weights=None):
     return v.astype(np.int32), w
 
 
+def validate_surface_handles(tot_NF, face_ids, bary, weights=None):
+    """The checks of tsl_set_handles_on_faces on the host, with its messages: returns (int32 face ids, float64 coordinates (n, 3), float64 weights or
+    None) or raises ValueError naming the offender -- a face outside [0, tot_NF), a barycentric coordinate that is not finite or outside [0, 1], a
+    triple whose sum differs from 1 by more than 1e-9, a negative or non-finite weight.  The coordinates are used as given, not renormalised."""
+    f = np.asarray(face_ids)
+    if f.ndim != 1 or (f.size and not np.issubdtype(f.dtype, np.integer)):
+        raise ValueError(f"set_surface_handles: face ids must be a flat list of integers (got shape {f.shape}, dtype {f.dtype})")
+    f = f.astype(np.int64)
+    b = np.asarray(bary, dtype=np.float64)
+    if b.shape != (f.size, 3):
+        raise ValueError(f"set_surface_handles: barycentric coordinates of shape {b.shape} for {f.size} handles (expected ({f.size}, 3))")
+    w = None
+    if weights is not None:
+        w = np.asarray(weights, dtype=np.float64)
+        if w.shape != f.shape:
+            raise ValueError(f"set_surface_handles: {w.size} weights for {f.size} handles")
+    for i, fi in enumerate(f.tolist()):
+        if fi < 0 or fi >= tot_NF:
+            raise ValueError(f"set_surface_handles: face {fi} of handle {i} out of range [0, {tot_NF})")
+        for a in range(3):
+            if not (np.isfinite(b[i, a]) and 0.0 <= b[i, a] <= 1.0):
+                raise ValueError(f"set_surface_handles: barycentric coordinate {b[i, a]:g} of handle {i} (face {fi}) is not finite or outside [0, 1]")
+        tot = (b[i, 0] + b[i, 1]) + b[i, 2]
+        if not abs(tot - 1.0) <= 1e-9:
+            raise ValueError(f"set_surface_handles: barycentric coordinates ({b[i, 0]:g}, {b[i, 1]:g}, {b[i, 2]:g}) of handle {i} (face {fi}) sum to {tot:.12g}, not 1")
+        if w is not None and not (w[i] >= 0.0 and np.isfinite(w[i])):
+            raise ValueError(f"set_surface_handles: weight {w[i]:g} of handle {i} (face {fi}) is negative or not finite")
+    return f.astype(np.int32), np.ascontiguousarray(b), w
+
+
 class _SystemMatrix:
     """Stand-in for ``SparseMatrix`` (sparse_solver.py): the matrix itself lives inside the context."""
 
@@ -109,6 +139,8 @@ class BaseScene:
         self.last_stats = {}
         # soft handles (set_handles): vertex ids, weights, targets and the stiffness k_handle, kept here and pushed to the engine context lazily
         self._handle_v = np.zeros(0, np.int32)
+        self._handle_f = None    # set_surface_handles: global face ids and barycentric coordinates (n, 3); None while the list is a vertex list
+        self._handle_b = None
         self._handle_w = None
         self._handle_t = np.zeros((0, 3))
         self.k_handle = 0.0
@@ -431,7 +463,7 @@ class BaseScene:
     # ------------------------------------------------------------------ soft handles (no counterpart in the reference)
     @property
     def n_handle(self):
-        return len(self._handle_v)
+        return len(self._handle_v) if self._handle_f is None else len(self._handle_f)
 
     def set_handles(self, vertex_ids, k, weights=None):
         """Target springs on vertices: E_h = 1/2 k sum_i w_i |x_{v_i} - t_i|^2 with global vertex ids v_i (at most one handle per vertex), stiffness
@@ -442,10 +474,38 @@ class BaseScene:
         if not (k >= 0.0 and np.isfinite(k)):
             raise ValueError(f"set_handles: k_handle must be finite and >= 0 (got {k:g})")
         self._handle_v, self._handle_w, self.k_handle = v, w, k
+        self._handle_f = self._handle_b = None   # (a scene holds a vertex list or a face list)
         self._handle_t = np.zeros((len(v), 3))
         self._frame_of, self._frame_local = np.zeros(0, np.int32), np.zeros((0, 3))   # (the handle list changed: the frames go with it)
         self._frame_pos, self._frame_quat = np.zeros((0, 3)), np.zeros((0, 4))
         self._dirty.add("handles")
+
+    def set_surface_handles(self, face_ids, bary, k, weights=None):
+        """Target springs on points of faces: E_h = 1/2 k sum_i w_i |p_i - t_i|^2 with p_i = sum_a b_a x_{v_a} the point of barycentric coordinates
+        bary[i] on the global face face_ids[i] = (v_0, v_1, v_2) of self.faces (a cloth face or a surface face of a body; Cloth.locate gives both for
+        a material point of a cloth).  Any number of handles may share a face or a vertex.  It replaces the handle list, as set_handles does -- each
+        drops the other's list and the frames; an empty list removes the handles.  The targets start at zero: set_handle_targets.  The lists are
+        checked here, before any library call; the engine context receives them at its next use."""
+        f, b, w = validate_surface_handles(self.tot_NF, face_ids, bary, weights)
+        k = float(k)
+        if not (k >= 0.0 and np.isfinite(k)):
+            raise ValueError(f"set_surface_handles: k_handle must be finite and >= 0 (got {k:g})")
+        self._handle_f, self._handle_b, self._handle_w, self.k_handle = f, b, w, k
+        self._handle_v = np.zeros(0, np.int32)
+        self._handle_t = np.zeros((len(f), 3))
+        self._frame_of, self._frame_local = np.zeros(0, np.int32), np.zeros((0, 3))   # (the handle list changed: the frames go with it)
+        self._frame_pos, self._frame_quat = np.zeros((0, 3)), np.zeros((0, 4))
+        self._dirty.add("handles")
+
+    def handle_points(self):
+        """(n, 3): the points the handles act on at the current positions -- sum_a b_a x_{v_a} of a face list, x_{v_i} of a vertex list (host arithmetic
+        on a copy of the positions: the grasp of set_handle_frames needs no engine context; TslContext.handle_points is the library's read-out)"""
+        x = self.pos.to_numpy()
+        if self._handle_f is None:
+            return x[self._handle_v]
+        fv = self.faces.to_numpy()[self._handle_f]
+        b = self._handle_b
+        return (b[:, 0:1] * x[fv[:, 0]] + b[:, 1:2] * x[fv[:, 1]]) + b[:, 2:3] * x[fv[:, 2]]
 
     def set_handle_targets(self, targets):
         """world-space targets (n, 3) of the next energy, assembly, time step or reverse step"""
@@ -460,7 +520,10 @@ class BaseScene:
         return self._ensure_ctx().handle_force(self.pos.t)
 
     def _push_handles(self):
-        self._ctx.set_handles(self._handle_v, self._handle_w)
+        if self._handle_f is None:
+            self._ctx.set_handles(self._handle_v, self._handle_w)
+        else:
+            self._ctx.set_handles_on_faces(self._handle_f, self._handle_b, self._handle_w)
         self._ctx.set_param("k_handle", self.k_handle)
         self._ctx.set_handle_targets(self._handle_t)
         self._push_frames()
@@ -474,7 +537,7 @@ class BaseScene:
         """Put handles on rigid frames: handle i belongs to frame frame_ids[i] in [0, n_frames) with the local point local_points[i], or stays a free
         handle with a world target (frame id -1).  The target of a framed handle is c + R(q) r_i with the frame's pose (c, q) (set_frame_poses,
         move_frames).  n_frames None: largest id + 1; n_frames = 0 (or all ids -1 with n_frames None) removes the frames.  local_points None grasps
-        the handled vertices where they are: r_i = R^T (x_{v_i} - c) at the current poses.  Poses are kept when the number of frames stays, and
+        the handled points where they are: r_i = R^T (p_i - c) at the current poses.  Poses are kept when the number of frames stays, and
         start at the identity at the origin otherwise.  The lists are checked here, before any library call."""
         f = np.asarray(frame_ids)
         if n_frames is None:
@@ -486,7 +549,7 @@ class BaseScene:
         if local_points is None:
             local_points = np.zeros((self.n_handle, 3))
             if f.shape == (self.n_handle,) and self.n_handle:
-                x = self.pos.to_numpy()[self._handle_v]
+                x = self.handle_points()
                 for i, fi in enumerate(f.tolist()):
                     if 0 <= fi < len(pos):
                         local_points[i] = quat_to_rotmat(quat[fi]).T @ (x[i] - pos[fi])

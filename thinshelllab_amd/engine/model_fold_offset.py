@@ -80,6 +80,33 @@ class Cloth:
         N, M = self.N, self.M
         return [self.offset + v for v in (0, M, N * (M + 1), N * (M + 1) + M)]
 
+    def locate(self, u, v):
+        """(global face id, barycentric coordinates (3,)) of the material point at the parametric coordinates (u, v) in [0, 1]^2 of the rest grid:
+        u runs along the N cells of grid index i, v along the M cells of index j, so that the point is sum_a b_a X_{v_a} = X(0, 0) + (u N dx, v M dx)
+        in the rest pose -- the same material point at every resolution, e.g. for BaseScene.set_surface_handles.  A point on an edge or a vertex
+        returns a valid face with zero coordinates; (1, 1) lies in the last cell."""
+        u, v = float(u), float(v)
+        if not (0.0 <= u <= 1.0 and 0.0 <= v <= 1.0):
+            raise ValueError(f"locate: ({u:g}, {v:g}) outside [0, 1]^2")
+        N, M = self.N, self.M
+        s, t = u * N, v * M
+        i, j = min(int(s), N - 1), min(int(t), M - 1)
+        fs, ft = min(max(s - i, 0.0), 1.0), min(max(t - j, 0.0), 1.0)
+        k = (i * M + j) * 2
+        # corners of the cell in (fs, ft): a (0, 0), b (0, 1), c (1, 1), d (1, 0); even cells are cut along a-c, odd ones along b-d (init_mesh)
+        if (i + j) % 2 == 0:
+            if ft >= fs:
+                f, b = k, (fs, ft - fs, 1.0 - ft)             # (c, b, a)
+            else:
+                f, b = k + 1, (1.0 - fs, fs - ft, ft)         # (a, d, c)
+        else:
+            if fs + ft <= 1.0:
+                f, b = k, (ft, 1.0 - fs - ft, fs)             # (b, a, d)
+            else:
+                f, b = k + 1, (1.0 - ft, fs + ft - 1.0, 1.0 - fs)   # (d, c, b)
+        b = np.clip(np.array(b, dtype=np.float64), 0.0, 1.0)
+        return self.offset_faces + f, b
+
     def _stvk_params(self):
         """(key suffix, value) of the membrane settings that differ from the defaults (pushed by BaseScene when it creates the engine context)"""
         return [(k, f.value) for k, f in (("stvk_mu", self.stvk_mu), ("stvk_lam", self.stvk_lam), ("membrane", self.membrane)) if f.value != 0.0]
