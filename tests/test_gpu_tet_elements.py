@@ -59,8 +59,9 @@ class Ctx:
         from thinshelllab_amd.context import _ptr
         pos = _dev(self.x if x is None else x)
         g = torch.zeros(3 * self.nv, dtype=torch.float64, device="cuda")
+        prev, vel = pos.clone(), torch.zeros_like(pos)   # (named: a temporary's memory is handed to the next allocation before the engine reads it)
         self.ctx.refresh_stream()
-        check(self.ctx.L.tsl_assemble(self.ctx.h, _ptr(pos), _ptr(pos.clone()), _ptr(torch.zeros_like(pos)), _ptr(self.ref), int(spd), _ptr(g)), "tsl_assemble")
+        check(self.ctx.L.tsl_assemble(self.ctx.h, _ptr(pos), _ptr(prev), _ptr(vel), _ptr(self.ref), int(spd), _ptr(g)), "tsl_assemble")
         torch.cuda.synchronize()
         return self.ctx.matrix_csr().toarray(), g.cpu().numpy()
 
@@ -97,11 +98,13 @@ def _mass12():
 
 
 class Ratios(dict):
+    label = "tet elements"
+
     def add(self, q, err, bnd):
         self[q] = max(self.get(q, 0.0), err / bnd)
 
     def check(self, what):
-        print("tet elements, %s: largest |gpu - mp| / bound: %s" % (what, ", ".join("%s %.3f" % kv for kv in sorted(self.items()))))
+        print("%s, %s: largest |gpu - mp| / bound: %s" % (self.label, what, ", ".join("%s %.3f" % kv for kv in sorted(self.items()))))
         bad = {k: v for k, v in self.items() if not v <= 1.0}
         assert not bad, (what, bad)
 

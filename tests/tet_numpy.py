@@ -37,6 +37,8 @@ class MP:
         return mp.mpf(v) if isinstance(v, str) else mp.mpf(float(v)) if not isinstance(v, mp.mpf) else v
 
     log = staticmethod(mp.log)
+    sqrt = staticmethod(mp.sqrt)
+    acos = staticmethod(mp.acos)
 
     @staticmethod
     def eigh(A):
@@ -54,6 +56,8 @@ class F64:
         return np.float64(v)
 
     log = staticmethod(np.log)
+    sqrt = staticmethod(np.sqrt)
+    acos = staticmethod(np.arccos)
 
     @staticmethod
     def eigh(A):
