@@ -1,12 +1,13 @@
-// Test program (never part of libtsl_hip.so): the checks and the gather lists of csrc/handle_face_host.hpp on the pattern of a small grid, printed
-// as "name: integers" lines for tests/test_surface_handle_numpy.py, which builds it with -fsanitize=address,undefined and compares the lists with
-// a NumPy construction of the same rule.  The refused lists print "refused: <message>"; the program ends with "done" and exit status 0.
+// Test program (never part of libtsl_hip.so): the checks and the gather lists of csrc/handle_host.hpp on the pattern of a small grid, for a face
+// list (three corners per handle) and a vertex list (one), printed as "name: integers" lines for tests/test_surface_handle_numpy.py, which builds
+// it with -fsanitize=address,undefined and compares the lists with a NumPy construction of the same rule.  The refused lists print
+// "refused: <message>"; the program ends with "done" and exit status 0.
 #include <cstdio>
 #include <limits>
 #include <string>
 #include <vector>
 
-#include "../../thinshelllab_amd/csrc/handle_face_host.hpp"
+#include "../../thinshelllab_amd/csrc/handle_host.hpp"
 #include "../../thinshelllab_amd/csrc/scene_tables.hpp"
 
 static void show(const char* name, const std::vector<int>& a) {
@@ -41,10 +42,11 @@ int main() {
   const int32_t n = (int32_t)hf.size();
   std::string err;
   if (handle_face_validate(NV, NF, faces.data(), hf.data(), hb.data(), hw.data(), n, err)) { printf("unexpected: %s\n", err.c_str()); return 1; }
-  FaceHandleLists L;
-  if (handle_face_lists(P, faces.data(), hf.data(), n, L, err)) { printf("unexpected: %s\n", err.c_str()); return 1; }
+  HandleLists L;
+  const std::vector<int> fv = handle_face_corners(faces.data(), hf.data(), n);
+  if (handle_lists(P, fv.data(), n, 3, L, err, hf.data())) { printf("unexpected: %s\n", err.c_str()); return 1; }
   show("handle_faces", std::vector<int>(hf.begin(), hf.end()));
-  show("fv", L.fv); show("vl_v", L.vl_v); show("vl_ptr", L.vl_ptr); show("vl_ent", L.vl_ent);
+  show("fv", fv); show("vl_v", L.vl_v); show("vl_ptr", L.vl_ptr); show("vl_ent", L.vl_ent);
   show("bl_addr", L.bl_addr); show("bl_ptr", L.bl_ptr); show("bl_ent", L.bl_ent);
   // n = 0 and weights == nullptr are valid
   if (handle_face_validate(NV, NF, faces.data(), nullptr, nullptr, nullptr, 0, err)) { printf("unexpected: %s\n", err.c_str()); return 1; }
@@ -68,8 +70,28 @@ int main() {
     tab[3 * 5 + 2] = NV - 1;   // face 5 now joins vertices that share no element
     const std::vector<int32_t> f = {17, 5};
     err.clear();
-    const int rc = handle_face_lists(P, tab.data(), f.data(), 2, L, err);
+    const int rc = handle_lists(P, handle_face_corners(tab.data(), f.data(), 2).data(), 2, 3, L, err, f.data());
     printf("refused: %s\n", rc ? err.c_str() : "NOT REFUSED");
+  }
+
+  // a vertex list: out of order, across both slices of the pattern, the first and the last vertex among them; one corner per handle
+  const std::vector<int32_t> hv = {71, 3, 89, 64, 0, 40, 63, 17, 88, 5};
+  const int32_t nv = (int32_t)hv.size();
+  if (handle_validate(NV, hv.data(), nullptr, nv, err)) { printf("unexpected: %s\n", err.c_str()); return 1; }
+  HandleLists V;
+  if (handle_lists(P, std::vector<int>(hv.begin(), hv.end()).data(), nv, 1, V, err)) { printf("unexpected: %s\n", err.c_str()); return 1; }
+  show("handle_verts", std::vector<int>(hv.begin(), hv.end()));
+  show("v_vl_v", V.vl_v); show("v_vl_ptr", V.vl_ptr); show("v_vl_ent", V.vl_ent);
+  show("v_bl_addr", V.bl_addr); show("v_bl_ptr", V.bl_ptr); show("v_bl_ent", V.bl_ent);
+  std::vector<int> diag;   // the pattern's diagonal addresses, what the scene tables keep as their diagonal-block table
+  for (int v = 0; v < NV; v++) diag.push_back(P.lookup(v, v));
+  show("diag", diag);
+  {   // the vertex list's refusals
+    const std::vector<int32_t> twice = {3, 7, 7}, out = {NV};
+    const std::vector<double> w = {1.0, -1.0};
+    err.clear(); printf("refused: %s\n", handle_validate(NV, twice.data(), nullptr, 3, err) ? err.c_str() : "NOT REFUSED");
+    err.clear(); printf("refused: %s\n", handle_validate(NV, out.data(), nullptr, 1, err) ? err.c_str() : "NOT REFUSED");
+    err.clear(); printf("refused: %s\n", handle_validate(NV, hv.data(), w.data(), 2, err) ? err.c_str() : "NOT REFUSED");
   }
   printf("done\n");
   return 0;

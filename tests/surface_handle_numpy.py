@@ -1,11 +1,11 @@
-"""NumPy restatement of soft handles at barycentric points of faces (csrc/k_handle_face.hpp): handle i sits on the face with the
+"""NumPy restatement of soft handles at barycentric points of faces (csrc/k_handle.hpp): handle i sits on the face with the
 vertices fv[i] = (v_0, v_1, v_2), has barycentric coordinates b[i] and ties the point p_i = sum_a b_a x_{v_a} to a world-space target t_i,
 
     E_h = 1/2 k sum_i w_i |p_i - t_i|^2,   H = k sum_i w_i (b_i b_i^T) (x) I_3 on the dofs of the face.
 
 Dense: x is (NV, 3), the matrix (3 NV, 3 NV).  Frozen rule (the engine's mask rule): a frozen dof has no gradient entry, no matrix row or column of
 the term, and contributes to no gradient with respect to a target or to k.  The energy, the points and the force read-out are not masked.
-gather_lists restates the two gather lists of csrc/handle_face_host.hpp, block addresses included."""
+gather_lists restates the two gather lists of csrc/handle_host.hpp, block addresses included."""
 import numpy as np
 
 
@@ -93,21 +93,28 @@ def block_addresses(NV, cliques):
     return out
 
 
-def gather_lists(NV, faces_tab, faces, address):
-    """the lists of handle_face_lists as a dict of int arrays: fv (n x 3 flat); the touched vertices ascending with their entries 3 i + a ascending;
-    the touched blocks ascending by (row vertex, column vertex) with their address and their entries 9 i + 3 a + b ascending"""
-    fv = np.asarray(faces_tab).reshape(-1, 3)[np.asarray(faces)]
-    n = len(fv)
+def corner_lists(cv, address):
+    """the lists of handle_lists (csrc/handle_host.hpp) for the corners cv (n x nc) as a dict of int arrays: the touched vertices ascending with their
+    entries nc i + a ascending; the touched blocks ascending by (row vertex, column vertex) with their address and their entries nc nc i + nc a + b
+    ascending"""
+    cv = np.asarray(cv)
+    n, nc = cv.shape
     by_v, by_b = {}, {}
     for i in range(n):
-        for a in range(3):
-            by_v.setdefault(int(fv[i, a]), []).append(3 * i + a)
-            for c in range(3):
-                by_b.setdefault((int(fv[i, a]), int(fv[i, c])), []).append(9 * i + 3 * a + c)
+        for a in range(nc):
+            by_v.setdefault(int(cv[i, a]), []).append(nc * i + a)
+            for c in range(nc):
+                by_b.setdefault((int(cv[i, a]), int(cv[i, c])), []).append(nc * nc * i + nc * a + c)
     vl_v, vl_ptr, vl_ent = [], [0], []
     for v in sorted(by_v):
         vl_v.append(v); vl_ent += sorted(by_v[v]); vl_ptr.append(len(vl_ent))
     bl_addr, bl_ptr, bl_ent = [], [0], []
     for pr in sorted(by_b):
         bl_addr.append(address[pr]); bl_ent += sorted(by_b[pr]); bl_ptr.append(len(bl_ent))
-    return dict(fv=fv.ravel(), vl_v=vl_v, vl_ptr=vl_ptr, vl_ent=vl_ent, bl_addr=bl_addr, bl_ptr=bl_ptr, bl_ent=bl_ent)
+    return dict(vl_v=vl_v, vl_ptr=vl_ptr, vl_ent=vl_ent, bl_addr=bl_addr, bl_ptr=bl_ptr, bl_ent=bl_ent)
+
+
+def gather_lists(NV, faces_tab, faces, address):
+    """the corners fv (n x 3 flat) of a face list and its lists: corner_lists with nc = 3 -- entries 3 i + a and 9 i + 3 a + b"""
+    fv = np.asarray(faces_tab).reshape(-1, 3)[np.asarray(faces)]
+    return dict(fv=fv.ravel(), **corner_lists(fv, address))

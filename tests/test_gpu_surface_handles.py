@@ -1,4 +1,4 @@
-"""Soft handles at barycentric points of faces (tsl_set_handles_on_faces; csrc/k_handle_face.hpp) through the C ABI.  The reference has
+"""Soft handles at barycentric points of faces (tsl_set_handles_on_faces; csrc/k_handle.hpp) through the C ABI.  The reference has
 no such term: it is checked against the dense NumPy restatement (tests/surface_handle_numpy.py), the vertex handles, differences of the assembled
 gradient and whole-rollout differences.  The idiom is that of tests/test_gpu_handles.py: a handle quantity of a state is the difference against the
 same state with k_handle = 0 -- no handle kernel runs there and the rest is formed by the same launches in both -- and K = 2e5 N/m, the size of

@@ -1,7 +1,7 @@
 """Soft handles at barycentric points of faces on the CPU: the NumPy restatement (tests/surface_handle_numpy.py) against differences
 of its own energy, the host checks of BaseScene.set_surface_handles, Cloth.locate, the tape's buffers for a face list, and the host module
-csrc/handle_face_host.hpp compiled into a stand-alone program under AddressSanitizer and UBSan (tests/native/handle_face_ref.cpp), its gather
-lists compared with a NumPy construction of the same rule."""
+csrc/handle_host.hpp compiled into a stand-alone program under AddressSanitizer and UBSan (tests/native/handle_ref.cpp), its gather lists -- of
+a face list and of a vertex list -- compared with a NumPy construction of the same rule."""
 import os
 import shutil
 import subprocess
@@ -179,9 +179,9 @@ def _ints(line):
 def test_host_module_under_sanitizers_builds_the_lists_of_the_rule(tmp_path):
     cxx = shutil.which("g++") or shutil.which("c++")
     assert cxx, "a host C++ compiler is needed"
-    exe = str(tmp_path / "handle_face_ref")
+    exe = str(tmp_path / "handle_ref")
     cmd = [cxx, "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer",
-           os.path.join(HERE, "native", "handle_face_ref.cpp"), "-o", exe]
+           os.path.join(HERE, "native", "handle_ref.cpp"), "-o", exe]
     # the sanitizers' runtimes inside the program where the tool chain has them as archives (the program then does not depend on the order in which
     # shared libraries are loaded into it); as shared libraries otherwise
     if subprocess.run(cmd + ["-static-libasan", "-static-libubsan"], capture_output=True).returncode != 0:
@@ -193,9 +193,19 @@ def test_host_module_under_sanitizers_builds_the_lists_of_the_rule(tmp_path):
     got = {ln.split(":", 1)[0]: _ints(ln) for ln in lines if ":" in ln and not ln.startswith("refused")}
     NV = int(got["NV"][0])
     tab = got["faces"].reshape(-1, 3)
-    want = sn.gather_lists(NV, tab, got["handle_faces"], sn.block_addresses(NV, tab))
+    address = sn.block_addresses(NV, tab)
+    want = sn.gather_lists(NV, tab, got["handle_faces"], address)
     for k, v in want.items():
         assert np.array_equal(got[k], np.asarray(v, np.int64)), k
+    # the vertex list: one corner per handle -- one entry per handled vertex and per diagonal block, at the pattern's diagonal address
+    hv = got["handle_verts"]
+    assert len(set(hv.tolist())) == len(hv) and (np.diff(hv) < 0).any() and hv.min() == 0 and hv.max() == NV - 1 and (hv < 64).any() and (hv >= 64).any()
+    for k, v in sn.corner_lists(hv.reshape(-1, 1), address).items():
+        assert np.array_equal(got["v_" + k], np.asarray(v, np.int64)), k
+    order = np.argsort(hv)
+    assert np.array_equal(got["v_vl_v"], hv[order]) and np.array_equal(got["v_vl_ent"], order) and np.array_equal(got["v_bl_ent"], order)
+    assert np.array_equal(got["v_vl_ptr"], np.arange(len(hv) + 1)) and np.array_equal(got["v_bl_ptr"], np.arange(len(hv) + 1))
+    assert np.array_equal(got["diag"], [address[(v, v)] for v in range(NV)]) and np.array_equal(got["v_bl_addr"], got["diag"][hv[order]])
     # properties the kernels rely on: every list is in range, every corner and every pair appears exactly once, the transposed block holds the same handles
     n = len(got["handle_faces"])
     assert sorted(got["vl_ent"].tolist()) == list(range(3 * n)) and sorted(got["bl_ent"].tolist()) == list(range(9 * n))
@@ -209,7 +219,8 @@ def test_host_module_under_sanitizers_builds_the_lists_of_the_rule(tmp_path):
               r"barycentric coordinate 1.2 of handle 2 \(face 5\) is not finite or outside \[0, 1\]",
               r"barycentric coordinates \(0.3, 0.3, 0.3\) of handle 2 \(face 5\) sum to 0.9, not 1",
               r"weight -1 of handle 2 \(face 5\) is negative or not finite", r"weight inf of handle 2 \(face 5\) is negative or not finite",
-              r"vertices 2 and 89 of face 5 \(handle 1\) have no block in the matrix pattern"]
+              r"vertices 2 and 89 of face 5 \(handle 1\) have no block in the matrix pattern",
+              r"vertex 7 has more than one handle", r"vertex 90 out of range \[0, 90\)", r"weight -1 of vertex 3 is negative or not finite"]
     import re
     assert len(refused) == len(expect), refused
     for msg, pat in zip(refused, expect):

@@ -30,14 +30,14 @@ __global__ void k_frame_targets(int n_handle, FrameArgs A, double* __restrict__ 
 }
 
 // Six sums per frame, one 256-lane workgroup per frame: out[6 j ..] = (sum_i f_i, sum_i a_i x f_i) over the frame's handles.
-//   FRAME_WRENCH: f_i = k w_i (t_i - x_{v_i}), the row of k_handle_force (frozen dofs not masked), a_i = t_i - c_j: force and moment about c_j that
+//   FRAME_WRENCH: f_i = k w_i (t_i - p_i), the row of k_handle_force (frozen dofs not masked), a_i = t_i - c_j: force and moment about c_j that
 //                 the frame's handles apply to the cloth, = dE_h / d(c_j, theta_j);  vec = positions.
-//   FRAME_GRAD:   f_i = k w_i p_{v_i} on free dofs, 0 on frozen ones, the row of k_handle_backprop, a_i = R_j r_i: one reverse step's contribution to
-//                 d(loss) / d(c_j, theta_j), theta a world-frame rotation vector applied on the left;  vec = the adjoint solution p.
-// Lane l takes the entries l, l + 256, ... of the frame's list in ascending order; the lanes of a wave are joined by wave_sum, the four waves in
-// order through LDS (the join of k_handle_energy); lane 0 stores.  A frame without handles stores six zeros.
+//   FRAME_GRAD:   f_i = the row of k_handle_backprop (k w_i sum_a b_a p_{v_a} on free dofs, 0 on frozen ones), a_i = R_j r_i: one reverse step's
+//                 contribution to d(loss) / d(c_j, theta_j), theta a world-frame rotation vector applied on the left;  vec = the adjoint solution p.
+// Lane l takes the entries l, l + 256, ... of the frame's list in ascending order; the lanes are joined by wg_join (the join of k_handle_energy,
+// six sums at once).  A frame without handles stores six zeros.  NC: the corners per handle of the list (k_handle.hpp).
 enum { FRAME_WRENCH = 0, FRAME_GRAD = 1 };
-template <int MODE>
+template <int MODE, int NC>
 __global__ void __launch_bounds__(256) k_frame_reduce(HandleArgs H, FrameArgs A, const double* __restrict__ vec, const int* __restrict__ frozen,
                                                       double* __restrict__ out) {
   const int j = blockIdx.x;
@@ -47,31 +47,19 @@ __global__ void __launch_bounds__(256) k_frame_reduce(HandleArgs H, FrameArgs A,
   const d3 c = MODE == FRAME_WRENCH ? ld3(A.c, j) : d3(0.0, 0.0, 0.0);   // (the wrench's arms start at c; the gradient's are R r)
   for (int e = A.ptr[j] + (int)threadIdx.x; e < e1; e += 256) {
     const int i = A.idx[e];
-    const int v = H.v[i];
-    const double kw = H.k * H.w[i];
     d3 f, a;
     if (MODE == FRAME_WRENCH) {
       const d3 t = ld3(H.t, i);
-      f = (t - ld3(vec, v)) * kw;
+      f = (t - handle_point<NC>(H, vec, i)) * (H.k * H.w[i]);
       a = t - c;
     } else {
-      const d3 pv = ld3(vec, v), r = ld3(A.local, i);
-      f = d3(frozen[3 * v] ? 0.0 : kw * pv.x, frozen[3 * v + 1] ? 0.0 : kw * pv.y, frozen[3 * v + 2] ? 0.0 : kw * pv.z);
+      const d3 r = ld3(A.local, i);
+      f = handle_backprop_row<NC>(H, vec, frozen, i);
       a = d3(R[0] * r.x + R[1] * r.y + R[2] * r.z, R[3] * r.x + R[4] * r.y + R[5] * r.z, R[6] * r.x + R[7] * r.y + R[8] * r.z);
     }
     const d3 m = cross(a, f);
     s[0] += f.x; s[1] += f.y; s[2] += f.z;
     s[3] += m.x; s[4] += m.y; s[5] += m.z;
   }
-  __shared__ double sw[4][6];
-#pragma unroll
-  for (int q = 0; q < 6; q++) {
-    const double r = wave_sum(s[q]);
-    if ((threadIdx.x & 63) == 0) sw[threadIdx.x >> 6][q] = r;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-#pragma unroll
-    for (int q = 0; q < 6; q++) out[6 * (size_t)j + q] = ((sw[0][q] + sw[1][q]) + sw[2][q]) + sw[3][q];
-  }
+  wg_join<6>(s, out + 6 * (size_t)j);
 }

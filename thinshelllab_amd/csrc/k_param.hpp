@@ -236,15 +236,24 @@ __global__ void __launch_bounds__(PG_THREADS) k_pg_final(PgTable tab, const doub
   if (threadIdx.x == 0) { cnt_out[0] = k1; cnt_out[1] = k2; }
 }
 
-// soft handles: {k_handle} -- the gradient row of k_handle_grad with k_handle = 1, w_i (x - t_i) at vertex v_i; one lane per handle
+// soft handles: {k_handle} -- the gradient rows of k_handle_grad with k_handle = 1, w_i b_a (p_i - t_i) at the corners v_a of handle i (class 5):
+// -w_i sum_a b_a p_{v_a} . (p_i - t_i) over free dofs; one lane per handle
+template <int NC>
 __global__ void __launch_bounds__(PG_THREADS) k_pg_handle(HandleArgs A, const double* __restrict__ pos, const double* __restrict__ p,
                                                           const int* __restrict__ frozen, double* __restrict__ part) {
   __shared__ double sm[PG_THREADS / 64];
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   double v[1] = {0.0};
   if (i < A.n) {
-    const int vi = A.v[i];
-    v[0] = -pg_dot_free(p, frozen, vi, (ld3(pos, vi) - ld3(A.t, i)) * A.w[i]);
+    const d3 r = handle_point<NC>(A, pos, i) - ld3(A.t, i);
+    if constexpr (NC == 1) {
+      v[0] = -pg_dot_free(p, frozen, A.cv[i], r * A.w[i]);
+    } else {
+      double s = 0.0;
+#pragma unroll
+      for (int a = 0; a < 3; a++) s += pg_dot_free(p, frozen, A.cv[3 * (size_t)i + a], r * (A.w[i] * A.cb[3 * (size_t)i + a]));
+      v[0] = -s;
+    }
   }
   pg_block_write<1>(v, i < A.n ? 0 : -1, 1, part, sm);
 }

@@ -258,21 +258,19 @@ struct tsl_ctx {
   DevBuf<int> diag_blk;             // NV
   std::vector<int> h_frozen;
   std::vector<double> h_mass;
-  // soft handles (tsl_set_handles, k_handle.hpp): vertex, weight and target of each, copies the context owns; the handle kernels run while
-  // n_handle > 0 and k_handle != 0
-  int n_handle = 0;
+  // soft handles (tsl_set_handles, tsl_set_handles_on_faces; k_handle.hpp): one list of n_handle handles with hd_nc corners each -- 1: a vertex list,
+  // 3: a face list -- as copies the context owns: corner vertices and coordinates, weights, targets, and the gather lists of handle_host.hpp.  Frames,
+  // targets and read-outs go by handle index.  The handle kernels run while n_handle > 0 and k_handle != 0
+  int n_handle = 0, hd_nc = 1;
   double k_handle = 0.0;
-  DevBuf<int> hd_v;
-  DevBuf<double> hd_w, hd_t, hd_out;   // n, n x 3, n x 3 (read-outs of tsl_handle_force / tsl_handle_grad)
-  // handles at barycentric points of faces (tsl_set_handles_on_faces, k_handle_face.hpp): a context holds a vertex list (hd_v) or a face list
-  // (handle_on_faces: hf_fv, hf_b and the gather lists of handle_face_host.hpp); weights, targets, read-outs and frames are shared, by handle index
-  bool handle_on_faces = false;
-  int n_hf_vert = 0, n_hf_blk = 0;   // touched vertices, touched blocks
-  DevBuf<int> hf_fv, hf_vl_v, hf_vl_ptr, hf_vl_ent, hf_bl_addr, hf_bl_ptr, hf_bl_ent;
-  DevBuf<double> hf_b;               // n x 3
+  DevBuf<int> hd_cv;                   // n x nc
+  DevBuf<double> hd_cb;                // n x nc (none for nc = 1: not read)
+  DevBuf<double> hd_w, hd_t, hd_out;   // n, n x 3, n x 3 (read-outs of tsl_handle_points / tsl_handle_force / tsl_handle_grad)
+  int n_hd_vert = 0, n_hd_blk = 0;     // touched vertices, touched blocks
+  DevBuf<int> hd_vl_v, hd_vl_ptr, hd_vl_ent, hd_bl_addr, hd_bl_ptr, hd_bl_ent;
   std::vector<int> h_faces;          // tot_NF x 3, the scene's global face table (host copy)
   // rigid frames of the handles (tsl_set_handle_frames, k_frame.hpp): frame and local point of each handle, the handles of every frame as a CSR,
-  // the poses as (c, R); k_frame_targets writes the framed rows of hd_t.  tsl_set_handles resets n_frame to 0
+  // the poses as (c, R); k_frame_targets writes the framed rows of hd_t.  A new handle list resets n_frame to 0
   int n_frame = 0;
   DevBuf<int> fr_of, fr_ptr, fr_idx;              // n_handle, n_frame + 1, number of framed handles
   DevBuf<double> fr_local, fr_c, fr_R, fr_out;    // n_handle x 3, n_frame x 3, n_frame x 9, n_frame x 6 (read-outs of tsl_frame_wrench / tsl_frame_grad)

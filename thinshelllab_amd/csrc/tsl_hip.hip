@@ -14,15 +14,9 @@
 #include "k_cloth.hpp"
 #include "k_contact.hpp"
 #include "k_fem.hpp"
-#include "k_frame.hpp"
-#include "k_handle.hpp"
-#include "k_handle_face.hpp"
 #include "k_mg.hpp"
 #include "k_param.hpp"
 #include "k_solver.hpp"
-#include "frame_host.hpp"
-#include "handle_face_host.hpp"
-#include "handle_host.hpp"
 #include "param_keys.hpp"
 #include "tsl_ctx.hpp"
 
@@ -54,6 +48,7 @@ int tsl_fail(const char* fmt, ...) {
 #define DOT_BLOCKS 120  // one f64 atomic per wave into a single address: more blocks only add contention (30 us at 600 blocks)
 static inline int nblk(long n, int b) { return (int)((n + b - 1) / b); }
 static inline int gsz(size_t n) { size_t b = (n + 255) / 256; return (int)std::min<size_t>(std::max<size_t>(b, 1), 4096); }
+#include "handle_api.hpp"
 
 // ------------------------------------------------------------------------------------------------
 static int mg_build(tsl_ctx* c, const tsl_scene_desc* d);
@@ -83,14 +78,6 @@ static TetArgs tet_args(tsl_ctx* c) {
   TetArgs A;
   A.n_tet = c->n_tet; A.el = c->d_el.p; A.tv = c->tet_v.p; A.tel = c->tet_el.p; A.B = c->tet_B.p; A.W = c->tet_W.p; A.gstage = nullptr;
   return A;
-}
-static HandleArgs handle_args(tsl_ctx* c) { return HandleArgs{c->n_handle, c->hd_v.p, c->hd_w.p, c->hd_t.p, c->k_handle}; }
-// the handle kernels of an energy / assembly / reverse step run only while this holds: without it the launches are the ones they were
-static bool handles_on(const tsl_ctx* c) { return c->n_handle > 0 && c->k_handle != 0.0; }
-// a face list (tsl_set_handles_on_faces, k_handle_face.hpp): the same places, the face kernels
-static FaceHandleArgs hface_args(tsl_ctx* c) { return FaceHandleArgs{c->n_handle, c->hf_fv.p, c->hf_b.p, c->hd_w.p, c->hd_t.p, c->k_handle}; }
-static FaceHandleLists_dev hface_lists(tsl_ctx* c) {
-  return FaceHandleLists_dev{c->n_hf_vert, c->n_hf_blk, c->hf_vl_v.p, c->hf_vl_ptr.p, c->hf_vl_ent.p, c->hf_bl_addr.p, c->hf_bl_ptr.p, c->hf_bl_ent.p};
 }
 static ContactArgs contact_args(tsl_ctx* c) {
   ContactArgs A;
@@ -349,201 +336,6 @@ extern "C" int tsl_set_gravity(tsl_ctx* c, const double* g) {
   return 0;
 }
 
-// Rigid frames of the handles (k_frame.hpp), used by the handle entry points below and defined behind them
-static void frames_release(tsl_ctx* c) {
-  c->n_frame = 0;
-  c->fr_of.release(); c->fr_ptr.release(); c->fr_idx.release(); c->fr_local.release(); c->fr_c.release(); c->fr_R.release(); c->fr_out.release();
-}
-static FrameArgs frame_args(tsl_ctx* c) { return FrameArgs{c->n_frame, c->fr_of.p, c->fr_local.p, c->fr_c.p, c->fr_R.p, c->fr_ptr.p, c->fr_idx.p}; }
-// the framed rows of the target buffer from the poses as they stand (nothing without frames); the caller synchronises
-static void frame_targets_launch(tsl_ctx* c) {
-  if (c->n_frame == 0 || c->n_handle == 0) return;
-  hipLaunchKernelGGL(k_frame_targets, dim3(nblk(c->n_handle, 256)), dim3(256), 0, c->stream, c->n_handle, frame_args(c), c->hd_t.p);
-}
-
-static void hface_release(tsl_ctx* c) {
-  c->handle_on_faces = false;
-  c->n_hf_vert = c->n_hf_blk = 0;
-  c->hf_fv.release(); c->hf_b.release(); c->hf_vl_v.release(); c->hf_vl_ptr.release(); c->hf_vl_ent.release();
-  c->hf_bl_addr.release(); c->hf_bl_ptr.release(); c->hf_bl_ent.release();
-}
-// Soft handles (k_handle.hpp): the lists are checked on the host (handle_host.hpp) and copied into buffers of the context; targets start at zero
-extern "C" int tsl_set_handles(tsl_ctx* c, const int32_t* verts, const double* weights, int32_t n) {
-  Scope scope(c);
-  (void)hipStreamSynchronize(c->stream);
-  std::string err;
-  if (handle_validate(c->NV, verts, weights, n, err)) return tsl_fail("tsl_set_handles: %s", err.c_str());
-  c->mg_omega_valid = false;
-  c->ds.anorm_valid = false;   // (the scale of the operator may change: |H|_inf is formed again when a refinement asks for it)
-  c->n_handle = 0;
-  frames_release(c);   // (the handle list changed: the frames went with it)
-  hface_release(c);    // (a context holds a vertex list or a face list)
-  if (n == 0) { c->hd_v.release(); c->hd_w.release(); c->hd_t.release(); c->hd_out.release(); return 0; }
-  std::vector<int> hv(verts, verts + n);
-  std::vector<double> hw(n, 1.0);
-  if (weights) hw.assign(weights, weights + n);
-  TSL_TRY(c->hd_v.upload(hv));
-  TSL_TRY(c->hd_w.upload(hw));
-  TSL_TRY(c->hd_t.upload(std::vector<double>(3 * (size_t)n, 0.0)));
-  TSL_TRY(c->hd_out.alloc(3 * (size_t)n));
-  c->n_handle = n;
-  return 0;
-}
-// Handles at barycentric points of faces (k_handle_face.hpp): the list is checked and the gather lists are built on the host (handle_face_host.hpp)
-// from the pattern the context keeps, before anything of the previous list is touched; conventions of tsl_set_handles
-extern "C" int tsl_set_handles_on_faces(tsl_ctx* c, const int32_t* faces, const double* bary, const double* weights, int32_t n) {
-  Scope scope(c);
-  (void)hipStreamSynchronize(c->stream);
-  std::string err;
-  if (handle_face_validate(c->NV, c->NF, c->h_faces.data(), faces, bary, weights, n, err)) return tsl_fail("tsl_set_handles_on_faces: %s", err.c_str());
-  FaceHandleLists L;
-  if (n > 0) {
-    Pattern P;   // (lookup reads the rows, their positions and the slice offsets)
-    P.rows = c->h_rows; P.rowpos = c->h_rowpos; P.slice_off = c->h_slice_off;
-    if (handle_face_lists(P, c->h_faces.data(), faces, n, L, err)) return tsl_fail("tsl_set_handles_on_faces: %s", err.c_str());
-  }
-  c->mg_omega_valid = false;
-  c->ds.anorm_valid = false;
-  c->n_handle = 0;
-  frames_release(c);
-  hface_release(c);
-  c->hd_v.release();
-  if (n == 0) { c->hd_w.release(); c->hd_t.release(); c->hd_out.release(); return 0; }
-  std::vector<double> hw(n, 1.0);
-  if (weights) hw.assign(weights, weights + n);
-  TSL_TRY(c->hf_fv.upload(L.fv));
-  TSL_TRY(c->hf_b.upload(std::vector<double>(bary, bary + 3 * (size_t)n)));
-  TSL_TRY(c->hf_vl_v.upload(L.vl_v)); TSL_TRY(c->hf_vl_ptr.upload(L.vl_ptr)); TSL_TRY(c->hf_vl_ent.upload(L.vl_ent));
-  TSL_TRY(c->hf_bl_addr.upload(L.bl_addr)); TSL_TRY(c->hf_bl_ptr.upload(L.bl_ptr)); TSL_TRY(c->hf_bl_ent.upload(L.bl_ent));
-  TSL_TRY(c->hd_w.upload(hw));
-  TSL_TRY(c->hd_t.upload(std::vector<double>(3 * (size_t)n, 0.0)));
-  TSL_TRY(c->hd_out.alloc(3 * (size_t)n));
-  c->n_hf_vert = (int)L.vl_v.size(); c->n_hf_blk = (int)L.bl_addr.size();
-  c->handle_on_faces = true;
-  c->n_handle = n;
-  return 0;
-}
-extern "C" int tsl_set_handle_targets(tsl_ctx* c, const double* targets) {
-  Scope scope(c);
-  (void)hipStreamSynchronize(c->stream);
-  if (c->n_handle == 0) return 0;
-  if (!targets) return tsl_fail("tsl_set_handle_targets: null targets for %d handles", c->n_handle);
-  HIP_OK(hipMemcpy(c->hd_t.p, targets, 3 * (size_t)c->n_handle * sizeof(double), hipMemcpyHostToDevice));
-  if (c->n_frame > 0) {   // the rows of framed handles follow their frame, whichever of the targets and the poses was set last
-    frame_targets_launch(c);
-    HIP_OK(hipGetLastError());
-    HIP_OK(hipStreamSynchronize(c->stream));
-  }
-  return 0;
-}
-// read-outs, one value per handle and axis: the kernel writes hd_out, one copy to the host, one synchronisation
-static int handle_readout(tsl_ctx* c, double* out_host) {
-  HIP_OK(hipGetLastError());
-  HIP_OK(hipMemcpyAsync(out_host, c->hd_out.p, 3 * (size_t)c->n_handle * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  HIP_OK(hipStreamSynchronize(c->stream));
-  return 0;
-}
-extern "C" int tsl_handle_force(tsl_ctx* c, const double* pos, double* out_host) {
-  Scope scope(c);
-  if (c->n_handle == 0) return 0;
-  if (!pos || !out_host) return tsl_fail("tsl_handle_force: null argument");
-  if (c->handle_on_faces) hipLaunchKernelGGL(k_hface_force, dim3(nblk(c->n_handle, 256)), dim3(256), 0, c->stream, hface_args(c), pos, c->hd_out.p);
-  else hipLaunchKernelGGL(k_handle_force, dim3(nblk(c->n_handle, 256)), dim3(256), 0, c->stream, handle_args(c), pos, c->hd_out.p);
-  return handle_readout(c, out_host);
-}
-extern "C" int tsl_handle_points(tsl_ctx* c, const double* pos, double* out_host) {
-  Scope scope(c);
-  if (c->n_handle == 0) return 0;
-  if (!pos || !out_host) return tsl_fail("tsl_handle_points: null argument");
-  if (c->handle_on_faces) hipLaunchKernelGGL(k_hface_points, dim3(nblk(c->n_handle, 256)), dim3(256), 0, c->stream, hface_args(c), pos, c->hd_out.p);
-  else hipLaunchKernelGGL(k_handle_points, dim3(nblk(c->n_handle, 256)), dim3(256), 0, c->stream, handle_args(c), pos, c->hd_out.p);
-  return handle_readout(c, out_host);
-}
-extern "C" int tsl_handle_grad(tsl_ctx* c, const double* p_dev, double* out_host) {
-  Scope scope(c);
-  if (c->n_handle == 0) return 0;
-  if (!out_host) return tsl_fail("tsl_handle_grad: null argument");
-  const double* p = p_dev ? p_dev : (const double*)c->pdir.p;
-  if (c->handle_on_faces) hipLaunchKernelGGL(k_hface_backprop, dim3(nblk(c->n_handle, 256)), dim3(256), 0, c->stream, hface_args(c), p, (const int*)c->frozen.p, c->hd_out.p);
-  else hipLaunchKernelGGL(k_handle_backprop, dim3(nblk(c->n_handle, 256)), dim3(256), 0, c->stream, handle_args(c), p, (const int*)c->frozen.p, c->hd_out.p);
-  return handle_readout(c, out_host);
-}
-
-// Rigid frames for the handles (k_frame.hpp): lists checked and the CSR built on the host (frame_host.hpp), copies the context owns; conventions of
-// tsl_set_handles.  Poses start at the identity at the origin
-extern "C" int tsl_set_handle_frames(tsl_ctx* c, const int32_t* frame_of, const double* local, int32_t n_frame) {
-  Scope scope(c);
-  (void)hipStreamSynchronize(c->stream);
-  std::string err;
-  if (frame_validate(c->n_handle, frame_of, local, n_frame, err)) return tsl_fail("tsl_set_handle_frames: %s", err.c_str());
-  frames_release(c);
-  if (n_frame == 0) return 0;
-  const size_t n = (size_t)c->n_handle;
-  std::vector<int> ptr, idx;
-  frame_csr(c->n_handle, frame_of, n_frame, ptr, idx);
-  std::vector<double> hl(local, local + 3 * n), hR(9 * (size_t)n_frame, 0.0);
-  for (size_t i = 0; i < n; i++)
-    if (frame_of[i] < 0) hl[3 * i] = hl[3 * i + 1] = hl[3 * i + 2] = 0.0;   // (never read; keeps what is uploaded finite)
-  for (int j = 0; j < n_frame; j++) hR[9 * (size_t)j] = hR[9 * (size_t)j + 4] = hR[9 * (size_t)j + 8] = 1.0;
-  TSL_TRY(c->fr_of.upload(std::vector<int>(frame_of, frame_of + n)));
-  TSL_TRY(c->fr_local.upload(hl));
-  TSL_TRY(c->fr_ptr.upload(ptr));
-  TSL_TRY(c->fr_idx.upload(idx));
-  TSL_TRY(c->fr_c.upload(std::vector<double>(3 * (size_t)n_frame, 0.0)));
-  TSL_TRY(c->fr_R.upload(hR));
-  TSL_TRY(c->fr_out.alloc(6 * (size_t)n_frame));
-  c->n_frame = n_frame;
-  frame_targets_launch(c);
-  HIP_OK(hipGetLastError());
-  HIP_OK(hipStreamSynchronize(c->stream));
-  return 0;
-}
-extern "C" int tsl_set_frame_poses(tsl_ctx* c, const double* pos, const double* quat) {
-  Scope scope(c);
-  (void)hipStreamSynchronize(c->stream);
-  if (c->n_frame == 0) return 0;
-  std::string err;
-  std::vector<double> hc, hR;
-  if (frame_pose_matrices(pos, quat, c->n_frame, hc, hR, err)) return tsl_fail("tsl_set_frame_poses: %s", err.c_str());
-  HIP_OK(hipMemcpy(c->fr_c.p, hc.data(), hc.size() * sizeof(double), hipMemcpyHostToDevice));
-  HIP_OK(hipMemcpy(c->fr_R.p, hR.data(), hR.size() * sizeof(double), hipMemcpyHostToDevice));
-  frame_targets_launch(c);
-  HIP_OK(hipGetLastError());
-  HIP_OK(hipStreamSynchronize(c->stream));
-  return 0;
-}
-extern "C" int tsl_handle_targets(tsl_ctx* c, double* out_host) {
-  Scope scope(c);
-  if (c->n_handle == 0) return 0;
-  if (!out_host) return tsl_fail("tsl_handle_targets: null argument");
-  HIP_OK(hipMemcpyAsync(out_host, c->hd_t.p, 3 * (size_t)c->n_handle * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  HIP_OK(hipStreamSynchronize(c->stream));
-  return 0;
-}
-// read-outs, six values per frame: one workgroup per frame writes fr_out, one copy to the host, one synchronisation; k_handle = 0: zeros, no launch
-template <int MODE>
-static int frame_readout(tsl_ctx* c, const double* vec, double* out_host) {
-  if (c->k_handle == 0.0) { std::fill(out_host, out_host + 6 * (size_t)c->n_frame, 0.0); return 0; }
-  if (c->handle_on_faces) hipLaunchKernelGGL(k_hface_frame_reduce<MODE>, dim3(c->n_frame), dim3(256), 0, c->stream, hface_args(c), frame_args(c), vec, (const int*)c->frozen.p, c->fr_out.p);
-  else hipLaunchKernelGGL(k_frame_reduce<MODE>, dim3(c->n_frame), dim3(256), 0, c->stream, handle_args(c), frame_args(c), vec, (const int*)c->frozen.p, c->fr_out.p);
-  HIP_OK(hipGetLastError());
-  HIP_OK(hipMemcpyAsync(out_host, c->fr_out.p, 6 * (size_t)c->n_frame * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  HIP_OK(hipStreamSynchronize(c->stream));
-  return 0;
-}
-extern "C" int tsl_frame_wrench(tsl_ctx* c, const double* pos, double* out_host) {
-  Scope scope(c);
-  if (c->n_frame == 0) return 0;
-  if (!pos || !out_host) return tsl_fail("tsl_frame_wrench: null argument");
-  return frame_readout<FRAME_WRENCH>(c, pos, out_host);
-}
-extern "C" int tsl_frame_grad(tsl_ctx* c, const double* p_dev, double* out_host) {
-  Scope scope(c);
-  if (c->n_frame == 0) return 0;
-  if (!out_host) return tsl_fail("tsl_frame_grad: null argument");
-  return frame_readout<FRAME_GRAD>(c, p_dev ? p_dev : (const double*)c->pdir.p, out_host);
-}
-
 // ------------------------------------------------------------------------------------------------
 template <bool STVK>   // STVK: some cloth has membrane = 1 (cface_energy_sel)
 TSL_DEV void energy_body(VertArgs VA, ClothArgs CA, TetArgs TA, const double* __restrict__ pos, const double* __restrict__ prev,
@@ -603,8 +395,7 @@ static int energy_async(tsl_ctx* c, const double* pos, const double* prev, const
   else hipLaunchKernelGGL(k_energy, dim3(nb1), dim3(256), 0, s, vert_args(c), cloth_args(c), tet_args(c), pos, prev, vel, ref, c->e_part.p);
   if (nb2 > 0) hipLaunchKernelGGL(k_contact_energy, dim3(nb2), dim3(64), 0, s, nvf, contact_args(c), pos, c->e_part.p + nb1);
   if (nb3 > 0) hipLaunchKernelGGL(k_ee_energy, dim3(nb3), dim3(64), 0, s, c->nc_ee, ee_args(contact_args(c), nvf), pos, c->e_part.p + nb1 + nb2);
-  if (nb4 > 0 && c->handle_on_faces) hipLaunchKernelGGL(k_hface_energy, dim3(nb4), dim3(256), 0, s, hface_args(c), pos, c->e_part.p + nb1 + nb2 + nb3);
-  else if (nb4 > 0) hipLaunchKernelGGL(k_handle_energy, dim3(nb4), dim3(256), 0, s, handle_args(c), pos, c->e_part.p + nb1 + nb2 + nb3);
+  if (nb4 > 0) handle_dispatch(c, [&](auto NC) { hipLaunchKernelGGL(k_handle_energy<NC>, dim3(nb4), dim3(256), 0, s, handle_args(c), pos, c->e_part.p + nb1 + nb2 + nb3); });
   hipLaunchKernelGGL(k_energy_final, dim3(1), dim3(256), 0, s, nb1 + nb2 + nb3 + nb4, (const double*)c->e_part.p, &SC(c)->energy);
   return 0;
 }
@@ -689,21 +480,6 @@ static void cloth_hess_face_launch(tsl_ctx* c, hipStream_t s, const ClothArgs& C
     else if (lit) hipLaunchKernelGGL((k_cloth_hess_face<false, true>), g, b, 0, s, CA, pos, ref, c->quirk.p, spd, c->cg_frec.p, S);
     else hipLaunchKernelGGL((k_cloth_hess_face<false>), g, b, 0, s, CA, pos, ref, c->quirk.p, spd, c->cg_frec.p, S);
   }
-}
-
-// Soft handles in an assembly: their gradient rows and diagonal entries behind the vertex terms on the same stream (nothing while no handle is on)
-static void handle_assemble_launch(tsl_ctx* c, hipStream_t s, const double* pos, double* grad) {
-  if (!handles_on(c)) return;
-  if (c->handle_on_faces) {   // one lane per touched vertex / per touched block (k_handle_face.hpp)
-    const FaceHandleArgs FA = hface_args(c);
-    const FaceHandleLists_dev FL = hface_lists(c);
-    if (grad) hipLaunchKernelGGL(k_hface_grad, dim3(nblk(FL.n_vert, 256)), dim3(256), 0, s, FA, FL, pos, grad);
-    hipLaunchKernelGGL(k_hface_hess, dim3(nblk(FL.n_blk, 256)), dim3(256), 0, s, FA, FL, c->vals_full.p);
-    return;
-  }
-  const HandleArgs HA = handle_args(c);
-  if (grad) hipLaunchKernelGGL(k_handle_grad, dim3(nblk(HA.n, 256)), dim3(256), 0, s, HA, pos, grad);
-  hipLaunchKernelGGL(k_handle_hess, dim3(nblk(HA.n, 256)), dim3(256), 0, s, HA, (const int*)c->diag_blk.p, c->vals_full.p);
 }
 
 // GPU work of one assembly (no host state, no allocation: assemble() below prepares both, so that the launches can be captured into a graph)
@@ -2297,8 +2073,7 @@ extern "C" int tsl_param_grad_keys(tsl_ctx* c, const double* pos, const double* 
     if (c->n_stvk > 0) hipLaunchKernelGGL(k_pg_face<true>, dim3(nb[0]), dim3(PG_THREADS), 0, s, cloth_args(c), n_cloth, pos, p, fz, part + off[0], stvk_args(c));
     else hipLaunchKernelGGL(k_pg_face<false>, dim3(nb[0]), dim3(PG_THREADS), 0, s, cloth_args(c), n_cloth, pos, p, fz, part + off[0], stvk_args(c));
   }
-  if (need[5] && nb[5] && c->handle_on_faces) hipLaunchKernelGGL(k_pg_hface, dim3(nb[5]), dim3(PG_THREADS), 0, s, hface_args(c), pos, p, fz, part + off[5]);
-  else if (need[5] && nb[5]) hipLaunchKernelGGL(k_pg_handle, dim3(nb[5]), dim3(PG_THREADS), 0, s, handle_args(c), pos, p, fz, part + off[5]);
+  if (need[5] && nb[5]) handle_dispatch(c, [&](auto NC) { hipLaunchKernelGGL(k_pg_handle<NC>, dim3(nb[5]), dim3(PG_THREADS), 0, s, handle_args(c), pos, p, fz, part + off[5]); });
   if (need[4] && nb[4]) hipLaunchKernelGGL(k_pg_stvk, dim3(nb[4]), dim3(PG_THREADS), 0, s, cloth_args(c), n_cloth, pos, p, fz, part + off[4], stvk_args(c));
   if (need[1] && nb[1]) hipLaunchKernelGGL(k_pg_hinge, dim3(nb[1]), dim3(PG_THREADS), 0, s, cloth_args(c), n_cloth, pos, ref, p, fz, part + off[1]);
   if (need[2] && nb[2]) hipLaunchKernelGGL(k_pg_tet, dim3(nb[2]), dim3(PG_THREADS), 0, s, tet_args(c), n_el, pos, p, fz, part + off[2]);
