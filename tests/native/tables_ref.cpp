@@ -1,5 +1,5 @@
 // Test shim (never part of libtsl_hip.so): a flat C view of the host tables of a scene (csrc/scene_tables.hpp) and of the indexed-key parser
-// (csrc/param_keys.hpp), for tests/test_ctx_tables.py.  tables_names lists the arrays as "name:type," (i int32, u uint32, d double, l int64);
+// and the differentiated keys' table, resolver and partial layout (csrc/param_keys.hpp), for tests/test_ctx_tables.py.  tables_names lists the arrays as "name:type," (i int32, u uint32, d double, l int64);
 // tables_sizes builds the tables and reports the length of every array; tables_copy builds them again and copies every array out.
 #include <cstring>
 
@@ -78,4 +78,43 @@ extern "C" int parse_indexed_key_c(const char* key, int* family, long long* inde
   *family = (int)k.family; *index = k.index;
   if (field && fieldlen > 0) { strncpy(field, k.field.c_str(), fieldlen - 1); field[fieldlen - 1] = 0; }
   return rc;
+}
+
+// pg_resolve_key as C: the return code, (class, row), the message
+extern "C" int pg_resolve_key_c(const char* key, int n_cloth, int n_el, int* cls, int* row, char* err, int errlen) {
+  PgRow r{PG_NCLASS, -1};
+  std::string e;
+  const int rc = pg_resolve_key(key, n_cloth, n_el, r, e);
+  *cls = (int)r.cls; *row = r.row;
+  if (err && errlen > 0) { strncpy(err, e.c_str(), errlen - 1); err[errlen - 1] = 0; }
+  return rc;
+}
+
+extern "C" const char* pg_supported_keys_c(void) {
+  static const std::string s = pg_supported_keys();
+  return s.c_str();
+}
+
+// pg_layout as C.  nb, need: PG_NCLASS entries each; the keys as (cls[j], row[j]), j < n_keys.  Out: off (PG_NCLASS entries), total, per key its
+// (key_off[j], key_cnt[j]) read from the chunk tables, and the length of every chunk (chunk_n, at most max_chunks of them); returns the number of
+// chunks, -1 on failure (message in err)
+extern "C" int pg_layout_c(int n_cloth, int n_el, const int* nb, const int* need, const int* cls, const int* row, int n_keys, long long* off, long long* total,
+                           int* key_off, int* key_cnt, int* chunk_n, int max_chunks, char* err, int errlen) {
+  bool nd[PG_NCLASS];
+  for (int q = 0; q < PG_NCLASS; q++) nd[q] = need[q] != 0;
+  std::vector<PgRow> keys(n_keys);
+  for (int j = 0; j < n_keys; j++) keys[j] = PgRow{(PgClass)cls[j], row[j]};
+  PgLayout L;
+  std::string e;
+  const int rc = pg_layout(n_cloth, n_el, nb, nd, keys, L, e);
+  if (err && errlen > 0) { strncpy(err, e.c_str(), errlen - 1); err[errlen - 1] = 0; }
+  if (rc) return -1;
+  for (int q = 0; q < PG_NCLASS; q++) off[q] = (long long)L.off[q];
+  *total = (long long)L.total;
+  int j = 0;
+  for (size_t k = 0; k < L.chunks.size(); k++) {
+    if ((int)k < max_chunks) chunk_n[k] = L.chunks[k].n;
+    for (int i = 0; i < L.chunks[k].n; i++, j++) { key_off[j] = L.chunks[k].off[i]; key_cnt[j] = L.chunks[k].cnt[i]; }
+  }
+  return j == n_keys ? (int)L.chunks.size() : -1;
 }

@@ -1,4 +1,5 @@
-"""The host tables tsl_ctx_create uploads (thinshelllab_amd/csrc/scene_tables.hpp) and the indexed-key parser (csrc/param_keys.hpp), on the CPU:
+"""The host tables tsl_ctx_create uploads (thinshelllab_amd/csrc/scene_tables.hpp), the indexed-key parser and the differentiated keys of
+tsl_param_grad_keys -- their table, key -> (class, row) and the layout of the partial sums (csrc/param_keys.hpp) -- on the CPU:
 tests/native/tables_ref.cpp compiles the two headers into a shim, the scenes come from the product's cloth and body builders through
 context.scene_desc (the struct the engine itself hands to the library), and every table is compared exactly with its restatement in
 tests/scene_tables_numpy.py.  The properties the kernels rely on are asserted one by one as well, so that a failure names the table."""
@@ -30,6 +31,10 @@ def shim():
     L.tables_sizes.argtypes = [C.POINTER(SceneDesc), C.POINTER(C.c_longlong), C.c_char_p, C.c_int]
     L.tables_copy.argtypes = [C.POINTER(SceneDesc), C.POINTER(C.c_void_p)]
     L.parse_indexed_key_c.argtypes = [C.c_char_p, C.POINTER(C.c_int), C.POINTER(C.c_longlong), C.c_char_p, C.c_int]
+    L.pg_resolve_key_c.argtypes = [C.c_char_p, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_char_p, C.c_int]
+    L.pg_supported_keys_c.restype = C.c_char_p
+    IP, LP = C.POINTER(C.c_int), C.POINTER(C.c_longlong)
+    L.pg_layout_c.argtypes = [C.c_int, C.c_int, IP, IP, IP, IP, C.c_int, LP, LP, IP, IP, IP, C.c_int, C.c_char_p, C.c_int]
     return L
 
 
@@ -239,3 +244,108 @@ def test_indexed_keys_rejected(shim, key):
 def test_keys_of_no_indexed_family(shim, key):
     rc, fam, _, _ = _parse(shim, key)
     assert (rc, fam) == (0, FAMILY["none"])
+
+
+# ------------------------------------------------------------------------------------------------ differentiated keys (tsl_param_grad_keys)
+PG = {"face": 0, "hinge": 1, "tet": 2, "contact": 3, "stvk": 4, "handle": 5}
+# the table of csrc/param_keys.hpp restated: name -> (class, row among the rows of one cloth / body, rows per cloth / body), plain name -> (class, row)
+CLOTH_FIELDS = {"Kl": ("face", 0, 2), "Ka": ("face", 1, 2), "Kb": ("hinge", 0, 1), "stvk_mu": ("stvk", 0, 2), "stvk_lam": ("stvk", 1, 2)}
+ELASTIC_FIELDS = {"mu": ("tet", 0, 2), "lam": ("tet", 1, 2)}
+PLAIN_KEYS = {"k_contact": ("contact", 0), "mu_cloth_elastic": ("contact", 1), "mu_cloth_cloth": ("contact", 2), "k_handle": ("handle", 0)}
+SUPPORTED = "cloth<i>.Kl|Ka|Kb|stvk_mu|stvk_lam, elastic<i>.mu|lam, k_contact, mu_cloth_elastic, mu_cloth_cloth, k_handle"
+N_CLOTH, N_EL = 2, 1          # the scene description of the key tests
+
+
+def _supported(n_cloth, n_el):
+    """key -> (class number, row) of every differentiated key of a scene with these counts"""
+    want = {}
+    for fam, n, fields in (("cloth", n_cloth, CLOTH_FIELDS), ("elastic", n_el, ELASTIC_FIELDS)):
+        for i in range(n):
+            for f, (cls, r, per) in fields.items():
+                want[f"{fam}{i}.{f}"] = (PG[cls], r + per * i)
+    want.update({k: (PG[cls], r) for k, (cls, r) in PLAIN_KEYS.items()})
+    return want
+
+
+def _class_rows(n_cloth, n_el):
+    rows = [0] * len(PG)
+    for cls, row in _supported(n_cloth, n_el).values():
+        rows[cls] = max(rows[cls], row + 1)
+    return rows
+
+
+def _resolve(shim, key, n_cloth, n_el):
+    cls, row, err = C.c_int(-7), C.c_int(-7), C.create_string_buffer(512)
+    rc = shim.pg_resolve_key_c(key.encode(), n_cloth, n_el, C.byref(cls), C.byref(row), err, 512)
+    return rc, cls.value, row.value, err.value.decode()
+
+
+def _layout(shim, nb, need, keys, n_cloth=N_CLOTH, n_el=N_EL):
+    """(offsets per class, total, [(offset, count) per key], chunk lengths), or the message of the failure"""
+    n = len(keys)
+    I = lambda a: (C.c_int * max(len(a), 1))(*a)
+    off, total = (C.c_longlong * len(PG))(), C.c_longlong(-1)
+    koff, kcnt, chunk_n, err = I([0] * n), I([0] * n), I([0] * 8), C.create_string_buffer(256)
+    rc = shim.pg_layout_c(n_cloth, n_el, I(nb), I([int(x) for x in need]), I([k[0] for k in keys]), I([k[1] for k in keys]), n, off, C.byref(total), koff, kcnt, chunk_n, 8, err, 256)
+    if rc < 0:
+        return err.value.decode()
+    return list(off), total.value, list(zip(koff[:n], kcnt[:n])), list(chunk_n[:rc])
+
+
+def test_every_supported_key_resolves_to_its_class_and_row(shim):
+    want = _supported(N_CLOTH, N_EL)
+    assert len(want) == 5 * N_CLOTH + 2 * N_EL + 4
+    for key, (cls, row) in want.items():
+        assert _resolve(shim, key, N_CLOTH, N_EL) == (0, cls, row, ""), key
+    assert len(set(want.values())) == len(want)          # no two keys share a row
+    assert shim.pg_supported_keys_c().decode() == SUPPORTED
+
+
+@pytest.mark.parametrize("key", ["no_such_key", "eps_contact", "damping", "cloth0.k_angle", "elastic0.mu", "cloth1.Kl", "cloth-1.Kb", "cg_tol", "cloth+0.Kl", "cloth 0.Kl"])
+def test_bad_keys_fail_and_the_message_names_them(shim, key):
+    """the keys of tests/test_gpu_param_grad.py::test_errors_name_the_key on its scene: one cloth, no body"""
+    rc, _, _, err = _resolve(shim, key, 1, 0)
+    assert rc == -1 and key in err and err.startswith("tsl_param_grad_keys: ")
+    if key in ("no_such_key", "eps_contact", "damping", "cloth0.k_angle", "cg_tol"):
+        assert err == f"tsl_param_grad_keys: {key} is not a differentiated key (supported: {SUPPORTED})"
+    assert _resolve(shim, "cloth0.Kl", 1, 0)[:3] == (0, PG["face"], 0)
+
+
+NB = [2, 1, 0, 3, 2, 1]          # workgroups per class; no tet at all
+
+
+@pytest.mark.parametrize("need", [[q == k for q in range(6)] for k in range(6)] + [[True] * 6], ids=lambda n: "".join("01"[x] for x in n))
+def test_layout_offsets_are_the_running_sum_over_the_needed_classes(shim, need):
+    rows = _class_rows(N_CLOTH, N_EL)
+    assert rows == [4, 2, 2, 3, 4, 1]
+    keys = [v for v in _supported(N_CLOTH, N_EL).values() if need[v[0]]]
+    off, total, per_key, chunks = _layout(shim, NB, need, keys)
+    run = 0
+    for q in range(6):
+        assert off[q] == run, q
+        run += rows[q] * NB[q] if need[q] else 0
+    assert total == run and chunks == ([len(keys)] if keys else [])
+    assert per_key == [(off[cls] + row * NB[cls], NB[cls]) for cls, row in keys]
+    if need[PG["tet"]]:          # a class without workgroups holds no partials: its keys sum nothing, the class behind it starts where it does
+        assert off[PG["tet"] + 1] == off[PG["tet"]] and all(c == 0 for (cls, _), (_, c) in zip(keys, per_key) if cls == PG["tet"])
+    rows_seen = [(o, o + c) for o, c in per_key if c]
+    assert all(0 <= a and b <= total for a, b in rows_seen) and len(set(rows_seen)) == len(rows_seen)          # inside the buffer, no two keys on one row
+
+
+def test_layout_33_keys_make_two_chunks_with_each_key_where_it_is_alone(shim):
+    sup = list(_supported(N_CLOTH, N_EL).values())
+    rng = np.random.default_rng(3)
+    for pool, need in ((sup, [True] * 6), ([v for v in sup if v[0] == PG["face"]], [q == PG["face"] for q in range(6)])):
+        keys = [pool[i] for i in rng.integers(0, len(pool), 33)]
+        _, total, per_key, chunks = _layout(shim, NB, need, keys)
+        assert chunks == [32, 1]
+        for k, got in zip(keys, per_key):
+            _, total1, alone, chunks1 = _layout(shim, NB, need, [k])
+            assert chunks1 == [1] and alone == [got] and total1 == total
+    assert _layout(shim, NB, [True] * 6, sup[:1] * 32)[3] == [32] and _layout(shim, NB, [True] * 6, sup[:1] * 64)[3] == [32, 32]
+
+
+def test_layout_fails_above_int32(shim):
+    need = [True] + [False] * 5
+    assert _layout(shim, [2 ** 29 - 1] + NB[1:], need, [(0, 0)])[1] == 4 * (2 ** 29 - 1)          # 2^31 - 4: the largest total these counts reach
+    assert _layout(shim, [2 ** 29] + NB[1:], need, [(0, 0)]) == "tsl_param_grad_keys: too many partials"

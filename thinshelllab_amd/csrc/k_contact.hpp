@@ -1307,7 +1307,7 @@ static ContactArgs ee_args(ContactArgs A, int nvf) {
 
 extern "C" int tsl_contact_counts(tsl_ctx* c, int32_t* out2) {
   if (!c || !out2) return tsl_fail("tsl_contact_counts: null argument");
-  out2[0] = c->nc - c->nc_ee; out2[1] = c->nc_ee;
+  out2[0] = contact_nvf(c); out2[1] = c->nc_ee;
   return 0;
 }
 
@@ -1323,7 +1323,7 @@ static int contact_assemble(tsl_ctx* c, const double* pos, int spd, double* grad
   A.k_contact = c->k_contact; A.eps_contact = c->eps_contact; A.eps_vh = c->eps_v * c->dt;
   if (grad && c->c_G.n < 12 * (size_t)c->max_n_constraints) { if (c->c_G.alloc(12 * (size_t)c->max_n_constraints)) return -1; }
   double* cg = grad ? c->c_G.p : (double*)nullptr;   // per-constraint gradients, summed per vertex by k_contact_row_gather
-  const int nvf = c->nc - c->nc_ee;   // vertex-triangle slots [0, nvf), edge-edge slots [nvf, nc)
+  const int nvf = contact_nvf(c);
   if (nvf > 0) {
     if (c->spd_literal && spd == 1) hipLaunchKernelGGL(k_contact_assemble_coop<true>, dim3(cnblk((long)nvf * 16, 256)), dim3(256), 0, s, nvf, A, pos, spd, c->c_Hfull.p, cg);
     else hipLaunchKernelGGL(k_contact_assemble_coop<false>, dim3(cnblk((long)nvf * 16, 256)), dim3(256), 0, s, nvf, A, pos, spd, c->c_Hfull.p, cg);

@@ -11,6 +11,7 @@
 #include "k_contact.hpp"
 #include "k_fem.hpp"
 #include "k_handle.hpp"
+#include "param_keys.hpp"
 #include "tsl_device.hpp"
 
 #define PG_THREADS 256
@@ -215,9 +216,8 @@ __global__ void __launch_bounds__(PG_THREADS) k_pg_contact(int nc, ContactArgs A
 
 // One workgroup: out[j] = sum of the partials [off[j], off[j] + cnt[j]) of key j, lanes strided, joined by block_sum (a fixed tree per key).  The
 // table travels as a kernel argument (no upload); a call with more than PG_KEYS_PER_LAUNCH keys launches this kernel once per chunk of keys, out
-// pointing at the chunk.  With n_ee > 0 it also counts the edge-edge slots kinds[0 .. n_ee) of kind 1 and 2 into cnt_out[0], cnt_out[1].
-#define PG_KEYS_PER_LAUNCH 32
-struct PgTable { int n; int off[PG_KEYS_PER_LAUNCH], cnt[PG_KEYS_PER_LAUNCH]; };
+// pointing at the chunk (PgTable: param_keys.hpp).  With n_ee > 0 it also counts the edge-edge slots kinds[0 .. n_ee) of kind 1 and 2 into
+// cnt_out[0], cnt_out[1].
 __global__ void __launch_bounds__(PG_THREADS) k_pg_final(PgTable tab, const double* __restrict__ part, int n_ee, const int* __restrict__ kinds,
                                                          double* __restrict__ out, double* __restrict__ cnt_out) {
   __shared__ double sm[PG_THREADS / 64];

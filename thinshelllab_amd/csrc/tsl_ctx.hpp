@@ -441,6 +441,9 @@ struct tsl_ctx {
   }
 };
 
+// The constraint slots of the last detection: the vertex-triangle ones [0, contact_nvf), then the edge-edge ones ("contact_ee") up to nc
+static inline int contact_nvf(const tsl_ctx* c) { return c->nc - c->nc_ee; }
+
 // Every entry point runs on the context's own stream; Enter/leave order it after / before the caller's stream.
 struct Scope {
   tsl_ctx* c;

@@ -1,7 +1,10 @@
 // libtsl_hip.so -- C ABI (include/tsl_hip.h) over the gfx950 kernels.  Host orchestration of
 //   BaseScene.compute_energy / compute_residual_and_Hessian / newton_step / time_step
 //   (/root/reference/code/engine/BaseScene.py:427-451, :976-1040, :1159-1230, :1327-1370),
-//   SparseMatrix.solve (sparse_solver.py:85-105) and Grad.transfer_grad (analytic_grad_single.py:217-257).
+//   and SparseMatrix.solve (sparse_solver.py:85-105).  No kernel is defined here: device code lives in the k_*.hpp headers (k_scene.hpp: energy and
+//   gradient gathers, k_adjoint.hpp: the reverse step), and the entry points of a subject in its own header, included below where what they call is
+//   defined: handle_api.hpp (soft handles), param_api.hpp (read-outs of system identification; its key table and partial layout are host logic in
+//   param_keys.hpp), adjoint_api.hpp (Grad.transfer_grad, analytic_grad_single.py:217-257), direct_host.hpp / direct_group.hpp (sparse direct solve).
 // There is no CPU fallback in this library: without a HIP device every entry point fails.
 #include <stdarg.h>
 #include <cctype>
@@ -49,6 +52,7 @@ int tsl_fail(const char* fmt, ...) {
 static inline int nblk(long n, int b) { return (int)((n + b - 1) / b); }
 static inline int gsz(size_t n) { size_t b = (n + 255) / 256; return (int)std::min<size_t>(std::max<size_t>(b, 1), 4096); }
 #include "handle_api.hpp"
+#include "k_scene.hpp"
 
 // ------------------------------------------------------------------------------------------------
 static int mg_build(tsl_ctx* c, const tsl_scene_desc* d);
@@ -337,47 +341,6 @@ extern "C" int tsl_set_gravity(tsl_ctx* c, const double* g) {
 }
 
 // ------------------------------------------------------------------------------------------------
-template <bool STVK>   // STVK: some cloth has membrane = 1 (cface_energy_sel)
-TSL_DEV void energy_body(VertArgs VA, ClothArgs CA, TetArgs TA, const double* __restrict__ pos, const double* __restrict__ prev,
-                         const double* __restrict__ vel, const double* __restrict__ ref_angle, double* __restrict__ e_part, StvkArgs S) {
-  const int t = blockIdx.x * blockDim.x + threadIdx.x;
-  double e = 0;
-  if (t < VA.NV) e += vert_energy(VA, t, pos, prev, vel);
-  if (t < CA.n_cface) {
-    int v[3]; d3 P[3];
-    load_face(pos, CA.f2v, t, v, P);
-    const double li[3] = {CA.li[3 * t], CA.li[3 * t + 1], CA.li[3 * t + 2]};
-    if constexpr (STVK) e += cface_energy_sel(CA.cloth[CA.cid[t]], S.stvk + 4 * CA.cid[t], S.dminv + 4 * t, P, CA.V[t], li);
-    else e += cface_energy(CA.cloth[CA.cid[t]], P, CA.V[t], li);
-  }
-  if (t < CA.n_hinge) e += hinge_energy(CA, t, pos, ref_angle);
-  if (t < TA.n_tet) e += tet_energy(TA, t, pos);
-  e = wave_sum(e);
-  // the four waves of the workgroup in order, one partial per workgroup; k_energy_final adds the partials in order
-  __shared__ double sw[4];
-  if ((threadIdx.x & 63) == 0) sw[threadIdx.x >> 6] = e;
-  __syncthreads();
-  if (threadIdx.x == 0) e_part[blockIdx.x] = ((sw[0] + sw[1]) + sw[2]) + sw[3];
-}
-__global__ void k_energy(VertArgs VA, ClothArgs CA, TetArgs TA, const double* __restrict__ pos, const double* __restrict__ prev,
-                         const double* __restrict__ vel, const double* __restrict__ ref_angle, double* __restrict__ e_part) {
-  energy_body<false>(VA, CA, TA, pos, prev, vel, ref_angle, e_part, StvkArgs{nullptr, nullptr});
-}
-__global__ void k_energy_stvk(VertArgs VA, ClothArgs CA, TetArgs TA, const double* __restrict__ pos, const double* __restrict__ prev,
-                              const double* __restrict__ vel, const double* __restrict__ ref_angle, double* __restrict__ e_part, StvkArgs S) {
-  energy_body<true>(VA, CA, TA, pos, prev, vel, ref_angle, e_part, S);
-}
-// sum of n partial energies in a fixed order (one workgroup: strided per-thread sums, then a fixed tree)
-__global__ void __launch_bounds__(256) k_energy_final(int n, const double* __restrict__ part, double* __restrict__ e_out) {
-  __shared__ double sh[256];
-  double a = 0.0;
-  for (int i = threadIdx.x; i < n; i += 256) a += part[i];
-  sh[threadIdx.x] = a;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) { if ((int)threadIdx.x < o) sh[threadIdx.x] += sh[threadIdx.x + o]; __syncthreads(); }
-  if (threadIdx.x == 0) *e_out = sh[0];
-}
-
 static CgScal* SC(tsl_ctx* c) { return (CgScal*)c->scal.p; }
 static CgScal* HSC(tsl_ctx* c) { return (CgScal*)c->h_scal; }
 
@@ -386,7 +349,7 @@ static int energy_async(tsl_ctx* c, const double* pos, const double* prev, const
   if (c->n_cface) hipLaunchKernelGGL(k_cloth_normals, dim3(nblk(c->n_cface, 256)), dim3(256), 0, s, c->n_cface, pos, c->cf_f2v.p, c->norm_dir.p);
   const int nmax = std::max(std::max(c->NV, c->n_cface), std::max(c->n_hinge, c->n_tet));
   // partials per workgroup, added in a fixed order (the line search decides on E < E0)
-  const int nvf = c->nc - c->nc_ee;   // vertex-triangle slots, then the edge-edge slots ("contact_ee")
+  const int nvf = contact_nvf(c);
   const int nb1 = nblk(nmax, 256), nb2 = nvf > 0 ? nblk(nvf, 64) : 0, nb3 = c->nc_ee > 0 ? nblk(c->nc_ee, 64) : 0;
   const int nb4 = handles_on(c) ? nblk(c->n_handle, 256) : 0;   // soft handles: their partials behind the contact ones
   const size_t n_part = (size_t)nb1 + (size_t)nblk(c->max_n_constraints, 64) + 1 + (size_t)nblk(c->n_handle, 256);
@@ -410,34 +373,6 @@ static int energy_sync(tsl_ctx* c, const double* pos, const double* prev, const 
 extern "C" int tsl_energy(tsl_ctx* c, const double* pos, const double* prev, const double* vel, const double* ref, double* E) {
   Scope scope(c);
   return energy_sync(c, pos, prev, vel, ref, E);
-}
-
-// Deterministic gradient: F[v] (holding the vertex term) += the staged gradients of the faces, hinges and tets at v (static lists, ascending
-// slot) + the rows of the contact constraints at v (the step's row lists, ascending constraint and slot), in this order
-__global__ void k_vertex_gather(int NV, const int* __restrict__ vg_ptr, const int* __restrict__ vg_idx, const double* __restrict__ stage, int lo, int hi, double* __restrict__ F) {
-  const int v = blockIdx.x * blockDim.x + threadIdx.x;
-  if (v >= NV) return;
-  d3 a = ld3(F, v);
-  for (int e = vg_ptr[v]; e < vg_ptr[v + 1]; e++) { const int i = vg_idx[e]; if (i >= lo && i < hi) a = a + ld3(stage, i); }   // staging slots in [lo, hi) only
-  st3(F, v, a);
-}
-// ... and the contact part: one WAVE per vertex, lanes over the entries of its row (l, l + 64, ...: a table vertex under a folded cloth has
-// hundreds), joined by the fixed tree of wave_sum; cg: per-constraint 12-vectors
-__global__ void __launch_bounds__(256) k_contact_row_gather(int NV, const int* __restrict__ rowpos, const int* __restrict__ cr_ptr, const int* __restrict__ cr_ent,
-                                                            const double* __restrict__ cg, double* __restrict__ F) {
-  const int v = (int)((blockIdx.x * (size_t)blockDim.x + threadIdx.x) >> 6), lane = threadIdx.x & 63;
-  if (v >= NV) return;
-  const int p = rowpos[v];
-  const int r0 = cr_ptr[p], r1 = cr_ptr[p + 1];
-  if (r1 <= r0) return;
-  double a0 = 0, a1 = 0, a2 = 0;
-  for (int e = r0 + lane; e < r1; e += 64) {
-    const int q = cr_ent[e];
-    const double* g = cg + 12 * (size_t)(q >> 2) + 3 * (q & 3);
-    a0 += g[0]; a1 += g[1]; a2 += g[2];
-  }
-  a0 = wave_sum(a0); a1 = wave_sum(a1); a2 = wave_sum(a2);
-  if (lane == 0) st3(F, v, ld3(F, v) + d3(a0, a1, a2));
 }
 
 // The face kernels of an assembly: the <STVK> instantiations only while some cloth has membrane = 1, else the spring ones as they were
@@ -1906,207 +1841,7 @@ extern "C" int tsl_solve(tsl_ctx* c, const double* rhs, double* x, tsl_solve_sta
   return 0;
 }
 
-// ------------------------------------------------------------------------------------------------
-// Internal force field of the FEM bodies (Elastic.get_force): consumed by BaseScene.check_early_stop / gather_force
-// (BaseScene.py:1541-1584).  force_dev: tot_NV x 3 (only the rows of elastic bodies are written, the rest is zeroed).
-extern "C" int tsl_elastic_force(tsl_ctx* c, const double* pos, double* force) {
-  Scope scope(c);
-  hipStream_t s = c->stream;
-  const size_t n3 = 3 * (size_t)c->NV;
-  HIP_OK(hipMemsetAsync(force, 0, n3 * sizeof(double), s));
-  if (c->n_tet) {
-    TetArgs TA = tet_args(c);
-    // element gradients staged and summed per vertex in a fixed order (as in the assembly)
-    TSL_TRY(ensure_vg_stage(c));
-    TA.gstage = c->vg_stage.p + 3 * (size_t)c->vg_tet0;
-    hipLaunchKernelGGL(k_tet_grad, dim3(nblk(c->n_tet, 256)), dim3(256), 0, s, TA, pos);
-    vertex_gather_launch(c, s, c->vg_stage.p, c->vg_tet0, c->vg_ns, force);
-    for (const ElasticDev& e : c->h_el)
-      hipLaunchKernelGGL(k_elastic_force_finish, dim3(nblk(e.n_verts, 256)), dim3(256), 0, s, vert_args(c), e.v_offset, e.v_offset + e.n_verts, force);
-  }
-  HIP_OK(hipStreamSynchronize(s));
-  HIP_OK(hipGetLastError());
-  return 0;
-}
-
-// ------------------------------------------------------------------------------------------------
-// Friction-coefficient gradient of the system-identification adjoint (Scene_sliding.contact_energy_backprop_friction,
-// Scene_sliding.py:139-176; called from analytic_grad_system.transfer_grad :150-151 instead of get_parameters_grad):
-// contribution of the last tsl_adjoint_step to d(loss)/d(mu_cloth_cloth).  pos = tape state x_s.
-extern "C" int tsl_friction_grad(tsl_ctx* c, const double* pos, double* out_host) {
-  Scope scope(c);
-  hipStream_t s = c->stream;
-  if (c->nc_ee > 0) {   // edge-edge slots of the mu_cloth_cloth pairs: no gradient (restating the vertex-triangle term with the edge-edge weights disagreed with
-                        // differences in mu by orders of magnitude), so the call fails instead of returning a wrong number
-    std::vector<int> kind(c->nc_ee);
-    HIP_OK(hipMemcpyAsync(kind.data(), c->c_kind.p + (c->nc - c->nc_ee), kind.size() * sizeof(int), hipMemcpyDeviceToHost, s));
-    HIP_OK(hipStreamSynchronize(s));
-    for (int k : kind)
-      if (k == 2) return tsl_fail("tsl_friction_grad: %d edge-edge constraints (contact_ee = 1) use mu_cloth_cloth; their friction-coefficient gradient is not implemented", c->nc_ee);
-  }
-  double* acc = &SC(c)->aux[0];
-  HIP_OK(hipMemsetAsync(acc, 0, sizeof(double), s));
-  const int nvf = c->nc - c->nc_ee;   // vertex-triangle slots, then the edge-edge slots ("contact_ee")
-  if (nvf > 0)
-    hipLaunchKernelGGL(k_contact_friction_grad, dim3(nblk(nvf, 64)), dim3(64), 0, s, nvf, contact_args(c), c->c_kind.p, c->frozen.p, pos, c->pdir.p, c->mu_cloth_cloth, acc,
-                       nblk(nvf, 64) <= 64 * 512 ? c->dot_part.p : (double*)nullptr, c->dot_ticket.p);
-
-  HIP_OK(hipMemcpyAsync(out_host, acc, sizeof(double), hipMemcpyDeviceToHost, s));
-  HIP_OK(hipStreamSynchronize(s));
-  return 0;
-}
-
-// ------------------------------------------------------------------------------------------------
-// Parameter gradients of the system-identification adjoint (analytic_grad_system.py:69-80 with BaseScene.get_paramters_grad
-// :1513-1525, Cloth.compute_deri model_fold_offset.py:1082-1127, Elastic.compute_deri): sum over the free dofs of
-// p . d(force)/d(parameter), p = the solution of the last tsl_adjoint_step.  out = {kb, mu, lam}; lam is always 0
-// because the reference never pushes d_lam up to the scene.
-extern "C" int tsl_param_grad(tsl_ctx* c, const double* pos, const double* ref, double* out_host) {
-  Scope scope(c);
-  hipStream_t s = c->stream;
-  const int NV = c->NV;
-  const size_t n3 = 3 * (size_t)NV;
-  double* tmp = c->v_t4.p;
-  double* acc = &SC(c)->aux[0];
-  HIP_OK(hipMemsetAsync(acc, 0, 2 * sizeof(double), s));
-  // hinge / tet contributions staged per element and summed per vertex in a fixed order, the dot products joined from per-block partials -- two runs of a
-  // system-identification sweep give the same bits
-  TSL_TRY(ensure_vg_stage(c));
-  // d_kb = -(bending gradient) / Kb per cloth
-  if (c->n_hinge) {
-    HIP_OK(hipMemsetAsync(tmp, 0, n3 * sizeof(double), s));
-    hipLaunchKernelGGL(k_cloth_normals, dim3(nblk(c->n_cface, 256)), dim3(256), 0, s, c->n_cface, pos, c->cf_f2v.p, c->norm_dir.p);
-    ClothArgs CA = cloth_args(c);
-    CA.gstage = c->vg_stage.p;
-    hipLaunchKernelGGL(k_cloth_grad_hinge, dim3(nblk(c->n_hinge, 256)), dim3(256), 0, s, CA, pos, ref);
-    vertex_gather_launch(c, s, c->vg_stage.p, c->vg_hinge0, c->vg_tet0, tmp);
-    for (const ClothDev& cd : c->h_cloth)
-      hipLaunchKernelGGL(k_dot_free, dim3(DOT_BLOCKS), dim3(256), 0, s, 3 * (size_t)cd.v_offset, 3 * (size_t)(cd.v_offset + cd.NV), c->pdir.p, tmp, c->frozen.p, -1.0 / cd.Kb, acc, DOT_SCRATCH(c));
-  }
-  // d_mu
-  if (c->n_tet) {
-    if (c->dmu_accum.n == 0) { TSL_TRY(c->dmu_accum.alloc(n3)); HIP_OK(hipMemsetAsync(c->dmu_accum.p, 0, n3 * sizeof(double), s)); }
-    HIP_OK(hipMemsetAsync(tmp, 0, n3 * sizeof(double), s));
-    if (c->vg_stage2.n < 12 * (size_t)c->n_tet) { if (c->vg_stage2.alloc(12 * (size_t)c->n_tet)) return tsl_fail("out of device memory (gradient staging)"); }
-    double *stA = c->vg_stage.p + 3 * (size_t)c->vg_tet0, *stB = c->vg_stage2.p;
-    hipLaunchKernelGGL(k_tet_deri_mu, dim3(nblk(c->n_tet, 64)), dim3(64), 0, s, tet_args(c), pos, stA, stB);
-    {   // (the second gather reads the same slot numbers from a staging array that holds the tet slots only)
-      vertex_gather_launch(c, s, c->vg_stage.p, c->vg_tet0, c->vg_ns, tmp);
-      vertex_gather_launch(c, s, c->vg_stage2.p - 3 * (size_t)c->vg_tet0, c->vg_tet0, c->vg_ns, c->dmu_accum.p);
-    }
-    hipLaunchKernelGGL(k_dot_free, dim3(DOT_BLOCKS), dim3(256), 0, s, (size_t)0, n3, c->pdir.p, tmp, c->frozen.p, 1.0, acc + 1, DOT_SCRATCH(c));
-    hipLaunchKernelGGL(k_dot_free, dim3(DOT_BLOCKS), dim3(256), 0, s, (size_t)0, n3, c->pdir.p, c->dmu_accum.p, c->frozen.p, 1.0, acc + 1, DOT_SCRATCH(c));
-  }
-  double h[2];
-  HIP_OK(hipMemcpyAsync(h, acc, 2 * sizeof(double), hipMemcpyDeviceToHost, s));
-  HIP_OK(hipStreamSynchronize(s));
-  out_host[0] = h[0]; out_host[1] = h[1]; out_host[2] = 0.0;
-  return 0;
-}
-
-// ------------------------------------------------------------------------------------------------
-// Parameter gradients by key (system identification beyond the reference's {kb, mu, lam}): out[j] = -sum over the free dofs of p . dF/d(theta_j),
-// F = the gradient of tsl_assemble at (pos, ref_angle) with the contact constraints as they stand -- the sign of tsl_param_grad, whose kb is the sum
-// of the cloth<i>.Kb values.  One pass per element class that some requested key needs (k_param.hpp), each writing one partial per workgroup and key
-// row; k_pg_final sums the requested keys' partials; one read-back.
-extern "C" int tsl_param_grad_keys(tsl_ctx* c, const double* pos, const double* ref, const double* p_dev, const char* const* keys, int32_t n_keys,
-                                   double* out_host) {
-  Scope scope(c);
-  if (n_keys <= 0) return 0;
-  if (!keys || !out_host || !pos) return tsl_fail("tsl_param_grad_keys: null argument");
-  hipStream_t s = c->stream;
-  const int n_cloth = (int)c->h_cloth.size(), n_el = (int)c->h_el.size();
-  const int nvf = c->nc - c->nc_ee;   // vertex-triangle slots, then the edge-edge slots ("contact_ee")
-  const char* supported = "cloth<i>.Kl|Ka|Kb|stvk_mu|stvk_lam, elastic<i>.mu|lam, k_contact, mu_cloth_elastic, mu_cloth_cloth, k_handle";
-  // ---- keys -> (class, row): class 0 faces (rows 2 i + {Kl, Ka}), 1 hinges (row i), 2 tets (rows 2 i + {mu, lam}), 3 contact slots (rows k_contact,
-  //      mu_cloth_elastic, mu_cloth_cloth), 4 faces of the StVK membrane (rows 2 i + {stvk_mu, stvk_lam}), 5 soft handles (row k_handle)
-  std::vector<std::array<int, 2>> kr(n_keys);
-  bool need[6] = {false, false, false, false, false, false};
-  for (int j = 0; j < n_keys; j++) {
-    if (!keys[j]) return tsl_fail("tsl_param_grad_keys: key %d is null", j);
-    const std::string k(keys[j]);
-    int cls = -1, row = -1;
-    if (k == "k_contact") { cls = 3; row = 0; }
-    else if (k == "mu_cloth_elastic") { cls = 3; row = 1; }
-    else if (k == "mu_cloth_cloth") { cls = 3; row = 2; }
-    else if (k == "k_handle") { cls = 5; row = 0; }
-    else {   // "cloth<i>.<field>", "elastic<i>.<field>": field -> (class, row among the rows of cloth / body i)
-      static const std::pair<const char*, std::array<int, 2>> cloth_rows[] = {{"Kl", {0, 0}}, {"Ka", {0, 1}}, {"Kb", {1, 0}}, {"stvk_mu", {4, 0}}, {"stvk_lam", {4, 1}}};
-      static const std::pair<const char*, std::array<int, 2>> elastic_rows[] = {{"mu", {2, 0}}, {"lam", {2, 1}}};
-      IndexedKey ik;
-      if (parse_indexed_key(keys[j], ik) && ik.family != IndexedKey::SelfContact) return tsl_fail("tsl_param_grad_keys: bad index in %s", keys[j]);
-      const bool is_cloth = ik.family == IndexedKey::Cloth;
-      const std::array<int, 2>* cr = is_cloth ? field_find(cloth_rows, ik.field) : (ik.family == IndexedKey::Elastic ? field_find(elastic_rows, ik.field) : nullptr);
-      if (cr && is_cloth && (ik.index < 0 || ik.index >= n_cloth)) return tsl_fail("tsl_param_grad_keys: bad cloth index in %s (%d cloths)", keys[j], n_cloth);
-      if (cr && !is_cloth && (ik.index < 0 || ik.index >= n_el)) return tsl_fail("tsl_param_grad_keys: bad elastic index in %s (%d bodies)", keys[j], n_el);
-      if (cr) { cls = (*cr)[0]; row = cls == 1 ? (int)ik.index : (*cr)[1] + 2 * (int)ik.index; }
-    }
-    if (cls < 0) return tsl_fail("tsl_param_grad_keys: %s is not a differentiated key (supported: %s)", keys[j], supported);
-    if (cls == 3) {
-      if (row == 0 && c->nc_ee > 0)
-        return tsl_fail("tsl_param_grad_keys: k_contact: %d edge-edge constraints (contact_ee = 1) are present; their friction derivative is not implemented", c->nc_ee);
-      const double live = row == 0 ? c->k_contact : (row == 1 ? c->mu_cloth_elastic : c->mu_cloth_cloth);
-      bool used = row == 0;
-      for (const auto& pr : c->h_pairs) used |= pr.mu_is_param == row;
-      if (live == 0.0 && used && nvf > 0)
-        return tsl_fail("tsl_param_grad_keys: %s = 0: the friction weights c_k of the detection vanish with it, their derivative is not available", keys[j]);
-    }
-    if (cls == 1 && !ref) return tsl_fail("tsl_param_grad_keys: %s needs ref_angle", keys[j]);
-    kr[j] = {cls, row};
-    need[cls] = true;
-  }
-  // ---- partial layout: class q holds rows[q] rows of nb[q] partials (class 4 behind the others: their layout does not depend on it).  With no cloth
-  //      of membrane = 1 the StVK keys have no partials and read exact zeros, as k_handle does with no handles
-  const int rows[6] = {2 * n_cloth, n_cloth, 2 * n_el, 3, 2 * n_cloth, 1};
-  const int nb[6] = {c->n_cface > 0 ? nblk(c->n_cface, PG_THREADS) : 0, c->n_hinge > 0 ? nblk(c->n_hinge, PG_THREADS) : 0, c->n_tet > 0 ? nblk(c->n_tet, PG_THREADS) : 0,
-                     nvf > 0 ? nblk(nvf, PG_THREADS) : 0, c->n_cface > 0 && c->n_stvk > 0 ? nblk(c->n_cface, PG_THREADS) : 0,
-                     c->n_handle > 0 ? nblk(c->n_handle, PG_THREADS) : 0};
-  size_t off[6], tot = 0;
-  for (int q = 0; q < 6; q++) { off[q] = tot; if (need[q]) tot += (size_t)rows[q] * nb[q]; }
-  if (tot > (size_t)INT32_MAX) return tsl_fail("tsl_param_grad_keys: too many partials");
-  if (c->pg_part.n < std::max<size_t>(tot, 1)) TSL_TRY(c->pg_part.alloc(std::max<size_t>(tot, 1)));
-  if (c->pg_out.n < (size_t)n_keys + 2) TSL_TRY(c->pg_out.alloc((size_t)n_keys + 2));
-  const double* p = p_dev ? p_dev : c->pdir.p;
-  const int* fz = c->frozen.p;
-  double* part = c->pg_part.p;
-  if (need[0] && nb[0]) {
-    if (c->n_stvk > 0) hipLaunchKernelGGL(k_pg_face<true>, dim3(nb[0]), dim3(PG_THREADS), 0, s, cloth_args(c), n_cloth, pos, p, fz, part + off[0], stvk_args(c));
-    else hipLaunchKernelGGL(k_pg_face<false>, dim3(nb[0]), dim3(PG_THREADS), 0, s, cloth_args(c), n_cloth, pos, p, fz, part + off[0], stvk_args(c));
-  }
-  if (need[5] && nb[5]) handle_dispatch(c, [&](auto NC) { hipLaunchKernelGGL(k_pg_handle<NC>, dim3(nb[5]), dim3(PG_THREADS), 0, s, handle_args(c), pos, p, fz, part + off[5]); });
-  if (need[4] && nb[4]) hipLaunchKernelGGL(k_pg_stvk, dim3(nb[4]), dim3(PG_THREADS), 0, s, cloth_args(c), n_cloth, pos, p, fz, part + off[4], stvk_args(c));
-  if (need[1] && nb[1]) hipLaunchKernelGGL(k_pg_hinge, dim3(nb[1]), dim3(PG_THREADS), 0, s, cloth_args(c), n_cloth, pos, ref, p, fz, part + off[1]);
-  if (need[2] && nb[2]) hipLaunchKernelGGL(k_pg_tet, dim3(nb[2]), dim3(PG_THREADS), 0, s, tet_args(c), n_el, pos, p, fz, part + off[2]);
-  if (need[3] && nb[3])
-    hipLaunchKernelGGL(k_pg_contact, dim3(nb[3]), dim3(PG_THREADS), 0, s, nvf, contact_args(c), (const int*)c->c_kind.p, c->mu_cloth_elastic, c->mu_cloth_cloth, pos, p, fz,
-                       part + off[3]);
-  // the (offset, count) table as kernel arguments, PG_KEYS_PER_LAUNCH keys per launch; the first launch also counts the kinds of the edge-edge
-  // slots -- only when a friction key asks (k_contact with such slots failed above)
-  const int n_ee = need[3] ? c->nc_ee : 0;
-  for (int j0 = 0; j0 < n_keys; j0 += PG_KEYS_PER_LAUNCH) {
-    PgTable tab;
-    tab.n = std::min(PG_KEYS_PER_LAUNCH, n_keys - j0);
-    for (int j = 0; j < tab.n; j++) {
-      const int q = kr[j0 + j][0];
-      tab.off[j] = (int)(off[q] + (size_t)kr[j0 + j][1] * nb[q]);
-      tab.cnt[j] = nb[q];
-    }
-    hipLaunchKernelGGL(k_pg_final, dim3(1), dim3(PG_THREADS), 0, s, tab, (const double*)part, j0 == 0 ? n_ee : 0,
-                       n_ee > 0 ? (const int*)c->c_kind.p + nvf : (const int*)nullptr, c->pg_out.p + j0, j0 == 0 ? c->pg_out.p + n_keys : (double*)nullptr);
-  }
-  HIP_OK(hipGetLastError());
-  std::vector<double> h((size_t)n_keys + 2);
-  HIP_OK(hipMemcpyAsync(h.data(), c->pg_out.p, h.size() * sizeof(double), hipMemcpyDeviceToHost, s));
-  HIP_OK(hipStreamSynchronize(s));
-  for (int j = 0; j < n_keys; j++) {
-    if (kr[j][0] != 3 || kr[j][1] == 0) continue;
-    const double n_kind = h[n_keys + kr[j][1] - 1];
-    if (n_kind > 0)
-      return tsl_fail("tsl_param_grad_keys: %s: %d edge-edge constraints (contact_ee = 1) use it; their friction derivative is not implemented", keys[j], (int)n_kind);
-  }
-  for (int j = 0; j < n_keys; j++) out_host[j] = h[j];
-  return 0;
-}
+#include "param_api.hpp"
 
 // ------------------------------------------------------------------------------------------------
 extern "C" int tsl_update_ref_angle(tsl_ctx* c, const double* pos, double* ref) {
@@ -2670,284 +2405,4 @@ extern "C" int tsl_spd_project(tsl_ctx* c, double* blocks, int32_t n, int32_t D)
   return 0;
 }
 
-// ------------------------------------------------------------------------------------------------ adjoint
-// Grad.clamp_grad (analytic_grad_single.py:176-185)
-__global__ void k_clamp(size_t n, double* __restrict__ v, double lim) {
-  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) v[i] = fmin(fmax(v[i], -lim), lim);
-}
-
-// Cloth.ref_angle_backprop_a2ax (model_fold_offset.py:1179-1206), one lane per hinge.
-// ag_s / ag_prev: angleref_grad[s], angleref_grad[s-1]; pg_s: pos_grad[s]; ref = ref_angle_{s-1}; pos = x_s
-__global__ void __launch_bounds__(256) k_adj_a2ax(ClothArgs A, const double* __restrict__ pos, const double* __restrict__ ref, const double* __restrict__ ag_s, double* __restrict__ ag_prev) {
-  const int h = blockIdx.x * blockDim.x + threadIdx.x;
-  if (h >= A.n_hinge) return;
-  const int f1 = A.hg_info[8 * h], l = A.hg_info[8 * h + 1], f2 = A.hg_info[8 * h + 2], p4 = A.hg_info[8 * h + 3], p21 = A.hg_info[8 * h + 4];
-  const ClothDev c = A.cloth[A.cid[f1]];
-  int v1[3], v2[3]; d3 P1[3], P2[3];
-  load_face(pos, A.f2v, f1, v1, P1);
-  load_face(pos, A.f2v, f2, v2, P2);
-  const FaceGeom g1 = face_geom(P1), g2 = face_geom(P2);
-  d3 g[4];
-  hinge_grad(g1, g2, l, p4, p21, g);
-  const double theta = dihedral(g1.n, g2.n, pick3(P1, (l + 1) % 2) - pick3(P1, l));
-  const double a = ag_s[3 * f1 + l];
-  ag_prev[3 * f1 + l] += a;
-  const double sgn = (fabs(theta - ref[3 * f1 + l]) > c.k_angle) ? a : a * 0.1;
-#pragma unroll
-  for (int j = 0; j < 4; j++) st3(A.gstage, A.gs_hinge + 4 * h + j, sgn * g[j]);   // staged, summed per vertex by k_vertex_gather
-}
-
-// Cloth.ref_angle_backprop_x2a (model_fold_offset.py:1154-1168): angleref_grad[s-1] += -z . (d_ref * grad theta)
-__global__ void __launch_bounds__(256) k_adj_x2a(ClothArgs A, const double* __restrict__ pos, const double* __restrict__ z, double* __restrict__ ag_prev) {
-  const int h = blockIdx.x * blockDim.x + threadIdx.x;
-  if (h >= A.n_hinge) return;
-  const int f1 = A.hg_info[8 * h], l = A.hg_info[8 * h + 1], f2 = A.hg_info[8 * h + 2], p4 = A.hg_info[8 * h + 3], p21 = A.hg_info[8 * h + 4];
-  const ClothDev c = A.cloth[A.cid[f1]];
-  int v1[3], v2[3]; d3 P1[3], P2[3];
-  load_face(pos, A.f2v, f1, v1, P1);
-  load_face(pos, A.f2v, f2, v2, P2);
-  const FaceGeom g1 = face_geom(P1), g2 = face_geom(P2);
-  d3 g[4];
-  hinge_grad(g1, g2, l, p4, p21, g);
-  const double d_ref = -2.0 * c.Kb * c.dx * c.dx * (1.0 / 3.0);
-  const double s = dot(ld3(z, pick3(v1, l)), g[0]) + dot(ld3(z, pick3(v1, (l + 1) % 3)), g[1]) + dot(ld3(z, pick3(v1, (l + 2) % 3)), g[2]) + dot(ld3(z, pick3(v2, p4)), g[3]);
-  ag_prev[3 * f1 + l] += -s * d_ref;
-}
-
-
-// The same sums without atomics: one thread per (permuted) row c with a frozen dof walks ITS blocks (c, p); the block that carries the
-// contribution is the transposed one, (p, c), found through a static table (trans[slot of (c, p)] = address of block (p, c); the
-// pattern is symmetric, the values are not: factor-2 quirk of the area term); fixed order, plain store of the row's three sums
-__global__ void k_zfrozen_gather(int NV, const int* __restrict__ slice_off, const int* __restrict__ slice_len, const int* __restrict__ colidx, const int* __restrict__ trans,
-                                 const unsigned char* __restrict__ fz, const double* __restrict__ vals, const double* __restrict__ zp, double* __restrict__ out) {
-  const int c = blockIdx.x * blockDim.x + threadIdx.x;
-  if (c >= NV) return;
-  const unsigned cm = fz[c];
-  double acc[3] = {0.0, 0.0, 0.0};
-  if (cm) {
-    const int slice = c >> 6, lane = c & 63, off = slice_off[slice], len = slice_len[slice];
-    for (int k = 0; k < len; k++) {
-      const int sl = off + 64 * k + lane;
-      const int p = colidx[sl];
-      const int tb = trans[sl];
-      if (tb < 0) continue;   // padding of the slice
-      const unsigned rm = fz[p];
-      if (rm == 7u) continue;
-      const d3 zi = ld3(zp, p);
-      const double zr[3] = {zi.x, zi.y, zi.z};
-      for (int cc = 0; cc < 3; cc++) {
-        if (!((cm >> cc) & 1u)) continue;
-        double s = 0;
-        for (int r = 0; r < 3; r++) if (!((rm >> r) & 1u)) s += vals[(size_t)tb + 64 * (3 * r + cc)] * zr[r];
-        acc[cc] -= s;
-      }
-    }
-  }
-  out[3 * (size_t)c] = acc[0]; out[3 * (size_t)c + 1] = acc[1]; out[3 * (size_t)c + 2] = acc[2];
-}
-// contact part of tmp_z_frozen per vertex (original order) through the row lists of the step's constraints, fixed order
-__global__ void __launch_bounds__(256) k_contact_zfrozen_gather(int NV, const int* __restrict__ rowpos, const int* __restrict__ cr_ptr, const int* __restrict__ cr_ent,
-                                                                const int* __restrict__ idx, const int* __restrict__ frozen, const double* __restrict__ Hfull,
-                                                                const double* __restrict__ z, double* __restrict__ out) {
-  const int v = (int)((blockIdx.x * (size_t)blockDim.x + threadIdx.x) >> 6), lane = threadIdx.x & 63;   // one wave per vertex, lanes over the row's entries
-  if (v >= NV) return;
-  const int fz[3] = {frozen[3 * v], frozen[3 * v + 1], frozen[3 * v + 2]};
-  if (!(fz[0] | fz[1] | fz[2])) return;
-  const int p = rowpos[v];
-  const int r0 = cr_ptr[p], r1 = cr_ptr[p + 1];
-  if (r1 <= r0) return;
-  double acc[3] = {0.0, 0.0, 0.0};
-  for (int e = r0 + lane; e < r1; e += 64) {
-    const int q = cr_ent[e], ci = q >> 2, a = q & 3;
-    const double* H = Hfull + 144 * (size_t)ci;
-    for (int cc = 0; cc < 3; cc++) {
-      if (!fz[cc]) continue;
-      double s = 0;
-      for (int k = 0; k < 4; k++) {
-        const int u = idx[4 * ci + k];
-        for (int j = 0; j < 3; j++) if (!frozen[3 * u + j]) s += H[(3 * k + j) * 12 + 3 * a + cc] * z[3 * (size_t)u + j];
-      }
-      acc[cc] -= s;
-    }
-  }
-  for (int cc = 0; cc < 3; cc++) { const double t = wave_sum(acc[cc]); if (lane == 0 && fz[cc]) out[3 * (size_t)v + cc] += t; }
-}
-
-// x_hat_grad = z m / dt^2 ; pos_grad[s-1] += (1+d) x_hat_grad, pos_grad[s-2] -= d x_hat_grad on free dofs
-// (Grad.get_grad / get_prev_grad / get_prev_prev_grad, analytic_grad_single.py:81-106)
-__global__ void k_adj_prev(int NV, const double* __restrict__ z, const double* __restrict__ mass, const int* __restrict__ frozen, double dt, double d,
-                           double* __restrict__ pg_prev, double* __restrict__ pg_prev2) {
-  const size_t n = 3 * (size_t)NV;
-  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-    if (frozen[i]) continue;
-    const double xh = z[i] * mass[i / 3] / (dt * dt);
-    if (pg_prev) pg_prev[i] += xh * (1.0 + d);
-    if (pg_prev2) pg_prev2[i] -= xh * d;
-  }
-}
-
-// Grad.transfer_grad (analytic_grad_single.py:217-257) without the gripper part (host: gripper.set / gather_grad), in two halves around the
-// linear solve p = H^-1 pos_grad[s] (tsl_adjoint_step: the scene's own solve; tsl_group_adjoint_step: the merged solve of a scene group).
-struct AdjArgs { int step, T; const double* pos_buffer; double* pos_grad; const double* ref_buffer; double* angleref_grad; double* tmp_z_frozen; double adj_damping; };
-
-// clamp, contacts at x_{s-1}, ref-angle backprop (a2ax), the un-projected Hessian at x_s in c->vals / c->c_H; *rhs = pos_grad[s]
-static int adjoint_pre(tsl_ctx* c, const AdjArgs& a, double** rhs) {
-  hipStream_t s = c->stream;
-  const int NV = c->NV;
-  const size_t n3 = 3 * (size_t)NV, nr = 3 * (size_t)std::max(c->n_cface, 1);
-  double* pg_s = a.pos_grad + (size_t)a.step * n3;
-  double* pg_prev = a.pos_grad + (size_t)(a.step - 1) * n3;
-  double* pg_prev2 = a.step > 1 ? a.pos_grad + (size_t)(a.step - 2) * n3 : nullptr;
-  const double* x_s = a.pos_buffer + (size_t)a.step * n3;
-  const double* x_prev = a.pos_buffer + (size_t)(a.step - 1) * n3;
-  double* ag_s = a.angleref_grad + (size_t)a.step * nr;
-  double* ag_prev = a.angleref_grad + (size_t)(a.step - 1) * nr;
-  const double* ref_prev = a.ref_buffer + (size_t)(a.step - 1) * nr;
-  (void)pg_prev; (void)pg_prev2; (void)ag_prev;
-  // clamp_grad
-  hipLaunchKernelGGL(k_clamp, dim3(gsz(n3)), dim3(256), 0, s, n3, pg_s, c->adj_clamp);
-  if (c->n_cface && c->adj_clamp_angleref)
-    hipLaunchKernelGGL(k_clamp, dim3(gsz(3 * (size_t)c->n_cface)), dim3(256), 0, s, 3 * (size_t)c->n_cface, ag_s, 1000.0);
-  // contacts re-detected at pos = prev_pos = x_{s-1} (copy_pos_only + calc_vn + f_contact + contact_analysis)
-  int nc = 0;
-  if (c->contact_enable) TSL_TRY(tsl_contact_detect(c, x_prev, x_prev, &nc));
-  else { c->nc = 0; c->nc_ee = 0; c->ds.cons_checked = false; }
-  ClothArgs CA = cloth_args(c);
-  TSL_TRY(ensure_vg_stage(c));
-  // pos = x_s, ref_angle = ref_{s-1}: init_folding + ref_angle_backprop_a2ax
-  if (c->n_hinge) {
-    CA.gstage = c->vg_stage.p;
-    hipLaunchKernelGGL(k_adj_a2ax, dim3(nblk(c->n_hinge, 256)), dim3(256), 0, s, CA, x_s, ref_prev, ag_s, ag_prev);
-    vertex_gather_launch(c, s, c->vg_stage.p, c->vg_hinge0, c->vg_tet0, pg_s);
-    CA.gstage = nullptr;
-  }
-  // preconditioner from the SPD-projected Hessian of the same state (block Jacobi + multigrid hierarchy): the operator
-  // below is the un-projected H, which may be indefinite, and smoothers / coarse operators built from it are not safe
-  const bool have_mg = !c->mg.empty() && c->mg_enable != 0;
-  // the direct path factorises the un-projected operator itself; its auto mode may still probe the hierarchy first (not marked hard)
-  const bool spd_pc = c->adj_spd_pc && (have_mg || body_active(c)) && !(direct_enabled(c) && (c->ds.enable == 1 || c->ds.hard || c->n_tet > 0 || c->nc > 0));   // (no probe of the hierarchy: see solve_direct)
-  c->bd_valid = false;
-  c->mg_omega_valid = false;
-  if (spd_pc) {
-    TSL_TRY(assemble(c, x_s, x_prev, x_prev, ref_prev, 1, nullptr));
-    if (body_active(c)) TSL_TRY(body_build_inverse(c));
-    if (have_mg) TSL_TRY(mg_setup_operators(c));
-    if (c->vals_pc.n == 0 && c->vals_pc.alloc(c->vals.n)) return tsl_fail("out of device memory (vals_pc)");
-    HIP_OK(hipMemcpyAsync(c->vals_pc.p, c->vals.p, c->vals.n * sizeof(double), hipMemcpyDeviceToDevice, s));
-    if (c->nc > 0) {
-      if (c->c_H_pc.n == 0 && c->c_H_pc.alloc(c->c_H.n)) return tsl_fail("out of device memory (c_H_pc)");
-      HIP_OK(hipMemcpyAsync(c->c_H_pc.p, c->c_H.p, (size_t)c->nc * 144 * sizeof(double), hipMemcpyDeviceToDevice, s));
-    }
-    c->pc_frozen = true;
-  }
-  // H.clear_all + compute_Hessian(False)
-  const int rc_asm = assemble(c, x_s, x_prev, x_prev /*vel unused without gradient*/, ref_prev, 0, nullptr);
-  c->pc_frozen = false;
-  if (rc_asm) return rc_asm;
-  if (spd_pc) c->pc_separate = true;
-  *rhs = pg_s;
-  return 0;
-}
-
-// p = c->pdir (original order), c->v_x (permuted): tmp_z_frozen, contact / ref-angle / inertia backprop into step s-1 and s-2
-static int adjoint_post(tsl_ctx* c, const AdjArgs& a) {
-  hipStream_t s = c->stream;
-  const int NV = c->NV;
-  const size_t n3 = 3 * (size_t)NV, nr = 3 * (size_t)std::max(c->n_cface, 1);
-  double* pg_s = a.pos_grad + (size_t)a.step * n3;
-  double* pg_prev = a.pos_grad + (size_t)(a.step - 1) * n3;
-  double* pg_prev2 = a.step > 1 ? a.pos_grad + (size_t)(a.step - 2) * n3 : nullptr;
-  const double* x_s = a.pos_buffer + (size_t)a.step * n3;
-  const double* x_prev = a.pos_buffer + (size_t)(a.step - 1) * n3;
-  double* ag_s = a.angleref_grad + (size_t)a.step * nr;
-  double* ag_prev = a.angleref_grad + (size_t)(a.step - 1) * nr;
-  const double* ref_prev = a.ref_buffer + (size_t)(a.step - 1) * nr;
-  (void)pg_s; (void)x_prev; (void)ag_s; (void)ref_prev;
-  double* tmp_z_frozen = a.tmp_z_frozen;
-  const double adj_damping = a.adj_damping;
-  ClothArgs CA = cloth_args(c);
-  // tmp_z_frozen (second compute_Hessian pass with counting_z_frozen)
-  hipLaunchKernelGGL(k_zfrozen_gather, dim3(nblk(NV, 256)), dim3(256), 0, s, NV, c->slice_off.p, c->slice_len.p, c->colidx.p, (const int*)c->trans.p, c->fzmask.p, c->vals_full.p,
-                     c->v_x.p, c->v_t4.p);
-  hipLaunchKernelGGL(k_scatter_perm, dim3(nblk(NV, 256)), dim3(256), 0, s, NV, c->perm.p, c->v_t4.p, tmp_z_frozen);
-  if (c->nc > 0) {
-    hipLaunchKernelGGL(k_contact_zfrozen_gather, dim3(nblk((long)NV * 64, 256)), dim3(256), 0, s, NV, (const int*)c->rowpos.p, (const int*)c->cr_ptr.p, (const int*)c->cr_ent.p, c->c_idx.p,
-                       c->frozen.p, c->c_Hfull.p, c->pdir.p, tmp_z_frozen);
-  }
-  // contact_energy_backprop(step-1) ; ref_angle_backprop_x2a
-  if (c->nc > 0) {
-    if (c->c_G.n < 12 * (size_t)c->max_n_constraints) { if (c->c_G.alloc(12 * (size_t)c->max_n_constraints)) return -1; }
-    const int nvf = c->nc - c->nc_ee;   // vertex-triangle slots, then the edge-edge slots ("contact_ee")
-    if (nvf > 0) hipLaunchKernelGGL(k_contact_backprop, dim3(nblk(nvf, 64)), dim3(64), 0, s, nvf, contact_args(c), x_s, c->pdir.p, c->c_G.p);
-    if (c->nc_ee > 0) hipLaunchKernelGGL(k_ee_backprop, dim3(nblk(c->nc_ee, 64)), dim3(64), 0, s, c->nc_ee, ee_args(contact_args(c), nvf), x_s, c->pdir.p, c->c_G.p + 12 * (size_t)nvf);
-    hipLaunchKernelGGL(k_contact_row_gather, dim3(nblk((long)NV * 64, 256)), dim3(256), 0, s, NV, (const int*)c->rowpos.p, (const int*)c->cr_ptr.p, (const int*)c->cr_ent.p,
-                       (const double*)c->c_G.p, pg_prev);
-  }
-  if (c->n_hinge) hipLaunchKernelGGL(k_adj_x2a, dim3(nblk(c->n_hinge, 256)), dim3(256), 0, s, CA, x_s, c->pdir.p, ag_prev);
-  // get_prev_grad / get_prev_prev_grad
-  hipLaunchKernelGGL(k_adj_prev, dim3(gsz(n3)), dim3(256), 0, s, NV, c->pdir.p, c->mass.p, c->frozen.p, c->dt, adj_damping, pg_prev, pg_prev2);
-  HIP_OK(hipGetLastError());
-  return 0;
-}
-
-extern "C" int tsl_adjoint_step(tsl_ctx* c, int step, int T, const double* pos_buffer, double* pos_grad, const double* ref_buffer, double* angleref_grad,
-                                double* tmp_z_frozen, double adj_damping, tsl_solve_stats* st) {
-  Scope scope(c);
-  if (step < 1 || step >= T) return tsl_fail("tsl_adjoint_step: step %d outside [1, %d)", step, T);
-  const AdjArgs a{step, T, pos_buffer, pos_grad, ref_buffer, angleref_grad, tmp_z_frozen, adj_damping};
-  double* pg_s = nullptr;
-  TSL_TRY(adjoint_pre(c, a, &pg_s));
-  // p = H^-1 pos_grad[s]
-  tsl_solve_stats local;
-  if (!st) st = &local;
-  TSL_TRY(solve_orig(c, pg_s, c->pdir.p, st));
-  if (st->method == 4) TSL_TRY(direct_prezero(c));   // the next adjoint step assembles another operator
-  if (c->verbose) fprintf(stderr, "[tsl] adjoint step %d: nc %d solver flag %d iters %d restarts %d rel_residual %.2e\n", step, c->nc, st->flag, st->iters, st->restarts, st->rel_residual);
-  TSL_TRY(adjoint_post(c, a));
-  HIP_OK(hipStreamSynchronize(c->stream));
-  HIP_OK(hipGetLastError());
-  return 0;
-}
-
-// Grad.transfer_grad of every scene of a group for the same reverse step: the S adjoint systems H_i p_i = pos_grad_i[s] go through ONE merged
-// factorisation and first application (group_solve), the halves before and after it run per member on its own stream (one host thread each).
-// Same bits per scene as tsl_adjoint_step on a context with the sparse direct solve.  stats: S records (or NULL).
-extern "C" int tsl_group_adjoint_step(tsl_group* G, int step, int T, const double* const* pos_buffer_a, double* const* pos_grad_a, const double* const* ref_buffer_a,
-                                      double* const* angleref_grad_a, double* const* tmp_z_a, const double* adj_damping_a, tsl_solve_stats* stats) {
-  const int n = (int)G->m.size();
-  tsl_ctx* g = G->g;
-  if (step < 1 || step >= T) return tsl_fail("tsl_group_adjoint_step: step %d outside [1, %d)", step, T);
-  std::vector<std::unique_ptr<Scope>> scopes;
-  for (int i = 0; i < n; i++) scopes.emplace_back(new Scope(G->m[i]));
-  std::vector<AdjArgs> aa(n);
-  std::vector<int> act(n);
-  for (int i = 0; i < n; i++) {
-    if (!direct_enabled(G->m[i])) return tsl_fail("tsl_group_adjoint_step: scene %d does not use the sparse direct solve", i);
-    aa[i] = AdjArgs{step, T, pos_buffer_a[i], pos_grad_a[i], ref_buffer_a[i], angleref_grad_a[i], tmp_z_a[i], adj_damping_a[i]};
-    act[i] = i;
-  }
-  g->verbose = G->m[0]->verbose;
-  TSL_TRY(G->pool->run(act, [&](int i) -> int {
-    tsl_ctx* c = G->m[i];
-    double* rhs = nullptr;
-    TSL_TRY(adjoint_pre(c, aa[i], &rhs));
-    hipLaunchKernelGGL(k_gather_perm, dim3(nblk(c->NV, 256)), dim3(256), 0, c->stream, c->NV, c->perm.p, (const double*)rhs, c->v_b.p);
-    return 0;
-  }));
-  std::vector<tsl_solve_stats> ss;
-  TSL_TRY(group_solve(G, act, ss, [](int) {}));
-  TSL_TRY(G->pool->run(act, [&](int i) -> int {
-    tsl_ctx* c = G->m[i];
-    hipLaunchKernelGGL(k_scatter_perm, dim3(nblk(c->NV, 256)), dim3(256), 0, c->stream, c->NV, c->perm.p, (const double*)c->v_x.p, c->pdir.p);
-    if (c->verbose) fprintf(stderr, "[tsl] group adjoint step %d, scene %d: nc %d solver flag %d iters %d restarts %d rel_residual %.2e\n", step, i, c->nc, ss[i].flag, ss[i].iters, ss[i].restarts,
-                            ss[i].rel_residual);
-    TSL_TRY(adjoint_post(c, aa[i]));
-    return 0;
-  }));
-  for (int i = 0; i < n; i++) {
-    HIP_OK(hipStreamSynchronize(G->m[i]->stream));
-    if (stats) stats[i] = ss[i];
-  }
-  HIP_OK(hipGetLastError());
-  return 0;
-}
+#include "adjoint_api.hpp"
