@@ -107,6 +107,7 @@ int tsl_set_stream(tsl_ctx* ctx, void* hip_stream);
  *  Scene (trajopt_folding.py:50,66; Scene_folding.py:30-31; geometry.py:8-19; geometry_self.py:166-230):
  *   "cloth<i>.Kb|Kl|Ka|k_angle", "elastic<i>.mu|lam|alpha", "mu_cloth_elastic", "mu_cloth_cloth", "k_contact", "eps_contact", "eps_v", "damping",
  *   "k_handle" (0 default: stiffness in N/m of the soft handles of tsl_set_handles; negative fails; with 0, or with no handles, no handle kernel is launched),
+ *   "k_tie" (0 default: stiffness in N/m of the ties of tsl_set_ties; negative fails; with 0, or with no ties, no tie slot exists and no tie kernel is launched),
  *   "cloth<i>.membrane" (0 default: edge springs Kl + area term Ka, as the reference; 1: a St. Venant-Kirchhoff membrane per face, A0 Psi(F) with
  *   F = [x1 - x0, x2 - x0] Dm^-1, Dm the rest triangle rebuilt from the face's rest lengths (fails naming a face whose lengths violate the triangle
  *   inequality), Psi = mu |E|^2 + lam/2 tr(E)^2, E = (F^T F - I) / 2, A0 the rest area; it replaces the springs and the area term of the cloth's
@@ -219,6 +220,33 @@ int tsl_handle_targets(tsl_ctx* ctx, double* out_host);
 int tsl_frame_wrench(tsl_ctx* ctx, const double* pos_dev, double* out_host);
 int tsl_frame_grad(tsl_ctx* ctx, const double* p_dev, double* out_host);
 
+/* Ties (no reference counterpart): tie i is a spring between vertex vertices[i] and the point with barycentric coordinates b_i on face faces[i] =
+ * (t0, t1, t2) of the scene's global face table -- a seam between two cloths, a cloth sewn into a tube, a cloth on a point of a body's surface, a
+ * tether.  r_i = x_v - sum_a b_a x_{t_a}, E_tie = 1/2 k_tie sum_i w_i |r_i|^2 with the scalar "k_tie" of tsl_set_param (0 by default; negative
+ * fails).  In the order (t0, t1, t2, v) with c = (-b0, -b1, -b2, 1): gradient on corner a: k_tie w_i c_a r_i; block: k_tie w_i (c c^T) (x) I_3,
+ * constant and positive semi-definite as it stands, so every spd mode and "spd_literal" add the same numbers.  b = (1, 0, 0) is a vertex-to-vertex
+ * stitch.  A tie couples vertices that share no element: while ties exist and k_tie != 0 they are constraint slots behind the vertex-triangle and
+ * edge-edge ones of the last detection (tsl_constraints_export, tsl_contact_blocks_export list them last; read with room for max_n_constraints + n
+ * slots), at every step, with contacts on or off, and the plans of the factorisation hold their cliques.  The energy depends on the current
+ * positions only: a reverse step carries nothing from a tie into the earlier steps.  Frozen dofs follow the mask rule.  With no ties or k_tie = 0
+ * every launch is the one of a context that never had any.  No atomics, fixed orders of addition: the same bits run to run.
+ *   tsl_set_ties: n ties (host pointers, copied; the stream is synchronised); weights_host == NULL: every weight is 1; n = 0 removes them.  Fails,
+ *     naming the offender (tie, face, vertex), and leaves the previous list in place for a face outside [0, tot_NF), a vertex outside [0, tot_NV),
+ *     a vertex that is a corner of its own face, a coordinate that is not finite or outside [0, 1], a triple that does not sum to 1 within 1e-9
+ *     (coordinates are used as given), a negative or non-finite weight.  A member of a scene group cannot take a longer list than it had when the
+ *     group was created: set the ties first.
+ *   tsl_tie_count: n.  tsl_contact_counts keeps its two numbers.
+ *   tsl_tie_force: out_host (n x 3) = -k_tie w_i r_i, the force tie i applies to its vertex at the state pos; frozen dofs are NOT masked.
+ *   tsl_tie_residuals: out_host (n x 3) = r_i.
+ *   tsl_tie_grad: out_host (n) = k_tie g_i, g_i = -sum_a sum_{c free} p_{a, c} c_a r_{i, c} at the tape state pos: the contribution of one reverse
+ *     step to d(loss)/d(w_i), sign of tsl_param_grad_keys; p_dev == NULL: the solution of the last tsl_adjoint_step.  The "k_tie" key of
+ *     tsl_param_grad_keys is sum_i w_i g_i. */
+int tsl_set_ties(tsl_ctx* ctx, const int32_t* vertices_host, const int32_t* faces_host, const double* bary_host, const double* weights_host, int32_t n);
+int tsl_tie_count(tsl_ctx* ctx, int32_t* out_host);
+int tsl_tie_force(tsl_ctx* ctx, const double* pos_dev, double* out_host);
+int tsl_tie_residuals(tsl_ctx* ctx, const double* pos_dev, double* out_host);
+int tsl_tie_grad(tsl_ctx* ctx, const double* pos_dev, const double* p_dev, double* out_host);
+
 /* BaseScene.compute_energy (BaseScene.py:427-451) at the given state, constraints as last detected. */
 int tsl_energy(tsl_ctx* ctx, const double* pos_dev, const double* prev_pos_dev, const double* vel_dev,
                const double* ref_angle_dev, double* energy_host);
@@ -282,7 +310,8 @@ int tsl_friction_grad(tsl_ctx* ctx, const double* pos_dev, double* out_host);
  * "elastic<i>.lam" (both material models, alpha fixed), "k_contact" (normal
  * term of every vertex-triangle slot and the friction weights c_k = -mu k_contact (gap - eps) of the detection), "mu_cloth_elastic",
  * "mu_cloth_cloth" (friction of the slots whose pair uses that live parameter, the pair's factor kept: d c_k = c_k / mu_live),
- * "k_handle" (soft handles: -sum_i w_i p_{v_i} . (x_{v_i} - t_i) over free dofs with the targets as last set; exactly 0 with no handles) -- eleven key forms.
+ * "k_handle" (soft handles: -sum_i w_i p_{v_i} . (x_{v_i} - t_i) over free dofs with the targets as last set; exactly 0 with no handles),
+ * "k_tie" (ties: sum_i w_i g_i of tsl_tie_grad; exactly 0 with no ties; resolved ahead of the key table, its partial sums lie behind the table's) -- twelve key forms.
  * p_dev == NULL: the solution of the last tsl_adjoint_step (as tsl_param_grad uses it); otherwise any 3*tot_NV vector (original vertex order).
  * pos = tape state x_s, ref_angle = tape rest angles of step s-1 (needed by the Kb keys only); contact constraints as last detected / as the
  * last adjoint step left them -- c_k and dx0 are records of the detection, the derivative does not differentiate detection.

@@ -214,6 +214,45 @@ class TslContext:
         check(self.L.tsl_frame_grad(self.h, _ptr(p), out.ctypes.data), "tsl_frame_grad")
         return out
 
+    # ---- ties (tsl_set_ties; stiffness: set_param("k_tie", k))
+    def set_ties(self, verts, faces, bary, weights=None):
+        """n ties: global vertex verts[i] to the barycentric point bary[i] of the global face faces[i]; weights None: all 1; an empty list removes them"""
+        v = _np(verts, np.int32).reshape(-1)
+        f = _np(faces, np.int32).reshape(-1)
+        b = _np(bary, np.float64).reshape(-1, 3)
+        w = None if weights is None else _np(weights, np.float64).reshape(-1)
+        n = len(v)
+        assert f.shape == v.shape and b.shape == (n, 3) and (w is None or w.shape == v.shape), (v.shape, f.shape, b.shape)
+        check(self.L.tsl_set_ties(self.h, v.ctypes.data if n else None, f.ctypes.data if n else None, b.ctypes.data if n else None,
+                                  None if w is None or not n else w.ctypes.data, n), "tsl_set_ties")
+
+    def tie_count(self):
+        out = C.c_int32(0)
+        check(self.L.tsl_tie_count(self.h, C.byref(out)), "tsl_tie_count")
+        return int(out.value)
+
+    def tie_force(self, pos):
+        """(n, 3) -k_tie w_i r_i: the force every tie applies to its vertex at the state pos (frozen dofs not masked)"""
+        self.refresh_stream()
+        out = np.zeros((self.tie_count(), 3))
+        check(self.L.tsl_tie_force(self.h, _ptr(pos), out.ctypes.data), "tsl_tie_force")
+        return out
+
+    def tie_residuals(self, pos):
+        """(n, 3) r_i = x_v - sum_a b_a x_{t_a} at the state pos"""
+        self.refresh_stream()
+        out = np.zeros((self.tie_count(), 3))
+        check(self.L.tsl_tie_residuals(self.h, _ptr(pos), out.ctypes.data), "tsl_tie_residuals")
+        return out
+
+    def tie_grad(self, pos, p=None):
+        """(n,) contribution of one reverse step to d(loss)/d(w_i) at the tape state pos; p None: the solution of the last adjoint_step, else a
+        3 * tot_NV device vector"""
+        self.refresh_stream()
+        out = np.zeros(self.tie_count())
+        check(self.L.tsl_tie_grad(self.h, _ptr(pos), _ptr(p), out.ctypes.data), "tsl_tie_grad")
+        return out
+
     # ---- engine calls
     def energy(self, pos, prev_pos, vel, ref_angle):
         self.refresh_stream()
@@ -281,7 +320,7 @@ class TslContext:
 
     def param_grads(self, pos, ref_angle, keys, p=None):
         """{key: sum over the free dofs of p . d(force)/d(key)} at the tape state pos (tsl_param_grad_keys): keys as tsl_set_param spells them
-        ("cloth<i>.Kl|Ka|Kb|stvk_mu|stvk_lam", "elastic<i>.mu|lam", "k_contact", "mu_cloth_elastic", "mu_cloth_cloth", "k_handle"); p None: the solution of the last
+        ("cloth<i>.Kl|Ka|Kb|stvk_mu|stvk_lam", "elastic<i>.mu|lam", "k_contact", "mu_cloth_elastic", "mu_cloth_cloth", "k_handle", "k_tie"); p None: the solution of the last
         adjoint_step, else a 3 * tot_NV device vector"""
         keys = list(keys)
         if not keys:
@@ -315,14 +354,14 @@ class TslContext:
         return sp.bsr_matrix((vals, col, rp), shape=(n, n)).tocsr()
 
     def constraints(self):
-        m = self.max_n_constraints
+        m = self.max_n_constraints + self.tie_count()   # (the tie slots lie behind the detected ones)
         idx = np.zeros((m, 4), np.int32); w = np.zeros((m, 3)); k = np.zeros(m); dx0 = np.zeros((m, 3)); T = np.zeros((m, 6)); n = np.zeros((m, 3)); mu = np.zeros(m)
         cnt = check(self.L.tsl_constraints_export(self.h, idx.ctypes.data, w.ctypes.data, k.ctypes.data, dx0.ctypes.data, T.ctypes.data, n.ctypes.data,
                                                   mu.ctypes.data, m), "tsl_constraints_export")
         return dict(idx=idx[:cnt], w=w[:cnt], k=k[:cnt], dx0=dx0[:cnt], T=T[:cnt], n=n[:cnt], mu=mu[:cnt])
 
     def contact_blocks(self, masked=True):
-        m = self.max_n_constraints
+        m = self.max_n_constraints + self.tie_count()
         blk = np.zeros((m, 12, 12))
         cnt = check(self.L.tsl_contact_blocks_export(self.h, blk.ctypes.data, m, int(masked)), "tsl_contact_blocks_export")
         return blk[:cnt]

@@ -30,7 +30,7 @@ static int adjoint_pre(tsl_ctx* c, const AdjStep& t) {
   // contacts re-detected at pos = prev_pos = x_{s-1} (copy_pos_only + calc_vn + f_contact + contact_analysis)
   int nc = 0;
   if (c->contact_enable) TSL_TRY(tsl_contact_detect(c, t.x_prev, t.x_prev, &nc));
-  else { c->nc = 0; c->nc_ee = 0; c->ds.cons_checked = false; }
+  else TSL_TRY(contact_slots_none(c));
   ClothArgs CA = cloth_args(c);
   TSL_TRY(ensure_vg_stage(c));
   // pos = x_s, ref_angle = ref_{s-1}: init_folding + ref_angle_backprop_a2ax
@@ -54,7 +54,7 @@ static int adjoint_pre(tsl_ctx* c, const AdjStep& t) {
     if (c->vals_pc.n == 0 && c->vals_pc.alloc(c->vals.n)) return tsl_fail("out of device memory (vals_pc)");
     HIP_OK(hipMemcpyAsync(c->vals_pc.p, c->vals.p, c->vals.n * sizeof(double), hipMemcpyDeviceToDevice, s));
     if (c->nc > 0) {
-      if (c->c_H_pc.n == 0 && c->c_H_pc.alloc(c->c_H.n)) return tsl_fail("out of device memory (c_H_pc)");
+      if (c->c_H_pc.n < c->c_H.n && c->c_H_pc.alloc(c->c_H.n)) return tsl_fail("out of device memory (c_H_pc)");
       HIP_OK(hipMemcpyAsync(c->c_H_pc.p, c->c_H.p, (size_t)c->nc * 144 * sizeof(double), hipMemcpyDeviceToDevice, s));
     }
     c->pc_frozen = true;
@@ -81,9 +81,12 @@ static int adjoint_post(tsl_ctx* c, const AdjStep& t) {
                        c->frozen.p, c->c_Hfull.p, c->pdir.p, t.tmp_z_frozen);
   }
   // contact_energy_backprop(step-1) ; ref_angle_backprop_x2a
-  if (c->nc > 0) {
-    if (c->c_G.n < 12 * (size_t)c->max_n_constraints) { if (c->c_G.alloc(12 * (size_t)c->max_n_constraints)) return -1; }
+  // (a tie's energy depends on the current positions only: it carries nothing into the earlier steps.  Its rows of c_G are cleared, so that the
+  // row gather adds zeros for them and not what the last assembly left there)
+  if (c->nc > c->nc_tie) {
+    if (c->c_G.n < 12 * contact_cap(c)) { if (c->c_G.alloc(12 * contact_cap(c))) return -1; }
     const int nvf = contact_nvf(c);
+    if (c->nc_tie > 0) HIP_OK(hipMemsetAsync(c->c_G.p + 12 * (size_t)(c->nc - c->nc_tie), 0, 12 * (size_t)c->nc_tie * sizeof(double), s));
     if (nvf > 0) hipLaunchKernelGGL(k_contact_backprop, dim3(nblk(nvf, 64)), dim3(64), 0, s, nvf, contact_args(c), t.x_s, c->pdir.p, c->c_G.p);
     if (c->nc_ee > 0) hipLaunchKernelGGL(k_ee_backprop, dim3(nblk(c->nc_ee, 64)), dim3(64), 0, s, c->nc_ee, ee_args(contact_args(c), nvf), t.x_s, c->pdir.p, c->c_G.p + 12 * (size_t)nvf);
     hipLaunchKernelGGL(k_contact_row_gather, dim3(nblk((long)NV * 64, 256)), dim3(256), 0, s, NV, (const int*)c->rowpos.p, (const int*)c->cr_ptr.p, (const int*)c->cr_ent.p,

@@ -9,6 +9,7 @@
 #pragma once
 
 #include "k_solver.hpp"
+#include "k_tie.hpp"
 #include "tsl_ctx.hpp"
 #include "tsl_device.hpp"
 
@@ -1092,13 +1093,49 @@ static int contact_alloc(tsl_ctx* c, const tsl_scene_desc* d) {
   return 0;
 }
 
+static TieArgs tie_args(const tsl_ctx* c) { return TieArgs{c->n_tie, c->ti_idx.p, c->ti_b.p, c->ti_w.p, c->k_tie}; }
+
+// The tail of every road to a constraint set -- a detection, its early return, a step or a reverse step with contacts switched off, a new tie list:
+// c->nc and c->nc_ee hold the detected slots; the tie slots are appended behind them (k_tie.hpp; none without ties or with k_tie = 0), then the
+// row lists of all slots are built.  Runs before ds.cons_checked is consulted.
+static int contact_slots_finish(tsl_ctx* c) {
+  hipStream_t s = c->stream;
+  c->nc_tie = 0;
+  if (ties_on(c)) {
+    const size_t o = (size_t)c->nc;
+    hipLaunchKernelGGL(k_tie_slots, dim3(cnblk(6 * (long)c->n_tie, 256)), dim3(256), 0, s, tie_args(c), c->c_idx.p + 4 * o, c->c_w.p + 3 * o, c->c_n.p + 3 * o, c->c_dx0.p + 3 * o,
+                       c->c_k.p + o, c->c_mu.p + o, c->c_T.p + 6 * o, c->c_kind.p + o);
+    c->nc_tie = c->n_tie;
+    c->nc += c->n_tie;
+  }
+  if (c->nc > 0) {
+    const int n1 = c->NV + 1;
+    const size_t cap4 = 4 * contact_cap(c);
+    if (c->cr_ptr.n == 0) { if (c->cr_ptr.alloc(n1) | c->cr_cnt.alloc(n1) | c->cr_fill.alloc(n1)) return -1; }
+    if (c->cr_ent.n < cap4) { if (c->cr_ent.alloc(cap4) | c->cr_rows.alloc(cap4) | c->cr_tmp.alloc(cap4)) return -1; }
+    HIP_OK(hipMemsetAsync(c->cr_cnt.p, 0, n1 * sizeof(int), s));
+    HIP_OK(hipMemsetAsync(c->cr_fill.p, 0, n1 * sizeof(int), s));
+    hipLaunchKernelGGL(k_cr_count, dim3(cnblk(4 * (long)c->nc, 256)), dim3(256), 0, s, c->nc, c->c_idx.p, c->rowpos.p, c->cr_cnt.p);
+    scan_exclusive(s, n1, c->cr_cnt.p, c->cr_ptr.p, c->scan_tmp.p);
+    hipLaunchKernelGGL(k_cr_fill, dim3(cnblk(4 * (long)c->nc, 256)), dim3(256), 0, s, c->nc, c->c_idx.p, c->rowpos.p, (const int*)c->cr_ptr.p, c->cr_fill.p, c->cr_tmp.p);
+    hipLaunchKernelGGL(k_cr_rank, dim3(cnblk(4 * (long)c->nc, 256)), dim3(256), 0, s, c->nc, c->c_idx.p, c->rowpos.p, (const int*)c->cr_ptr.p, (const int*)c->cr_tmp.p, c->cr_ent.p, c->cr_rows.p);
+    HIP_OK(hipGetLastError());
+  }
+  return 0;
+}
+// the constraint set of a step or a reverse step with contacts switched off: no detected slots, the ties
+static int contact_slots_none(tsl_ctx* c) {
+  c->nc = 0; c->nc_ee = 0; c->ds.cons_checked = false;
+  return contact_slots_finish(c);
+}
+
 extern "C" int tsl_contact_reset(tsl_ctx* c) { Scope scope(c); return c->proj_flag.zero(c->stream); }
 
 extern "C" int tsl_contact_detect(tsl_ctx* c, const double* pos, const double* prev, int32_t* nc_host) {
   Scope scope(c);
   hipStream_t s = c->stream;
   const int NV = c->NV;
-  c->nc = 0; c->nc_ee = 0;
+  c->nc = 0; c->nc_ee = 0; c->nc_tie = 0;
   c->bd_valid = false;
   c->ds.cons_checked = false;   // the factorisation plan compares the new constraint list with the one it was made for
   const bool ee = c->contact_ee && !c->ee_desc.empty();
@@ -1106,7 +1143,7 @@ extern "C" int tsl_contact_detect(tsl_ctx* c, const double* pos, const double* p
   if (ee) HIP_OK(hipMemsetAsync(c->ee_nvf.p + 1, 0, sizeof(int), c->stream));   // [1]: largest oversized edge-midpoint bucket
   bool any_self = false;
   for (int v : c->self_contact) any_self |= v != 0;
-  if ((c->n_body < 2 && !any_self) || c->NF == 0) { if (nc_host) *nc_host = 0; return 0; }   // a single body can still touch itself (geometry_self.py)
+  if ((c->n_body < 2 && !any_self) || c->NF == 0) { if (nc_host) *nc_host = 0; return contact_slots_finish(c); }   // a single body can still touch itself (geometry_self.py)
   HIP_OK(hipMemsetAsync(c->nc_dev.p + 1, 0, sizeof(int), s));
   // calc_vn
   hipLaunchKernelGGL(k_vn_gather, dim3(cnblk(NV, 256)), dim3(256), 0, s, NV, (const int*)c->vnf_ptr.p, (const int*)c->vnf_lst.p, c->faces.p, pos, c->vn.p);
@@ -1283,20 +1320,7 @@ extern "C" int tsl_contact_detect(tsl_ctx* c, const double* pos, const double* p
   nc += n_ee;
   c->nc = nc; c->nc_ee = n_ee;
   if (nc_host) *nc_host = c->nc;
-  if (c->nc > 0) {
-    const int n1 = NV + 1;
-    if (c->cr_ptr.n == 0) {
-      if (c->cr_ptr.alloc(n1) | c->cr_cnt.alloc(n1) | c->cr_fill.alloc(n1) | c->cr_ent.alloc(4 * (size_t)c->max_n_constraints) | c->cr_rows.alloc(4 * (size_t)c->max_n_constraints) | c->cr_tmp.alloc(4 * (size_t)c->max_n_constraints)) return -1;
-    }
-    HIP_OK(hipMemsetAsync(c->cr_cnt.p, 0, n1 * sizeof(int), s));
-    HIP_OK(hipMemsetAsync(c->cr_fill.p, 0, n1 * sizeof(int), s));
-    hipLaunchKernelGGL(k_cr_count, dim3(cnblk(4 * (long)c->nc, 256)), dim3(256), 0, s, c->nc, c->c_idx.p, c->rowpos.p, c->cr_cnt.p);
-    scan_exclusive(s, n1, c->cr_cnt.p, c->cr_ptr.p, c->scan_tmp.p);
-    hipLaunchKernelGGL(k_cr_fill, dim3(cnblk(4 * (long)c->nc, 256)), dim3(256), 0, s, c->nc, c->c_idx.p, c->rowpos.p, (const int*)c->cr_ptr.p, c->cr_fill.p, c->cr_tmp.p);
-    hipLaunchKernelGGL(k_cr_rank, dim3(cnblk(4 * (long)c->nc, 256)), dim3(256), 0, s, c->nc, c->c_idx.p, c->rowpos.p, (const int*)c->cr_ptr.p, (const int*)c->cr_tmp.p, c->cr_ent.p, c->cr_rows.p);
-    HIP_OK(hipGetLastError());
-  }
-  return 0;
+  return contact_slots_finish(c);
 }
 
 // the arguments of the edge-edge slots: every per-constraint array from slot nvf on
@@ -1321,7 +1345,7 @@ static int contact_assemble(tsl_ctx* c, const double* pos, int spd, double* grad
   ContactArgs A;
   A.idx = c->c_idx.p; A.w = c->c_w.p; A.n = c->c_n.p; A.dx0 = c->c_dx0.p; A.k = c->c_k.p; A.mu = c->c_mu.p; A.T = c->c_T.p;
   A.k_contact = c->k_contact; A.eps_contact = c->eps_contact; A.eps_vh = c->eps_v * c->dt;
-  if (grad && c->c_G.n < 12 * (size_t)c->max_n_constraints) { if (c->c_G.alloc(12 * (size_t)c->max_n_constraints)) return -1; }
+  if (grad && c->c_G.n < 12 * contact_cap(c)) { if (c->c_G.alloc(12 * contact_cap(c))) return -1; }
   double* cg = grad ? c->c_G.p : (double*)nullptr;   // per-constraint gradients, summed per vertex by k_contact_row_gather
   const int nvf = contact_nvf(c);
   if (nvf > 0) {
@@ -1334,6 +1358,10 @@ static int contact_assemble(tsl_ctx* c, const double* pos, int spd, double* grad
     double* cge = cg ? cg + 12 * (size_t)nvf : (double*)nullptr;
     if (c->spd_literal && spd == 1) hipLaunchKernelGGL((k_contact_assemble_coop<true, true>), dim3(cnblk((long)c->nc_ee * 16, 256)), dim3(256), 0, s, c->nc_ee, E, pos, spd, Hf, cge);
     else hipLaunchKernelGGL((k_contact_assemble_coop<false, true>), dim3(cnblk((long)c->nc_ee * 16, 256)), dim3(256), 0, s, c->nc_ee, E, pos, spd, Hf, cge);
+  }
+  if (c->nc_tie > 0) {   // the tie slots behind them: constant blocks, the gradient from the positions
+    const size_t t0 = (size_t)(c->nc - c->nc_tie);
+    hipLaunchKernelGGL(k_tie_assemble, dim3(cnblk(144 * (long)c->nc_tie, 256)), dim3(256), 0, s, tie_args(c), pos, c->c_Hfull.p + 144 * t0, cg ? cg + 12 * t0 : (double*)nullptr);
   }
   hipLaunchKernelGGL(k_contact_mask, dim3(cnblk((long)c->nc * 144, 256)), dim3(256), 0, s, c->nc, c->c_idx.p, c->frozen.p, c->c_Hfull.p, c->c_H.p);
   // the diagonal 3 x 3 blocks of the contact terms feed the block-Jacobi inverse and the hierarchy's Galerkin diagonal only: a solve that goes to the

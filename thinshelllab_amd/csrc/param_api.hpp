@@ -118,8 +118,10 @@ extern "C" int tsl_param_grad_keys(tsl_ctx* c, const double* pos, const double* 
   std::vector<PgRow> kr(n_keys);
   bool need[PG_NCLASS] = {};
   std::string err;
+  std::vector<int> tie_keys;   // "k_tie" is resolved ahead of the table (tie_host.hpp): its partials lie behind the table's, so no row of the table moves
   for (int j = 0; j < n_keys; j++) {
     if (!keys[j]) return tsl_fail("tsl_param_grad_keys: key %d is null", j);
+    if (!strcmp(keys[j], PG_TIE_KEY)) { tie_keys.push_back(j); kr[j] = PgRow{PG_HANDLE, 0}; continue; }   // (a placeholder row: its table entry is rewritten below)
     if (pg_resolve_key(keys[j], n_cloth, n_el, kr[j], err)) return tsl_fail("%s", err.c_str());
     const int row = kr[j].row;
     if (kr[j].cls == PG_CONTACT) {
@@ -142,7 +144,10 @@ extern "C" int tsl_param_grad_keys(tsl_ctx* c, const double* pos, const double* 
   nb[PG_STVK] = c->n_stvk > 0 ? groups(c->n_cface) : 0; nb[PG_HANDLE] = groups(c->n_handle);
   PgLayout L;
   if (pg_layout(n_cloth, n_el, nb, need, kr, L, err)) return tsl_fail("%s", err.c_str());
-  if (c->pg_part.n < std::max<size_t>(L.total, 1)) TSL_TRY(c->pg_part.alloc(std::max<size_t>(L.total, 1)));
+  const PgTiePlace tp = pg_tie_place(L.total, !tie_keys.empty() && c->n_tie > 0 ? nblk(c->n_tie, PG_TIE_THREADS) : 0);
+  if (tp.total > (size_t)INT32_MAX) return tsl_fail("tsl_param_grad_keys: too many partials");
+  for (int j : tie_keys) { PgTable& tab = L.chunks[j / PG_KEYS_PER_LAUNCH]; tab.off[j % PG_KEYS_PER_LAUNCH] = (int)tp.off; tab.cnt[j % PG_KEYS_PER_LAUNCH] = tp.cnt; }
+  if (c->pg_part.n < std::max<size_t>(tp.total, 1)) TSL_TRY(c->pg_part.alloc(std::max<size_t>(tp.total, 1)));
   if (c->pg_out.n < (size_t)n_keys + 2) TSL_TRY(c->pg_out.alloc((size_t)n_keys + 2));
   const double* p = p_dev ? p_dev : c->pdir.p;
   const int* fz = c->frozen.p;
@@ -154,6 +159,7 @@ extern "C" int tsl_param_grad_keys(tsl_ctx* c, const double* pos, const double* 
   }
   if (on(PG_HANDLE))
     handle_dispatch(c, [&](auto NC) { hipLaunchKernelGGL(k_pg_handle<NC>, dim3(nb[PG_HANDLE]), dim3(PG_THREADS), 0, s, handle_args(c), pos, p, fz, part + L.off[PG_HANDLE]); });
+  if (tp.cnt > 0) hipLaunchKernelGGL(k_pg_tie, dim3(tp.cnt), dim3(PG_TIE_THREADS), 0, s, tie_args(c), pos, p, fz, (double*)nullptr, part + tp.off);
   if (on(PG_STVK)) hipLaunchKernelGGL(k_pg_stvk, dim3(nb[PG_STVK]), dim3(PG_THREADS), 0, s, cloth_args(c), n_cloth, pos, p, fz, part + L.off[PG_STVK], stvk_args(c));
   if (on(PG_HINGE)) hipLaunchKernelGGL(k_pg_hinge, dim3(nb[PG_HINGE]), dim3(PG_THREADS), 0, s, cloth_args(c), n_cloth, pos, ref, p, fz, part + L.off[PG_HINGE]);
   if (on(PG_TET)) hipLaunchKernelGGL(k_pg_tet, dim3(nb[PG_TET]), dim3(PG_THREADS), 0, s, tet_args(c), n_el, pos, p, fz, part + L.off[PG_TET]);

@@ -391,6 +391,13 @@ struct tsl_ctx {
   std::vector<size_t> ee_f0, ee_t0, ee_s0;
   DevBuf<unsigned long long> ee_lmax;   // per body: bits of its longest edge at the detection's positions
   DevBuf<int> ee_qcnt, ee_qscan, ee_cand, ee_scan_tmp, ee_nvf;
+  // ---- ties (tsl_set_ties, k_tie.hpp): the list as copies the context owns, and its constraint slots [nc - nc_tie, nc) behind the edge-edge ones.
+  // The slots are there whenever ties exist and k_tie != 0 (nc_tie = n_tie), whatever a detection finds; else nc_tie = 0.  The per-slot arrays hold
+  // max_n_constraints + n_tie slots (contact_cap)
+  int n_tie = 0, nc_tie = 0;
+  double k_tie = 0.0;
+  DevBuf<int> ti_idx;                  // n x 4 (t0, t1, t2, v)
+  DevBuf<double> ti_b, ti_w, ti_out;   // n x 3, n, n x 3 (read-outs of tsl_tie_force / tsl_tie_residuals / tsl_tie_grad)
 
   // ---- multigrid preconditioner
   std::vector<MgCloth*> mg;
@@ -441,8 +448,12 @@ struct tsl_ctx {
   }
 };
 
-// The constraint slots of the last detection: the vertex-triangle ones [0, contact_nvf), then the edge-edge ones ("contact_ee") up to nc
-static inline int contact_nvf(const tsl_ctx* c) { return c->nc - c->nc_ee; }
+// The constraint slots: the vertex-triangle ones of the last detection [0, contact_nvf), then its edge-edge ones ("contact_ee"), then the ties up to nc
+static inline int contact_nvf(const tsl_ctx* c) { return c->nc - c->nc_ee - c->nc_tie; }
+// slots the per-slot arrays hold: the scene's cap for the detected ones plus the ties
+static inline size_t contact_cap(const tsl_ctx* c) { return (size_t)c->max_n_constraints + (size_t)c->n_tie; }
+// the tie kernels of an energy / assembly run, and the tie slots exist, only while this holds: without it the launches are the ones they were
+static inline bool ties_on(const tsl_ctx* c) { return c->n_tie > 0 && c->k_tie != 0.0; }
 
 // Every entry point runs on the context's own stream; Enter/leave order it after / before the caller's stream.
 struct Scope {

@@ -52,6 +52,7 @@ int tsl_fail(const char* fmt, ...) {
 static inline int nblk(long n, int b) { return (int)((n + b - 1) / b); }
 static inline int gsz(size_t n) { size_t b = (n + 255) / 256; return (int)std::min<size_t>(std::max<size_t>(b, 1), 4096); }
 #include "handle_api.hpp"
+#include "tie_api.hpp"
 #include "k_scene.hpp"
 
 // ------------------------------------------------------------------------------------------------
@@ -275,6 +276,11 @@ extern "C" int tsl_set_param(tsl_ctx* c, const char* key, double v) {
     if (!(v >= 0.0) || !std::isfinite(v)) return tsl_fail("tsl_set_param: k_handle must be finite and >= 0 (got %g)", v);
     c->k_handle = v;
   }
+  else if (k == "k_tie") {
+    if (!(v >= 0.0) || !std::isfinite(v)) return tsl_fail("tsl_set_param: k_tie must be finite and >= 0 (got %g)", v);
+    c->k_tie = v;
+    TSL_TRY(tie_slots_refresh(c));   // (the tie slots exist while k_tie != 0)
+  }
   else if (k == "cg_tol") c->cg_tol = v;
   else if (k == "cg_maxit") c->cg_maxit = (int)v;
   else if (k == "newton_cap") c->newton_cap = (int)v;
@@ -352,14 +358,16 @@ static int energy_async(tsl_ctx* c, const double* pos, const double* prev, const
   const int nvf = contact_nvf(c);
   const int nb1 = nblk(nmax, 256), nb2 = nvf > 0 ? nblk(nvf, 64) : 0, nb3 = c->nc_ee > 0 ? nblk(c->nc_ee, 64) : 0;
   const int nb4 = handles_on(c) ? nblk(c->n_handle, 256) : 0;   // soft handles: their partials behind the contact ones
-  const size_t n_part = (size_t)nb1 + (size_t)nblk(c->max_n_constraints, 64) + 1 + (size_t)nblk(c->n_handle, 256);
+  const int nb5 = ties_on(c) ? nblk(c->n_tie, 64) : 0;          // ties: one partial per wave, behind the handle ones
+  const size_t n_part = (size_t)nb1 + (size_t)nblk(c->max_n_constraints, 64) + 1 + (size_t)nblk(c->n_handle, 256) + (size_t)nblk(c->n_tie, 64);
   if (c->e_part.n < n_part) { if (c->e_part.alloc(n_part)) return -1; }
   if (c->n_stvk > 0) hipLaunchKernelGGL(k_energy_stvk, dim3(nb1), dim3(256), 0, s, vert_args(c), cloth_args(c), tet_args(c), pos, prev, vel, ref, c->e_part.p, stvk_args(c));
   else hipLaunchKernelGGL(k_energy, dim3(nb1), dim3(256), 0, s, vert_args(c), cloth_args(c), tet_args(c), pos, prev, vel, ref, c->e_part.p);
   if (nb2 > 0) hipLaunchKernelGGL(k_contact_energy, dim3(nb2), dim3(64), 0, s, nvf, contact_args(c), pos, c->e_part.p + nb1);
   if (nb3 > 0) hipLaunchKernelGGL(k_ee_energy, dim3(nb3), dim3(64), 0, s, c->nc_ee, ee_args(contact_args(c), nvf), pos, c->e_part.p + nb1 + nb2);
   if (nb4 > 0) handle_dispatch(c, [&](auto NC) { hipLaunchKernelGGL(k_handle_energy<NC>, dim3(nb4), dim3(256), 0, s, handle_args(c), pos, c->e_part.p + nb1 + nb2 + nb3); });
-  hipLaunchKernelGGL(k_energy_final, dim3(1), dim3(256), 0, s, nb1 + nb2 + nb3 + nb4, (const double*)c->e_part.p, &SC(c)->energy);
+  if (nb5 > 0) hipLaunchKernelGGL(k_tie_energy, dim3(nblk(c->n_tie, 256)), dim3(256), 0, s, tie_args(c), pos, c->e_part.p + nb1 + nb2 + nb3 + nb4);
+  hipLaunchKernelGGL(k_energy_final, dim3(1), dim3(256), 0, s, nb1 + nb2 + nb3 + nb4 + nb5, (const double*)c->e_part.p, &SC(c)->energy);
   return 0;
 }
 static int energy_sync(tsl_ctx* c, const double* pos, const double* prev, const double* vel, const double* ref, double* E) {
@@ -564,7 +572,7 @@ static int assemble(tsl_ctx* c, const double* pos, const double* prev, const dou
   // ---- allocations the launches rely on (staging slots of the gradient, element records of the matrix)
   TSL_TRY(ensure_vg_stage(c));
   if (c->n_tet > 0 && c->cg_trec.n < 144 * (size_t)c->n_tet) { if (c->cg_trec.alloc(144 * (size_t)c->n_tet)) return tsl_fail("out of device memory (element records)"); }
-  if (grad && c->nc > 0 && c->c_G.n < 12 * (size_t)c->max_n_constraints) { if (c->c_G.alloc(12 * (size_t)c->max_n_constraints)) return -1; }
+  if (grad && c->nc > 0 && c->c_G.n < 12 * contact_cap(c)) { if (c->c_G.alloc(12 * contact_cap(c))) return -1; }
   if (c->n_cgblk > 0 && c->n_cface > 0 && c->cg_frec.n == 0) {
     if (c->cg_hrec.alloc((size_t)std::max(c->n_hinge, 1) * 16) | c->cg_frec.alloc((size_t)c->n_cface * 81)) return tsl_fail("out of device memory (cloth element records)");
   }
@@ -1011,7 +1019,7 @@ static int forward_spd_pc(tsl_ctx* c) {
   if (!c->in_step || c->pc_separate || !c->st_pos || c->mg.empty() || c->mg_enable == 0) return 1;
   hipStream_t s = c->stream;
   if (c->vals_pc.n == 0 && c->vals_pc.alloc(c->vals.n)) return tsl_fail("out of device memory (vals_pc)");
-  if (c->nc > 0 && c->c_H_pc.n == 0 && c->c_H_pc.alloc(c->c_H.n)) return tsl_fail("out of device memory (c_H_pc)");
+  if (c->nc > 0 && c->c_H_pc.n < c->c_H.n && c->c_H_pc.alloc(c->c_H.n)) return tsl_fail("out of device memory (c_H_pc)");
   // operator -> the "pc" buffers, assemble the SPD variant into the regular ones, then swap the roles back
   std::swap(c->vals.p, c->vals_pc.p);
   if (c->nc > 0) std::swap(c->c_H.p, c->c_H_pc.p);
@@ -1904,7 +1912,7 @@ static int newton_step(const std::vector<StepMember>& m, GroupPool* pool, tsl_ct
     tsl_ctx* c = m[i].c;
     int nc = 0;
     if (c->contact_enable) TSL_TRY(tsl_contact_detect(c, m[i].pos, m[i].prev, &nc));
-    else { c->nc = 0; c->nc_ee = 0; c->ds.cons_checked = false; }
+    else TSL_TRY(contact_slots_none(c));
     st[i].nc = nc;
   }
   const long gfact0 = g ? g->ds.n_factor : 0;

@@ -86,6 +86,47 @@ def validate_surface_handles(tot_NF, face_ids, bary, weights=None):
     return f.astype(np.int32), np.ascontiguousarray(b), w
 
 
+def validate_ties(tot_NV, faces_tab, vertex_ids, face_ids, bary, weights=None):
+    """The checks of tsl_set_ties on the host, with its messages: returns (int32 vertex ids, int32 face ids, float64 coordinates (n, 3), float64
+    weights or None) or raises ValueError naming the offender -- a face outside [0, tot_NF), a vertex outside [0, tot_NV), a vertex that is a corner of
+    its own face, a barycentric coordinate that is not finite or outside [0, 1], a triple whose sum differs from 1 by more than 1e-9, a negative or
+    non-finite weight.  faces_tab: the scene's global face table (tot_NF, 3).  The coordinates are used as given, not renormalised."""
+    v = np.asarray(vertex_ids)
+    f = np.asarray(face_ids)
+    for name, a in (("vertex", v), ("face", f)):
+        if a.ndim != 1 or (a.size and not np.issubdtype(a.dtype, np.integer)):
+            raise ValueError(f"set_ties: {name} ids must be a flat list of integers (got shape {a.shape}, dtype {a.dtype})")
+    if v.shape != f.shape:
+        raise ValueError(f"set_ties: {v.size} vertices for {f.size} faces")
+    v = v.astype(np.int64); f = f.astype(np.int64)
+    b = np.asarray(bary, dtype=np.float64)
+    if b.shape != (f.size, 3):
+        raise ValueError(f"set_ties: barycentric coordinates of shape {b.shape} for {f.size} ties (expected ({f.size}, 3))")
+    w = None
+    if weights is not None:
+        w = np.asarray(weights, dtype=np.float64)
+        if w.shape != f.shape:
+            raise ValueError(f"set_ties: {w.size} weights for {f.size} ties")
+    faces_tab = np.asarray(faces_tab).reshape(-1, 3)
+    tot_NF = len(faces_tab)
+    for i, (vi, fi) in enumerate(zip(v.tolist(), f.tolist())):
+        if fi < 0 or fi >= tot_NF:
+            raise ValueError(f"set_ties: face {fi} of tie {i} out of range [0, {tot_NF})")
+        if vi < 0 or vi >= tot_NV:
+            raise ValueError(f"set_ties: vertex {vi} of tie {i} (face {fi}) out of range [0, {tot_NV})")
+        if vi in faces_tab[fi].tolist():
+            raise ValueError(f"set_ties: vertex {vi} of tie {i} is a corner of its own face {fi}")
+        for a in range(3):
+            if not (np.isfinite(b[i, a]) and 0.0 <= b[i, a] <= 1.0):
+                raise ValueError(f"set_ties: barycentric coordinate {b[i, a]:g} of tie {i} (face {fi}, vertex {vi}) is not finite or outside [0, 1]")
+        tot = (b[i, 0] + b[i, 1]) + b[i, 2]
+        if not abs(tot - 1.0) <= 1e-9:
+            raise ValueError(f"set_ties: barycentric coordinates ({b[i, 0]:g}, {b[i, 1]:g}, {b[i, 2]:g}) of tie {i} (face {fi}, vertex {vi}) sum to {tot:.12g}, not 1")
+        if w is not None and not (w[i] >= 0.0 and np.isfinite(w[i])):
+            raise ValueError(f"set_ties: weight {w[i]:g} of tie {i} (face {fi}, vertex {vi}) is negative or not finite")
+    return v.astype(np.int32), f.astype(np.int32), np.ascontiguousarray(b), w
+
+
 class _SystemMatrix:
     """Stand-in for ``SparseMatrix`` (sparse_solver.py): the matrix itself lives inside the context."""
 
@@ -144,6 +185,12 @@ class BaseScene:
         self._handle_w = None
         self._handle_t = np.zeros((0, 3))
         self.k_handle = 0.0
+        # ties (set_ties, sew): vertex ids, face ids, barycentric coordinates, weights and the stiffness k_tie, kept here and pushed to the engine context lazily
+        self._tie_v = np.zeros(0, np.int32)
+        self._tie_f = np.zeros(0, np.int32)
+        self._tie_b = np.zeros((0, 3))
+        self._tie_w = None
+        self.k_tie = 0.0
         # rigid frames of the handles (set_handle_frames): frame and local point of every handle, position and unit quaternion of every frame
         self._frame_of = np.zeros(0, np.int32)
         self._frame_local = np.zeros((0, 3))
@@ -419,8 +466,12 @@ class BaseScene:
             self._ctx.set_ext_force(self._ext_force_array())
             if self.n_handle:
                 self._push_handles()
+            if self.n_tie:
+                self._push_ties()
             self._dirty.clear()
         if self._dirty:
+            if "ties" in self._dirty:
+                self._push_ties()
             if "handles" in self._dirty:
                 self._push_handles()
             else:
@@ -527,6 +578,52 @@ class BaseScene:
         self._ctx.set_param("k_handle", self.k_handle)
         self._ctx.set_handle_targets(self._handle_t)
         self._push_frames()
+
+    # ------------------------------------------------------------------ ties (no counterpart in the reference)
+    @property
+    def n_tie(self):
+        return len(self._tie_v)
+
+    def set_ties(self, vertex_ids, face_ids, bary, k, weights=None):
+        """Springs between material points: tie i binds the global vertex vertex_ids[i] to the point with barycentric coordinates bary[i] on the global
+        face face_ids[i] of self.faces (a cloth face or a surface face of a FEM body), E = 1/2 k sum_i w_i |x_v - sum_a b_a x_{t_a}|^2 with stiffness
+        k >= 0 in N/m and weights w_i >= 0 (None: all 1).  Any number of ties may share a vertex or a face; the vertex must not be a corner of its
+        face.  An empty list removes the ties.  A member of a SceneGroup sets its ties before the group is created."""
+        v, f, b, w = validate_ties(self.tot_NV, self.faces.to_numpy(), vertex_ids, face_ids, bary, weights)
+        k = float(k)
+        if not (k >= 0.0 and np.isfinite(k)):
+            raise ValueError(f"set_ties: k_tie must be finite and >= 0 (got {k:g})")
+        self._tie_v, self._tie_f, self._tie_b, self._tie_w, self.k_tie = v, f, b, w, k
+        self._dirty.add("ties")
+
+    def sew(self, verts_a, verts_b, k, weights=None):
+        """Vertex-to-vertex stitches: vertex verts_a[i] is tied to vertex verts_b[i] -- to the lowest-numbered face that contains verts_b[i], with a
+        one-hot coordinate on it.  Replaces the tie list (set_ties)."""
+        va = np.asarray(verts_a, np.int64).reshape(-1)
+        vb = np.asarray(verts_b, np.int64).reshape(-1)
+        if va.shape != vb.shape:
+            raise ValueError(f"sew: {va.size} vertices onto {vb.size} vertices")
+        tab = self.faces.to_numpy().reshape(-1, 3)
+        faces, bary = [], np.zeros((len(vb), 3))
+        for i, t in enumerate(vb.tolist()):
+            hit = np.nonzero((tab == t).any(axis=1))[0]
+            if not len(hit):
+                raise ValueError(f"sew: vertex {t} (pair {i}) lies on no face of the scene")
+            faces.append(int(hit[0]))
+            bary[i, int(np.nonzero(tab[hit[0]] == t)[0][0])] = 1.0
+        self.set_ties(va, np.array(faces, np.int64), bary, k, weights)
+
+    def tie_force(self):
+        """(n, 3): the force -k w_i r_i every tie applies to its vertex at the current positions"""
+        return self._ensure_ctx().tie_force(self.pos.t)
+
+    def tie_residuals(self):
+        """(n, 3): r_i = x_v - sum_a b_a x_{t_a} at the current positions"""
+        return self._ensure_ctx().tie_residuals(self.pos.t)
+
+    def _push_ties(self):
+        self._ctx.set_ties(self._tie_v, self._tie_f, self._tie_b, self._tie_w)
+        self._ctx.set_param("k_tie", self.k_tie)
 
     # ------------------------------------------------------------------ rigid frames for the handles (no counterpart in the reference)
     @property

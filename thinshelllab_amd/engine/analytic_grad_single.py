@@ -26,9 +26,15 @@ def handle_tape_init(grad, sys, T):
         grad.frame_pos = Field(torch.zeros((T, grad.n_frame, 3), dtype=torch.float64))
         grad.frame_quat = Field(torch.zeros((T, grad.n_frame, 4), dtype=torch.float64))
         grad.frame_grad = Field(torch.zeros((T, grad.n_frame, 6), dtype=torch.float64))
+    # ties (BaseScene.set_ties): d(loss)/d(weight of tie i) per reverse step
+    grad.n_tie = getattr(sys, "n_tie", 0)
+    if grad.n_tie:
+        grad.tie_grad = Field(torch.zeros((T, grad.n_tie), dtype=torch.float64))
 
 
 def handle_tape_reset(grad):
+    if grad.n_tie:
+        grad.tie_grad.fill(0)
     if grad.n_handle:
         grad.handle_targets.fill(0)
         grad.handle_grad.fill(0)
@@ -62,6 +68,8 @@ def handle_tape_pull(grad, ctx, step):
         grad.handle_grad.t[step] += torch.as_tensor(ctx.handle_grad())
     if grad.n_frame:
         grad.frame_grad.t[step] += torch.as_tensor(ctx.frame_grad())
+    if grad.n_tie:   # tie_grad[step] += d(loss)/d(tie weights) of the reverse step just taken, at the tape state x_step
+        grad.tie_grad.t[step] += torch.as_tensor(ctx.tie_grad(grad.pos_buffer.t[step]))
 
 
 class Grad:
@@ -90,12 +98,16 @@ class Grad:
         self.f_loss_ratio = f_loss_ratio
         self.vertical_only = vertical_only
         self.last_stats = {}
+        # keys of tsl_param_grad_keys (e.g. "k_tie", "k_handle"): every reverse step adds their contribution to grad_params, as analytic_grad_system.Grad does
+        self.param_keys = []
+        self.grad_params = {}
         handle_tape_init(self, sys, T)
 
     def reset(self):
         self.pos_buffer.fill(0)
         self.pos_grad.fill(0)
         self.angleref_grad.fill(0)
+        self.grad_params = {}
         handle_tape_reset(self)
 
     def init_mass(self, sys):
@@ -136,6 +148,9 @@ class Grad:
                                            sys.tmp_z_frozen.t, self.damping)
         self.check_solve(step)
         handle_tape_pull(self, ctx, step)
+        if self.param_keys:
+            for k, v in ctx.param_grads(self.pos_buffer.t[step], self.ref_angle_buffer.t[step - 1], self.param_keys).items():
+                self.grad_params[k] = self.grad_params.get(k, 0.0) + v
         # leave the scene in the state the reference leaves it in (copy_pos_and_refangle + gripper.set)
         sys.copy_pos_and_refangle(self, step)
         if self.n_part > 0 and hasattr(sys, "gripper"):

@@ -8,7 +8,7 @@ accumulates the parameter gradients ``grad_kb`` / ``grad_mu`` / ``grad_lam`` = s
 ``Scene_sliding`` (``contact_energy_backprop_friction``, Scene_sliding.py:139-176, ``tsl_friction_grad``).
 
 Beyond the reference: ``param_keys`` names further scalars, spelled as ``tsl_set_param`` spells them ("cloth<i>.Kl|Ka|Kb",
-"cloth<i>.stvk_mu|stvk_lam" (StVK membrane), "elastic<i>.mu|lam", "k_contact", "mu_cloth_elastic", "mu_cloth_cloth", "k_handle" (soft handles)); every reverse step then adds their
+"cloth<i>.stvk_mu|stvk_lam" (StVK membrane), "elastic<i>.mu|lam", "k_contact", "mu_cloth_elastic", "mu_cloth_cloth", "k_handle" (soft handles), "k_tie" (ties)); every reverse step then adds their
 ``p . d(force)/d(key)`` (``tsl_param_grad_keys``) to ``grad_params[key]``.  Empty (the default): no such call, the reference's behaviour.
 """
 import torch
