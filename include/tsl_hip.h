@@ -103,11 +103,13 @@ int tsl_ctx_create(const tsl_scene_desc* desc, tsl_ctx** out);
 void tsl_ctx_destroy(tsl_ctx* ctx);
 int tsl_set_stream(tsl_ctx* ctx, void* hip_stream);
 
-/* 0-d field writes of the reference and the engine's own switches (42 keys + three patterns; an unknown key is an error).
+/* 0-d field writes of the reference and the engine's own switches (43 keys + three patterns; an unknown key is an error).
  *  Scene (trajopt_folding.py:50,66; Scene_folding.py:30-31; geometry.py:8-19; geometry_self.py:166-230):
  *   "cloth<i>.Kb|Kl|Ka|k_angle", "elastic<i>.mu|lam|alpha", "mu_cloth_elastic", "mu_cloth_cloth", "k_contact", "eps_contact", "eps_v", "damping",
  *   "k_handle" (0 default: stiffness in N/m of the soft handles of tsl_set_handles; negative fails; with 0, or with no handles, no handle kernel is launched),
  *   "k_tie" (0 default: stiffness in N/m of the ties of tsl_set_ties; negative fails; with 0, or with no ties, no tie slot exists and no tie kernel is launched),
+ *   "k_collider" (0 default: stiffness in N/m shared by the half-space colliders of tsl_set_colliders; negative or non-finite fails; with 0, or with no
+ *   colliders, no collider kernel is launched),
  *   "cloth<i>.membrane" (0 default: edge springs Kl + area term Ka, as the reference; 1: a St. Venant-Kirchhoff membrane per face, A0 Psi(F) with
  *   F = [x1 - x0, x2 - x0] Dm^-1, Dm the rest triangle rebuilt from the face's rest lengths (fails naming a face whose lengths violate the triangle
  *   inequality), Psi = mu |E|^2 + lam/2 tr(E)^2, E = (F^T F - I) / 2, A0 the rest area; it replaces the springs and the area term of the cloth's
@@ -246,6 +248,38 @@ int tsl_tie_count(tsl_ctx* ctx, int32_t* out_host);
 int tsl_tie_force(tsl_ctx* ctx, const double* pos_dev, double* out_host);
 int tsl_tie_residuals(tsl_ctx* ctx, const double* pos_dev, double* out_host);
 int tsl_tie_grad(tsl_ctx* ctx, const double* pos_dev, const double* p_dev, double* out_host);
+
+/* Half-space colliders (no reference counterpart: its tables are frozen bodies): up to TSL_MAX_COLLIDERS planes.  Collider j has a unit normal n_j,
+ * fixed once the list is set, an offset o_j that may be set before every step -- the solid side is n_j . x < o_j --, and a friction coefficient
+ * mu_j >= 0; the stiffness "k_collider" of tsl_set_param is shared (0 by default: off), the thickness of the shell is eps_contact, the friction
+ * regularisation eps_v dt.  A per-vertex 8-bit mask says which colliders act on a vertex.  For vertex v and collider j, with x_prev the
+ * start-of-step positions (the prev_pos argument of tsl_energy / tsl_assemble; x_{s-1} in a reverse step):
+ *   d = n . x - o,  d0 = n . x_prev - o,  lam = mu k max(0, eps - d0),  u = T^T (x - x_prev),  r = |u|  (T from n as the contact pairs build theirs)
+ *   E = [d < eps] 1/2 k (d - eps)^2 + lam f0(r),  g = [d < eps] k (d - eps) n + lam f1(r) T u,
+ *   H = [d < eps] k n n^T + lam T (f1 I + [r > 1e-9] (f2 / r) u u^T) T^T  on the vertex's own diagonal block,
+ * positive semi-definite as it stands: every spd mode and "spd_literal" add the same numbers.  No constraint slot, no row list: the plans of the
+ * factorisation and tsl_contact_counts do not depend on colliders.  A plane that moves along its own normal adds no slip.  Nothing is stored per
+ * step; the normal term is evaluated at every evaluation.  Frozen dofs follow the mask rule.  One lane per vertex, no atomics: the same bits run
+ * to run.  With no colliders or k_collider = 0 every launch is the one it was.
+ *   tsl_set_colliders: normals_host (n x 3; normalised here), offsets_host (n), mu_host (n), vertex_mask_host (tot_NV bytes, bit j: collider j acts
+ *     on the vertex; NULL: every collider on every vertex); host pointers, copied; the stream is synchronised; n = 0 removes the colliders.  Fails,
+ *     naming the offender, and leaves the previous list in place for more than TSL_MAX_COLLIDERS colliders, a zero or non-finite normal, a
+ *     non-finite offset, a negative or non-finite mu, a mask byte that names a collider at or above n.
+ *   tsl_set_collider_offsets: offsets_host (n) for the next energy, assemble, step or adjoint step; set the offsets of step s before the reverse
+ *     step s and before tsl_collider_grad.  A non-finite offset fails, naming the collider, and leaves the offsets in place.
+ *   tsl_collider_count: n.
+ *   tsl_collider_force: out_host (n x 3) = -sum_v g_v of collider j at the state (pos, prev_pos): the net force between plane j and the cloth, in the sign of
+ *     tsl_handle_force (what the plane applies to the cloth: + m g along n under a resting cloth); frozen dofs are NOT masked; k_collider = 0: zeros.
+ *   tsl_collider_grad: out_host (n x 2) at the tape state (pos = x_s, prev_pos = x_{s-1}), sign of tsl_handle_grad: column 0 the share of one
+ *     reverse step in d(loss)/d(o_j at step s), -sum_v p_v . (-[d < eps] k n_j + [d0 < eps] mu_j k f1 T u); column 1 the share in d(loss)/d(mu_j),
+ *     -sum_v p_v . (k max(0, eps - d0) f1 T u); free dofs only; p_dev == NULL: the solution of the last tsl_adjoint_step.  The reverse step itself
+ *     adds H_f p_v + [d0 < eps] mu_j k (p_v . f1 T u) n_j (H_f the friction part of H) to the free dofs of the vertex's row of pos_grad[s-1]. */
+#define TSL_MAX_COLLIDERS 8
+int tsl_set_colliders(tsl_ctx* ctx, const double* normals_host, const double* offsets_host, const double* mu_host, int32_t n, const uint8_t* vertex_mask_host);
+int tsl_set_collider_offsets(tsl_ctx* ctx, const double* offsets_host);
+int tsl_collider_count(tsl_ctx* ctx, int32_t* out_host);
+int tsl_collider_force(tsl_ctx* ctx, const double* pos_dev, const double* prev_pos_dev, double* out_host);
+int tsl_collider_grad(tsl_ctx* ctx, const double* pos_dev, const double* prev_pos_dev, const double* p_dev, double* out_host);
 
 /* BaseScene.compute_energy (BaseScene.py:427-451) at the given state, constraints as last detected. */
 int tsl_energy(tsl_ctx* ctx, const double* pos_dev, const double* prev_pos_dev, const double* vel_dev,

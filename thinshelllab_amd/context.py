@@ -253,6 +253,46 @@ class TslContext:
         check(self.L.tsl_tie_grad(self.h, _ptr(pos), _ptr(p), out.ctypes.data), "tsl_tie_grad")
         return out
 
+    # ---- half-space colliders (tsl_set_colliders; stiffness: set_param("k_collider", k))
+    def set_colliders(self, normals, offsets, mu, vertex_mask=None):
+        """n half-spaces n_j . x < o_j with friction mu_j; vertex_mask (tot_NV,) uint8, bit j: collider j acts on the vertex, None: all on all; an empty
+        list removes them.  The normals are normalised by the library and stay fixed."""
+        nr = _np(normals, np.float64).reshape(-1, 3)
+        o = _np(offsets, np.float64).reshape(-1)
+        m = _np(mu, np.float64).reshape(-1)
+        n = len(o)
+        assert nr.shape == (n, 3) and m.shape == (n,), (nr.shape, o.shape, m.shape)
+        vm = None if vertex_mask is None else _np(vertex_mask, np.uint8).reshape(-1)
+        assert vm is None or vm.shape == (self.tot_NV,), vm.shape
+        check(self.L.tsl_set_colliders(self.h, nr.ctypes.data if n else None, o.ctypes.data if n else None, m.ctypes.data if n else None, n,
+                                       None if vm is None else vm.ctypes.data), "tsl_set_colliders")
+
+    def set_collider_offsets(self, offsets):
+        o = _np(offsets, np.float64).reshape(-1)
+        assert o.shape == (self.collider_count(),), o.shape
+        if len(o):
+            check(self.L.tsl_set_collider_offsets(self.h, o.ctypes.data), "tsl_set_collider_offsets")
+
+    def collider_count(self):
+        out = C.c_int32(0)
+        check(self.L.tsl_collider_count(self.h, C.byref(out)), "tsl_collider_count")
+        return int(out.value)
+
+    def collider_force(self, pos, prev_pos):
+        """(n, 3) -sum_v g_v: the net force every plane applies to the cloth at the state (pos, prev_pos) (frozen dofs not masked)"""
+        self.refresh_stream()
+        out = np.zeros((self.collider_count(), 3))
+        check(self.L.tsl_collider_force(self.h, _ptr(pos), _ptr(prev_pos), out.ctypes.data), "tsl_collider_force")
+        return out
+
+    def collider_grad(self, pos, prev_pos, p=None):
+        """(n, 2) contribution of one reverse step to d(loss)/d(offset) and d(loss)/d(mu) of every collider at the tape state (x_s, x_{s-1}) with the
+        offsets of step s in place; p None: the solution of the last adjoint_step, else a 3 * tot_NV device vector"""
+        self.refresh_stream()
+        out = np.zeros((self.collider_count(), 2))
+        check(self.L.tsl_collider_grad(self.h, _ptr(pos), _ptr(prev_pos), _ptr(p), out.ctypes.data), "tsl_collider_grad")
+        return out
+
     # ---- engine calls
     def energy(self, pos, prev_pos, vel, ref_angle):
         self.refresh_stream()

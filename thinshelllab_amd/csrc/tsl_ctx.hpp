@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "../../include/tsl_hip.h"
+#include "collider_host.hpp"
 #include "k_body.hpp"
 #include "direct_plan.hpp"
 #include "scene_tables.hpp"   // ClothDev, ElasticDev (the per-cloth / per-body constants the kernels read) and the host tables of a scene
@@ -398,6 +399,12 @@ struct tsl_ctx {
   double k_tie = 0.0;
   DevBuf<int> ti_idx;                  // n x 4 (t0, t1, t2, v)
   DevBuf<double> ti_b, ti_w, ti_out;   // n x 3, n, n x 3 (read-outs of tsl_tie_force / tsl_tie_residuals / tsl_tie_grad)
+  // ---- half-space colliders (tsl_set_colliders, k_collider.hpp): the plane table (col.n planes; its k, eps, eh are filled in per launch), the
+  // per-vertex mask, and the partials and the result of the read-outs.  The collider kernels run while col.n > 0 and k_collider != 0
+  ColliderPlanes col{};
+  double k_collider = 0.0;
+  DevBuf<unsigned char> col_mask;      // NV
+  DevBuf<double> col_part, col_out;    // COLLIDER_SLOTS per workgroup of 256 vertices; COLLIDER_SLOTS
 
   // ---- multigrid preconditioner
   std::vector<MgCloth*> mg;

@@ -127,6 +127,49 @@ def validate_ties(tot_NV, faces_tab, vertex_ids, face_ids, bary, weights=None):
     return v.astype(np.int32), f.astype(np.int32), np.ascontiguousarray(b), w
 
 
+TSL_MAX_COLLIDERS = 8
+
+
+def validate_colliders(tot_NV, normals, offsets, mu, vertex_ids=None):
+    """The checks of tsl_set_colliders on the host, with the messages of csrc/collider_host.hpp: returns (unit normals (n, 3), offsets (n), mu (n),
+    uint8 mask (tot_NV)) or raises ValueError naming the offender -- more than TSL_MAX_COLLIDERS colliders, a zero or non-finite normal, a non-finite
+    offset, a negative or non-finite friction coefficient, a vertex id out of range.  vertex_ids None: every collider acts on every vertex; else one
+    entry per collider, None (all vertices) or a list of global vertex ids."""
+    o = np.asarray(offsets, dtype=np.float64).reshape(-1)
+    n = len(o)
+    nr = np.asarray(normals, dtype=np.float64).reshape(-1, 3) if n else np.zeros((0, 3))
+    m = np.asarray(mu, dtype=np.float64).reshape(-1)
+    if nr.shape != (n, 3) or m.shape != (n,):
+        raise ValueError(f"set_colliders: {len(nr)} normals and {m.size} friction coefficients for {n} offsets")
+    if n > TSL_MAX_COLLIDERS:
+        raise ValueError(f"set_colliders: {n} colliders: at most {TSL_MAX_COLLIDERS}")
+    unit = np.zeros((n, 3))
+    for j in range(n):
+        length = float(np.sqrt((nr[j, 0] * nr[j, 0] + nr[j, 1] * nr[j, 1]) + nr[j, 2] * nr[j, 2]))
+        if not (np.isfinite(length) and length > 0.0):
+            raise ValueError(f"set_colliders: normal ({nr[j, 0]:g}, {nr[j, 1]:g}, {nr[j, 2]:g}) of collider {j} is zero or not finite")
+        if not np.isfinite(o[j]):
+            raise ValueError(f"set_colliders: offset {o[j]:g} of collider {j} is not finite")
+        if not (m[j] >= 0.0 and np.isfinite(m[j])):
+            raise ValueError(f"set_colliders: friction coefficient {m[j]:g} of collider {j} is negative or not finite")
+        unit[j] = nr[j] / length
+    mask = np.full(tot_NV, (1 << n) - 1, np.uint8)
+    if vertex_ids is not None:
+        if len(vertex_ids) != n:
+            raise ValueError(f"set_colliders: {len(vertex_ids)} vertex lists for {n} colliders")
+        mask[:] = 0
+        for j, ids in enumerate(vertex_ids):
+            if ids is None:
+                mask |= np.uint8(1 << j)
+                continue
+            v = np.asarray(ids, dtype=np.int64).reshape(-1)
+            for vi in v.tolist():
+                if vi < 0 or vi >= tot_NV:
+                    raise ValueError(f"set_colliders: vertex {vi} of collider {j} out of range [0, {tot_NV})")
+            mask[v] |= np.uint8(1 << j)
+    return unit, o.copy(), m.copy(), mask
+
+
 class _SystemMatrix:
     """Stand-in for ``SparseMatrix`` (sparse_solver.py): the matrix itself lives inside the context."""
 
@@ -191,6 +234,13 @@ class BaseScene:
         self._tie_b = np.zeros((0, 3))
         self._tie_w = None
         self.k_tie = 0.0
+        # half-space colliders (set_colliders): unit normals, offsets, friction coefficients, the per-vertex mask and the stiffness k_collider, kept
+        # here and pushed to the engine context lazily
+        self._col_n = np.zeros((0, 3))
+        self._col_o = np.zeros(0)
+        self._col_mu = np.zeros(0)
+        self._col_mask = np.zeros(0, np.uint8)
+        self.k_collider = 0.0
         # rigid frames of the handles (set_handle_frames): frame and local point of every handle, position and unit quaternion of every frame
         self._frame_of = np.zeros(0, np.int32)
         self._frame_local = np.zeros((0, 3))
@@ -468,10 +518,16 @@ class BaseScene:
                 self._push_handles()
             if self.n_tie:
                 self._push_ties()
+            if self.n_collider:
+                self._push_colliders()
             self._dirty.clear()
         if self._dirty:
             if "ties" in self._dirty:
                 self._push_ties()
+            if "colliders" in self._dirty:
+                self._push_colliders()
+            elif "collider_offsets" in self._dirty:
+                self._ctx.set_collider_offsets(self._col_o)
             if "handles" in self._dirty:
                 self._push_handles()
             else:
@@ -624,6 +680,44 @@ class BaseScene:
     def _push_ties(self):
         self._ctx.set_ties(self._tie_v, self._tie_f, self._tie_b, self._tie_w)
         self._ctx.set_param("k_tie", self.k_tie)
+
+    # ------------------------------------------------------------------ half-space colliders (no counterpart in the reference)
+    @property
+    def n_collider(self):
+        return len(self._col_o)
+
+    def set_colliders(self, normals, offsets, mu, k, vertex_ids=None):
+        """Up to 8 half-spaces n_j . x < o_j (the solid side) with friction coefficients mu_j >= 0 and one stiffness k >= 0 in N/m: a floor, a
+        ramp, a plate that moves along its normal (set_collider_offsets before every step).  The shell is eps_contact thick, the friction is
+        regularised with eps_v dt.  vertex_ids None: every collider acts on every vertex; else one entry per collider, None or a list of global
+        vertex ids.  The normals are normalised and stay fixed; an empty list removes the colliders.  The lists are checked here, before any
+        library call."""
+        n, o, m, mask = validate_colliders(self.tot_NV, normals, offsets, mu, vertex_ids)
+        k = float(k)
+        if not (k >= 0.0 and np.isfinite(k)):
+            raise ValueError(f"set_colliders: k_collider must be finite and >= 0 (got {k:g})")
+        self._col_n, self._col_o, self._col_mu, self._col_mask, self.k_collider = n, o, m, mask, k
+        self._dirty.add("colliders")
+
+    def set_collider_offsets(self, offsets):
+        """the offsets o_j of the next step (or energy, assembly, reverse step)"""
+        o = np.asarray(offsets, dtype=np.float64).reshape(-1)
+        if o.shape != (self.n_collider,):
+            raise ValueError(f"set_collider_offsets: {o.size} offsets for {self.n_collider} colliders")
+        for j in range(len(o)):
+            if not np.isfinite(o[j]):
+                raise ValueError(f"set_collider_offsets: offset {o[j]:g} of collider {j} is not finite")
+        self._col_o = o.copy()
+        self._dirty.add("collider_offsets")
+
+    def collider_force(self):
+        """(n, 3): the net force every plane applies to the cloth at the current positions and start-of-step positions (a plate under a resting cloth
+        reads its weight along the normal)"""
+        return self._ensure_ctx().collider_force(self.pos.t, self.prev_pos.t)
+
+    def _push_colliders(self):
+        self._ctx.set_colliders(self._col_n, self._col_o, self._col_mu, self._col_mask if self.n_collider else None)
+        self._ctx.set_param("k_collider", self.k_collider)
 
     # ------------------------------------------------------------------ rigid frames for the handles (no counterpart in the reference)
     @property

@@ -30,11 +30,19 @@ def handle_tape_init(grad, sys, T):
     grad.n_tie = getattr(sys, "n_tie", 0)
     if grad.n_tie:
         grad.tie_grad = Field(torch.zeros((T, grad.n_tie), dtype=torch.float64))
+    # half-space colliders (BaseScene.set_colliders): the offsets of every step and d(loss)/d(offset, mu) per reverse step
+    grad.n_collider = getattr(sys, "n_collider", 0)
+    if grad.n_collider:
+        grad.collider_offsets = Field(torch.zeros((T, grad.n_collider), dtype=torch.float64))
+        grad.collider_grad = Field(torch.zeros((T, grad.n_collider, 2), dtype=torch.float64))
 
 
 def handle_tape_reset(grad):
     if grad.n_tie:
         grad.tie_grad.fill(0)
+    if grad.n_collider:
+        grad.collider_offsets.fill(0)
+        grad.collider_grad.fill(0)
     if grad.n_handle:
         grad.handle_targets.fill(0)
         grad.handle_grad.fill(0)
@@ -51,6 +59,8 @@ def handle_tape_record(grad, sys, step):
     if grad.n_frame:
         grad.frame_pos.t[step] = torch.as_tensor(sys._frame_pos)
         grad.frame_quat.t[step] = torch.as_tensor(sys._frame_quat)
+    if grad.n_collider:
+        grad.collider_offsets.t[step] = torch.as_tensor(sys._col_o)
 
 
 def handle_tape_push(grad, sys, step):
@@ -60,6 +70,8 @@ def handle_tape_push(grad, sys, step):
         sys.set_handle_targets(grad.handle_targets.t[step].numpy())
     if grad.n_frame:
         sys.set_frame_poses(grad.frame_pos.t[step].numpy(), grad.frame_quat.t[step].numpy())
+    if grad.n_collider:   # the offsets of step `step`: the reverse step evaluates d, d0 and the blocks with them
+        sys.set_collider_offsets(grad.collider_offsets.t[step].numpy())
 
 
 def handle_tape_pull(grad, ctx, step):
@@ -70,6 +82,8 @@ def handle_tape_pull(grad, ctx, step):
         grad.frame_grad.t[step] += torch.as_tensor(ctx.frame_grad())
     if grad.n_tie:   # tie_grad[step] += d(loss)/d(tie weights) of the reverse step just taken, at the tape state x_step
         grad.tie_grad.t[step] += torch.as_tensor(ctx.tie_grad(grad.pos_buffer.t[step]))
+    if grad.n_collider:   # collider_grad[step] += d(loss)/d(offsets of step `step`, mu) of the reverse step just taken, at the tape state (x_step, x_{step-1})
+        grad.collider_grad.t[step] += torch.as_tensor(ctx.collider_grad(grad.pos_buffer.t[step], grad.pos_buffer.t[step - 1]))
 
 
 class Grad:
