@@ -1,0 +1,917 @@
+"""Restatement of the vertex-triangle contact constraint (csrc/k_contact.hpp: k_contact_pair, k_contact_energy, k_contact_assemble_coop, k_contact_mask,
+k_contact_backprop, k_contact_friction_grad; k_contact_zfrozen_gather of csrc/k_adjoint.hpp; k_pg_contact of csrc/k_param.hpp) for
+tests/test_contact_numpy.py and tests/test_gpu_contact_elements.py, written from the reference's formulas (engine/BaseScene.py: contact_pair_analysis,
+f0 / f1 / f2, contact_energy, contact_energy_backprop; task_scene/Scene_sliding.py: contact_energy_backprop_friction; engine/linalg.py: the two
+projections; engine/contact_diff.py), not from the kernels and not from oracle/tslo_contact.cpp.  The pattern is that of tests/tet_numpy.py and
+tests/cloth_numpy.py, whose backends and helpers it uses: every function takes a backend `xp`, MP (mpmath at 50 digits, the reference proper) or F64
+(float64 scalars, the same formulas in the same plain order: it only measures what double precision delivers, see tet_numpy.bound).  Nothing here
+calls the GPU except probe_context().  Detection (broad phase, closest triangle) is not restated: it delivers the slots, the slots are data.
+
+Conventions restated:
+- a slot is (idx[4], w[3], k, mu, dx0, T, n): idx = (triangle vertices, query vertex).  Where proj_dir == 0 the normal is negated, vertices 1 and 2
+  and their weights swap (the barycentre of the previous step, dx0, is formed with the unswapped ones: the same sum in another order);
+- gap = (x_q - x_c) . n with n = unit((x_1 - x_0) x (x_2 - x_0)) of the unswapped vertices, negated with proj_dir == 0; active: gap < eps;
+- k = -mu k_contact (gap - eps); dx0 = prev_q - prev_c; t1 = (n.x, n.z, -n.y) where |n.x| < 0.5, else (n.y, -n.x, n.z); t2 = n x t1; t1 = n x t2.
+  The two rows of T are orthogonal to n and to each other and of EQUAL length sqrt(1 - (n . t1)^2) < 1 (n . t1 = n.x^2 or n.z^2): T is not
+  orthonormal, and the friction radius r = |T dx| is that much shorter than the tangential slip;
+- normal energy at pos, in the relative coordinates q = (a, b, p) = (x_1 - x_0, x_2 - x_0, x_3 - x_0): d = D / C, D = p . (a x b), C = |a x b|; where
+  d < eps: k_contact / 2 (d - eps)^2, gradient k_contact (d - eps) grad d, block k_contact grad d grad d^T + k_contact (d - eps) hess d by the
+  quotient rule; vertex 0 takes minus the sums.  spd: the 9 x 9 block is eigen-clamped in the relative coordinates, before the map to 12 x 12;
+- friction at pos: u = T (x_3 - sum w_i x_i - dx0), r = |u|, energy k f0(r), gradient w1_i k f1(r) T^T u with w1 = (-w, 1), block
+  w1_i w1_j k T^T (f1 I + [r > 1e-9] f2 u u^T / r) T; spd: the 2 x 2 core is eigen-clamped first.  f0, f1, f2 switch at r = eps_v dt;
+- frozen rule of k_contact_mask: rows and columns of frozen dofs of a slot's block are zero (the diagonal m / dt^2 belongs to the static matrix);
+- reverse step (friction-lag adjoint) for a vector z: entry (i2, j2) = sum_{i1 j1} z[i1 j1] wp_i1 g1_j1 / pressure * wp_i2 n_j2 k_contact +
+  sum z[i1 j1] w1_i1 w1_i2 h1[j1][j2], wp = (w, -1), g1 = k f1 T^T u, pressure = k / mu, h1 the unprojected friction block;
+- tmp_z_frozen, contact part: entry (v, c) frozen = -sum over the slots of v and the free dofs (u, j) of H[(u, j)][(v, c)] z[u, j], H unprojected;
+- friction_grad: sum over the slots of kind 2 and the free dofs of z wp_i g1_j / mu_cloth_cloth;
+- per-key sums for a vector p: k_contact: -(p . normal gradient per unit k_contact + p . friction gradient / k_contact); mu_cloth_elastic /
+  mu_cloth_cloth: -(p . friction gradient) / mu_live on the slots of kind 1 / 2; free dofs only.
+
+Every decision (active d < eps, r > eps_v dt, r > 1e-9, |n.x| < 0.5, gap < eps at the detection) is recorded with its normalised distance from the
+threshold; decisions_safe() asserts that each is at least SAFE away on the same side in mp, in float64 and in every rotated or jittered copy."""
+import functools
+
+import mpmath as mp
+import numpy as np
+
+from tet_numpy import F64, MP, R1, R2, U, bound, fro, rest_tables  # noqa: F401
+from cloth_numpy import _cross, _dot, _norm, _scal, _sub, _z, diff, jitters, ratio, rotations, split  # noqa: F401
+
+SAFE = 5e-7
+R_GUARD = 1e-9
+MASS, DT = 2.0 ** -10, 2.0 ** -8           # m / dt^2 = 64 exactly
+MDT2 = MASS / DT ** 2
+K_CONTACT, EPS, EPS_V, GRID_H = 1000.0, 1e-3, 0.01, 0.003
+EH = EPS_V * DT
+MU_FIXED, MU_CE, CE_FACTOR, MU_CC = 0.3, 0.4, 2.5, 0.7
+KEYS = ("k_contact", "mu_cloth_elastic", "mu_cloth_cloth")
+
+
+class Scalars:
+    k_contact, eps, eh, mu_ce, mu_cc = K_CONTACT, EPS, EH, MU_CE, MU_CC
+
+
+SC = Scalars()
+
+
+def _V(xp, a):
+    return [xp.num(v) for v in np.asarray(a, dtype=object).ravel()]
+
+
+def _P(xp, X):
+    X = np.asarray(X, dtype=object).reshape(-1, 3)
+    return [[xp.num(v) for v in r] for r in X]
+
+
+# ------------------------------------------------------------------------------------------------ f0, f1, f2
+def f0(xp, x, eh):
+    return x if x > eh else -x / (3 * eh ** 2) * x * x + x / eh * x + eh / 3
+
+
+def f1(xp, x, eh):
+    return 1 / x if x > eh else -x / eh ** 2 + 2 / eh
+
+
+def f2(xp, x, eh):
+    return -1 / x ** 2 if x > eh else -1 / eh ** 2
+
+
+# ------------------------------------------------------------------------------------------------ records of a slot
+def slot_records(xp, Xd, Pd, w, pdir, mu, sc=SC, dec=None):
+    """Xd, Pd: (4, 3) positions and previous positions of (the triangle as the projection names it, the query vertex); w: the projection's weights.
+    Returns dict(order, w, gap, active, k, mu, dx0, n, T): order = the slot's vertices as positions 0..3 of the input"""
+    X, P, w = _P(xp, Xd), _P(xp, Pd), _V(xp, w)
+    xc = [X[0][j] * w[0] + X[1][j] * w[1] + X[2][j] * w[2] for j in range(3)]
+    pc = [P[0][j] * w[0] + P[1][j] * w[1] + P[2][j] * w[2] for j in range(3)]
+    cr = _cross(_sub(X[1], X[0]), _sub(X[2], X[0]))
+    nn = _norm(xp, cr)
+    n = [cr[j] / nn for j in range(3)]
+    order = [0, 1, 2, 3]
+    if pdir == 0:
+        n = [-v for v in n]
+        order = [0, 2, 1, 3]
+        w = [w[0], w[2], w[1]]
+    gap = _dot(_sub(X[3], xc), n)
+    eps = xp.num(sc.eps)
+    mu = xp.num(mu)
+    if dec is not None:
+        dec.append(("gap", gap / eps - 1))
+        dec.append(("nx", abs(n[0]) / xp.num(0.5) - 1))
+    t1 = [n[0], n[2], -n[1]] if abs(n[0]) < xp.num(0.5) else [n[1], -n[0], n[2]]
+    t2 = _cross(n, t1)
+    t1 = _cross(n, t2)
+    return dict(order=order, w=w, gap=gap, active=bool(gap < eps), k=-mu * (xp.num(sc.k_contact) * (gap - eps)), mu=mu, dx0=_sub(P[3], pc), n=n,
+                T=t1 + t2)
+
+
+# ------------------------------------------------------------------------------------------------ evaluation of a slot
+def _unit(j, xp):
+    return [xp.num(1 if a == j else 0) for a in range(3)]
+
+
+def normal_part(xp, X, sc=SC, dec=None):
+    """(d, active, energy, g9, H9) of the normal part in the relative coordinates (a, b, p); g9, H9 zero where the slot is off"""
+    a, b, p = _sub(X[1], X[0]), _sub(X[2], X[0]), _sub(X[3], X[0])
+    cr = _cross(a, b)
+    C, D = _norm(xp, cr), _dot(cr, p)
+    d, eps, kc = D / C, xp.num(sc.eps), xp.num(sc.k_contact)
+    if dec is not None:
+        dec.append(("active", d / eps - 1))
+    zero = xp.num(0)
+    if not d < eps:
+        return d, False, zero, [zero] * 9, _z(xp, 9, 9)
+    nh = [v / C for v in cr]
+    gD = _cross(b, p) + _cross(p, a) + cr
+    gC = _cross(b, nh) + _cross(nh, a) + [zero] * 3
+    E = [_unit(j, xp) for j in range(3)]
+    ejb, aej = [_cross(E[j], b) for j in range(3)], [_cross(a, E[j]) for j in range(3)]
+    n_ejb, n_aej = [_dot(nh, v) for v in ejb], [_dot(nh, v) for v in aej]
+    third = {(0, 1): p, (1, 2): a, (2, 0): b}
+    H9 = _z(xp, 9, 9)
+    pe = kc * (d - eps)
+    G = [gD[j] / C - D * gC[j] / C ** 2 for j in range(9)]
+    for j in range(9):
+        jb, ja = divmod(j, 3)
+        for k in range(9):
+            kb, ka = divmod(k, 3)
+            ejk = _cross(E[ja], E[ka])
+            HC = HD = zero
+            if jb == 0 and kb == 0:
+                HC = (_dot(ejb[ja], ejb[ka]) - n_ejb[ja] * n_ejb[ka]) / C
+            elif jb == 1 and kb == 1:
+                HC = (_dot(aej[ja], aej[ka]) - n_aej[ja] * n_aej[ka]) / C
+            elif jb == 0 and kb == 1:   # d / d b_k of nh . (e_j x b): the cross product's own derivative + that of nh
+                cross_term = _dot(nh, ejk)
+                HC = (_dot(ejb[ja], aej[ka]) - n_ejb[ja] * n_aej[ka]) / C + cross_term
+            elif jb == 1 and kb == 0:
+                cross_term = _dot(nh, _cross(E[ka], E[ja]))
+                HC = (_dot(ejb[ka], aej[ja]) - n_ejb[ka] * n_aej[ja]) / C + cross_term
+            if (jb, kb) in third:
+                HD = _dot(ejk, third[(jb, kb)])
+            elif (kb, jb) in third:
+                HD = -_dot(ejk, third[(kb, jb)])
+            Hd = HD / C - gD[j] * gC[k] / C ** 2 - gD[k] * gC[j] / C ** 2 - D * HC / C ** 2 + 2 * D * gC[j] * gC[k] / C ** 3
+            H9[j][k] = kc * G[j] * G[k] + pe * Hd
+    return d, True, kc / 2 * (d - eps) ** 2, [G[j] * pe for j in range(9)], H9
+
+
+def clamp(xp, K):
+    """symmetrise, eigen-decompose, negative eigenvalues to zero, rebuild (any size)"""
+    n = len(K)
+    w, V = xp.eigh([[(K[i][j] + K[j][i]) / 2 for j in range(n)] for i in range(n)])
+    out = _z(xp, n, n)
+    for i in range(n):
+        for j in range(n):
+            s = xp.num(0)
+            for e in range(n):
+                if w[e] > 0:
+                    s = s + w[e] * V[i][e] * V[j][e]
+            out[i][j] = s
+    return out
+
+
+def to12(xp, g9, H9):
+    """relative coordinates -> vertices: vertex 0 takes minus the sums"""
+    g = [-(g9[j] + g9[3 + j] + g9[6 + j]) for j in range(3)] + list(g9)
+    H = _z(xp, 12, 12)
+    for r in range(9):
+        for c in range(9):
+            H[3 + r][3 + c] = H9[r][c]
+    for r in range(9):
+        for j in range(3):
+            H[3 + r][j] = -(H9[r][j] + H9[r][3 + j] + H9[r][6 + j])
+            H[j][3 + r] = -(H9[j][r] + H9[3 + j][r] + H9[6 + j][r])
+    for j in range(3):
+        for j2 in range(3):
+            s = xp.num(0)
+            for a in range(3):
+                for b in range(3):
+                    s = s + H9[3 * a + j][3 * b + j2]
+            H[j][j2] = s
+    return g, H
+
+
+def friction_part(xp, X, rec, sc=SC, spd=0, dec=None):
+    """dict(r, u, f1, e, g1 (3: k f1 T^T u), h1 (3 x 3: k T^T core T), w1): the friction term of a slot with its records as data"""
+    w, T, dx0, k = _V(xp, rec["w"]), _V(xp, rec["T"]), _V(xp, rec["dx0"]), xp.num(rec["k"])
+    eh = xp.num(sc.eh)
+    xc = [X[0][j] * w[0] + X[1][j] * w[1] + X[2][j] * w[2] for j in range(3)]
+    dx = [X[3][j] - xc[j] - dx0[j] for j in range(3)]
+    u = [T[0] * dx[0] + T[1] * dx[1] + T[2] * dx[2], T[3] * dx[0] + T[4] * dx[1] + T[5] * dx[2]]
+    r = xp.sqrt(u[0] * u[0] + u[1] * u[1])
+    if dec is not None:
+        dec.append(("r_eh", r / eh - 1))
+        dec.append(("r_guard", r / xp.num(R_GUARD) - 1))
+    v1, v2 = f1(xp, r, eh), f2(xp, r, eh)
+    core = [[v1, xp.num(0)], [xp.num(0), v1]]
+    if r > xp.num(R_GUARD):
+        core = [[core[i][j] + v2 * (u[i] / r) * u[j] for j in range(2)] for i in range(2)]
+    if spd:
+        core = clamp(xp, core)
+    g1 = [k * v1 * (u[0] * T[j] + u[1] * T[3 + j]) for j in range(3)]
+    h1 = [[k * (T[a] * (core[0][0] * T[b] + core[0][1] * T[3 + b]) + T[3 + a] * (core[1][0] * T[b] + core[1][1] * T[3 + b])) for b in range(3)]
+          for a in range(3)]
+    return dict(r=r, u=u, f1=v1, e=k * f0(xp, r, eh), g1=g1, h1=h1, w1=[-w[0], -w[1], -w[2], xp.num(1)], tu=[v1 * (u[0] * T[j] + u[1] * T[3 + j]) for j in range(3)])
+
+
+def slot_eval(xp, X, rec, sc=SC, spd=0, dec=None):
+    """energy, 12 gradient entries, 12 x 12 block (spd: both parts clamped before the map to 12 x 12) of one slot at the positions X (4, 3) in the slot's
+    order, and gn1: the normal gradient per unit k_contact"""
+    X = _P(xp, X)
+    d, active, en, g9, H9 = normal_part(xp, X, sc, dec)
+    if spd and active:
+        H9 = clamp(xp, H9)
+    g, H = to12(xp, g9, H9)
+    fr = friction_part(xp, X, rec, sc, spd, dec)
+    for i1 in range(4):
+        for j1 in range(3):
+            g[3 * i1 + j1] = g[3 * i1 + j1] + fr["w1"][i1] * fr["g1"][j1]
+            for i2 in range(4):
+                for j2 in range(3):
+                    H[3 * i1 + j1][3 * i2 + j2] = H[3 * i1 + j1][3 * i2 + j2] + fr["w1"][i1] * fr["w1"][i2] * fr["h1"][j1][j2]
+    kc = xp.num(sc.k_contact)
+    gn1 = [v / kc for v in to12(xp, g9, _z(xp, 9, 9))[0]]
+    gf1 = [fr["w1"][i] * fr["tu"][j] for i in range(4) for j in range(3)]      # friction gradient per unit k
+    return dict(E=en + fr["e"], g=g, H=H, gn1=gn1, gf1=gf1, d=d, r=fr["r"])
+
+
+def slot_reverse(xp, X, rec, z, sc=SC):
+    """the 12 entries of the friction-lag adjoint of one slot for the 12 values z of its vertices, and sum_i z_i wp_i g1 (for friction_grad, per dof)"""
+    X = _P(xp, X)
+    fr = friction_part(xp, X, rec, sc, 0)
+    w, n, z = _V(xp, rec["w"]), _V(xp, rec["n"]), _V(xp, z)
+    wp = [w[0], w[1], w[2], xp.num(-1)]
+    pressure = xp.num(rec["k"]) / xp.num(rec["mu"])
+    s = xp.num(0)
+    for i1 in range(4):
+        for j1 in range(3):
+            s = s + z[3 * i1 + j1] * (wp[i1] * fr["g1"][j1] / pressure)
+    acc = [s * wp[i2] * n[j2] * xp.num(sc.k_contact) for i2 in range(4) for j2 in range(3)]
+    for i1 in range(4):
+        for i2 in range(4):
+            for j1 in range(3):
+                for j2 in range(3):
+                    acc[3 * i2 + j2] = acc[3 * i2 + j2] + z[3 * i1 + j1] * fr["w1"][i1] * fr["w1"][i2] * fr["h1"][j1][j2]
+    fg = [wp[i1] * fr["g1"][j1] for i1 in range(4) for j1 in range(3)]   # times z / mu_cloth_cloth on the free dofs: friction_grad
+    return dict(acc=acc, fg=fg)
+
+
+# ------------------------------------------------------------------------------------------------ probe scenes
+class Probe:
+    """one target triangle and one query vertex over its interior: tri (3, 3), q (3,), their previous positions, winding / side -> proj_dir, kind"""
+    def __init__(self, tri, q, ptri, pq, pdir, kind, active, tag):
+        self.tri, self.q, self.ptri, self.pq, self.pdir, self.kind, self.active, self.tag = tri, q, ptri, pq, pdir, kind, active, tag
+
+
+def _frame(nx, phi):
+    """unit vector with first component nx, and two unit vectors orthogonal to it"""
+    s = np.sqrt(1 - nx * nx)
+    n = np.array([nx, s * np.cos(phi), s * np.sin(phi)])
+    a = np.cross(n, [0.3, -0.5, 0.8]); a /= np.linalg.norm(a)
+    return n, a, np.cross(n, a)
+
+
+NX = (0.5 - 1e-6, 0.5 + 1e-6, 0.1, -0.9)
+BARY = ((0.3, 0.45, 0.25), (0.2, 0.3, 0.5), (0.4, 0.25, 0.35))
+
+
+def make_probe(center, L, sliver, pdir, nx, kind, gap=0.5, bary=0, phi=0.7, seed=0):
+    """the query vertex at gap * eps from the triangle, on the side and with the winding that give proj_dir = pdir and a slot normal with n.x = nx.  The
+    previous positions: the triangle moved rigidly, the query vertex by another vector (0.2 eps_v dt sideways, a little along n): dx0 != 0"""
+    n, e1, e2 = _frame(nx, phi + 0.37 * seed)
+    uv = np.array([[0, 0], [1, 0], [0.5, 1e-3 if sliver else np.sqrt(0.75)]]) * L
+    b = np.array(BARY[bary % 3])
+    uv = uv - b @ uv                       # the projection point at the centre of the probe's cell
+    tri = center + uv[:, :1] * e1 + uv[:, 1:] * e2
+    if pdir == 0:                          # winding normal -n: the query vertex lies on its negative side
+        tri = tri[[0, 2, 1]]
+    q = center + gap * EPS * n
+    rng = np.random.default_rng(1000 + seed)
+    vt = 1e-5 * rng.normal(size=3)
+    vq = vt + EH * (0.2 * np.cos(seed) * e1 + 0.2 * np.sin(seed) * e2) + 1e-6 * n
+    return Probe(tri, q, tri - vt, q - vq, pdir, kind, gap < 1.0, "L%g %s pdir%d nx%g kind%d" % (L, "sliver" if sliver else "equilateral", pdir, nx, kind))
+
+
+class Scene:
+    """probes on a lattice of cells several grid_h wide; vertices: every triangle's three, then the query vertices (a pair per kind: a contiguous range of
+    query vertices, so the probes are ordered by kind); carriers: one tetrahedron (triangle, query vertex) per probe with mu = lam = 0"""
+    def __init__(self, probes, shared_triangle=False, mass=MASS):
+        self.mass, self.mdt2 = mass, mass / DT ** 2
+        probes = sorted(probes, key=lambda p: p.kind)
+        self.probes, self.P = probes, len(probes)
+        tris = [probes[0]] if shared_triangle else probes
+        self.nt = len(tris)
+        self.x = np.concatenate([p.tri for p in tris] + [p.q[None] for p in probes])
+        self.prev = np.concatenate([p.ptri for p in tris] + [p.pq[None] for p in probes])
+        self.nv = len(self.x)
+        self.faces = np.arange(3 * self.nt, dtype=np.int32).reshape(-1, 3)
+        self.qv = 3 * self.nt + np.arange(self.P)
+        self.tri_of = np.zeros(self.P, int) if shared_triangle else np.arange(self.P)
+        self.bodies = [(0, 3 * self.nt, 0, self.nt), (3 * self.nt, self.nv, self.nt, self.nt)]
+        self.pairs = []
+        for kind, mu in ((0, (MU_FIXED,)), (1, (None, CE_FACTOR)), (2, ("cloth_cloth",))):
+            ids = [i for i, p in enumerate(probes) if p.kind == kind]
+            if ids:
+                self.pairs.append((0, int(self.qv[ids[0]]), int(self.qv[ids[-1]]) + 1) + mu)
+        self.mu_of_kind = {0: MU_FIXED, 1: MU_CE * CE_FACTOR, 2: MU_CC}
+        self.tets = np.array([list(self.faces[self.tri_of[i]]) + [self.qv[i]] for i in range(self.P)], np.int32)
+        self.active = [i for i, p in enumerate(probes) if p.active]
+        for i in range(self.P):      # strictly interior projections: proj_flag = 1 needs no border table
+            assert barycentric(self.x[list(self.faces[self.tri_of[i]]) + [self.qv[i]]]).min() > 0.05, i
+
+    def slot_verts(self, i):
+        """global vertices of probe i's slot as the construction has them: (triangle with the proj_dir swap, query vertex)"""
+        f = self.faces[self.tri_of[i]]
+        return [f[0], f[2], f[1], self.qv[i]] if self.probes[i].pdir == 0 else [f[0], f[1], f[2], self.qv[i]]
+
+    def idx(self):
+        return np.array([self.slot_verts(i) for i in self.active], np.int32).reshape(-1, 4)
+
+    def kinds(self):
+        return np.array([self.probes[i].kind for i in self.active])
+
+
+def lattice(n, pitch=0.02):
+    """n cell centres, `pitch` apart (6 2/3 grid_h: the 27 cells about a query vertex hold its own triangle only), inside the broad phase's box"""
+    m = int(np.ceil(np.sqrt(n)))
+    return [np.array([(i % m - (m - 1) / 2) * pitch, (i // m - (m - 1) / 2) * pitch, 0.013 * ((i % 3) - 1)]) for i in range(n)]
+
+
+LS = (1.0 / 150, 1e-4)
+
+
+def geometry_probes(n=16, inactive=1):
+    """the probes of the assembly tests: edge 1 / 150 and 1e-4, equilateral and sliver, proj_dir 1 and 0 (16 combinations with the four n.x), the three
+    kinds in turn, + `inactive` probes at 1.5 eps, which the detection must leave out"""
+    cs = lattice(n + inactive)
+    out = []
+    for i in range(n):
+        out.append(make_probe(cs[i], LS[i % 2], (i // 2) % 2 == 1, (i // 4) % 2, NX[(i + i // 8) % 4], i % 3, bary=i, seed=i))
+    for j in range(inactive):
+        out.append(make_probe(cs[n + j], LS[0], False, 1, 0.1, j % 3, gap=1.5, seed=50 + j))
+    return out
+
+
+def launch_probes(nc):
+    """nc active probes (the launch-edge contexts): the geometries of geometry_probes in turn"""
+    cs = lattice(nc)
+    return [make_probe(cs[i], LS[i % 2], (i // 2) % 2 == 1, (i // 4) % 2, NX[(i + i // 8) % 4], i % 3, gap=0.3 + 0.05 * (i % 9), bary=i, seed=i) for i in range(nc)]
+
+
+MASS_REVERSE = 2.0 ** -6     # m / dt^2 = 1024
+MASS_REVERSE_ALL = 2.0 ** 10   # m / dt^2 = 2^26 = 6.7e7: above the -2e7 that a penetrated sliver of 1e-4 m puts into the unprojected operator ("rw" scenes: the
+#                                probes of launch_probes, every edge length and shape); the read-back of p stays exact
+
+
+def reverse_probes(nc):
+    """nc active probes of the reverse-step tests: equilateral triangles of 1 / 150 m, proj_dir 1 and 0, the four n.x, the three kinds.  The vector p of a
+    reverse step comes out of the engine's own solve of the unprojected operator; with m / dt^2 = 1024 that operator stays positive definite through the
+    penetrated slots of these probes (k_contact (d - eps) times the curvature of d, 1 / edge, is a few hundred)"""
+    cs = lattice(nc)
+    return [make_probe(cs[i], LS[0], False, (i // 4) % 2, NX[(i + i // 8) % 4], i % 3, gap=0.3 + 0.05 * (i % 9), bary=i, seed=i) for i in range(nc)]
+
+
+def crowd_probes(n=70):
+    """n query vertices over ONE triangle of 1 / 150 m: its three vertices have constraint rows of n entries"""
+    c, L = np.zeros(3), LS[0]
+    base = make_probe(c, L, False, 1, 0.1, 0, seed=3)
+    out = []
+    for i in range(n):
+        b = np.array([0.1 + 0.5 * ((i * 7) % n) / n, 0.1 + 0.05 * (i % 5), 0.0]); b[2] = 1 - b[0] - b[1]
+        nrm = np.cross(base.tri[1] - base.tri[0], base.tri[2] - base.tri[0]); nrm /= np.linalg.norm(nrm)
+        q = b @ base.tri + (0.3 + 0.005 * i) * EPS * nrm
+        vq = EH * 0.1 * (base.tri[1] - base.tri[0]) / L * (1 + i % 4)
+        out.append(Probe(base.tri, q, base.ptri, q - vq, 1, i % 3, True, "crowd %d" % i))
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def scene(name):
+    if name == "geometry":
+        return Scene(geometry_probes())
+    if name == "crowd":
+        return Scene(crowd_probes(), shared_triangle=True)
+    if name.startswith("rv"):
+        return Scene(reverse_probes(int(name[2:])), mass=MASS_REVERSE)
+    if name.startswith("rw"):
+        return Scene(launch_probes(int(name[2:])), mass=MASS_REVERSE_ALL)
+    assert name.startswith("nc")
+    return Scene(launch_probes(int(name[2:])))
+
+
+def probe_context(sc, frozen=None, max_n_constraints=None):
+    """engine context of a Scene: tetrahedra with mu = lam = 0 (alpha 1) as carriers, gravity 0, one target body (all triangles) and one body of query
+    vertices, a pair per kind"""
+    from thinshelllab_amd.context import TslContext
+    BW = [rest_tables(sc.x[t]) for t in sc.tets]
+    el = dict(kind=0, n_verts=sc.nv, n_cells=len(sc.tets), v_offset=0, mu=0.0, lam=0.0, alpha=1.0, tets=sc.tets,
+              B=np.array([b for b, _ in BW]).reshape(-1, 9), W=np.array([w for _, w in BW]))
+    ctx = TslContext(tot_NV=sc.nv, dt=DT, mass=np.full(sc.nv, sc.mass), gravity=np.zeros((sc.nv, 3)),
+                     frozen=np.zeros(3 * sc.nv, np.int32) if frozen is None else frozen, elastics=[el], faces=sc.faces, bodies=sc.bodies, pairs=sc.pairs,
+                     k_contact=K_CONTACT, eps_contact=EPS, eps_v=EPS_V, grid_h=GRID_H,
+                     max_n_constraints=max(sc.P, 1) if max_n_constraints is None else max_n_constraints)
+    ctx.set_param("mu_cloth_elastic", MU_CE)
+    ctx.set_param("mu_cloth_cloth", MU_CC)
+    return ctx
+
+
+# ------------------------------------------------------------------------------------------------ records of a scene
+def scene_records(xp, sc, proj=None, dec=None, x=None, prev=None):
+    """records of the active probes in slot order.  proj = (pidx (P, 3), pw (P, 3), pdir (P,)) per probe as the projection delivered them; None: the
+    construction's own (weights from the construction's barycentric solve in float64)"""
+    x, prev = sc.x if x is None else x, sc.prev if prev is None else prev
+    out = []
+    for i, p in enumerate(sc.probes):
+        f = sc.faces[sc.tri_of[i]] if proj is None else proj[0][i]
+        vs = list(f) + [sc.qv[i]]
+        w = barycentric(x[vs]) if proj is None else proj[1][i]
+        pdir = p.pdir if proj is None else proj[2][i]
+        d = [] if dec is not None else None
+        rec = slot_records(xp, x[vs], prev[vs], w, pdir, sc.mu_of_kind[p.kind], SC, d)
+        if dec is not None:
+            dec.append((i, d))
+        if rec["active"]:
+            rec["idx"] = [vs[o] for o in rec["order"]]
+            rec["kind"], rec["probe"] = p.kind, i
+            out.append(rec)
+    return out
+
+
+def barycentric(X4):
+    """weights of the foot of X4[3] in the triangle X4[:3] (float64, for the construction only)"""
+    a, b, p = X4[1] - X4[0], X4[2] - X4[0], X4[3] - X4[0]
+    n = np.cross(a, b)
+    S = n @ n
+    w1, w2 = np.cross(p, b) @ n / S, np.cross(a, p) @ n / S
+    return np.array([1 - w1 - w2, w1, w2])
+
+
+def construction_proj(sc):
+    """(pidx, pw, pdir) per probe as the construction has them (what proj_export() delivers for a probe scene, up to the rounding of the weights)"""
+    pidx = np.array([sc.faces[sc.tri_of[i]] for i in range(sc.P)], np.int32)
+    pw = np.array([barycentric(sc.x[list(pidx[i]) + [sc.qv[i]]]) for i in range(sc.P)])
+    return pidx, pw, np.array([p.pdir for p in sc.probes], np.int32)
+
+
+def check_records(sc, cons, proj, R):
+    """the exported records against the restatement fed with the projection (pidx, pw, pdir per probe) and the detection state: idx and mu exact (the kind is not exported: it shows through mu, a value per kind, and through the per-key sums), w
+    bit-equal to proj_w after the swap, k, dx0, T, n within the bound (e64 over the state and eight one-ulp jitters of pos and prev; a rotation would change
+    the branch of T), the rows of T orthogonal to n and to each other within 8 u"""
+    with mp.workdps(50):
+        rm = scene_records(MP, sc, proj)
+    with np.errstate(all="ignore"):
+        copies = [scene_records(F64, sc, proj)] + [scene_records(F64, sc, proj, x=xj, prev=pj) for xj, pj in zip(jitters(sc.x, seed=1), jitters(sc.prev, seed=2))]
+    assert len(cons["k"]) == len(rm) == len(sc.active), (len(cons["k"]), len(rm))
+    assert np.array_equal(cons["idx"], sc.idx()) and np.array_equal(cons["idx"], np.array([r["idx"] for r in rm]))
+    for s, r in enumerate(rm):
+        i = r["probe"]
+        w = np.asarray(proj[1][i], float)
+        assert np.array_equal(cons["w"][s], w[[0, 2, 1]] if proj[2][i] == 0 else w), (s, "w is not proj_w after the swap")
+        assert cons["mu"][s] == sc.mu_of_kind[sc.probes[i].kind], s
+        for q in ("k", "dx0", "n", "T"):
+            hl = split(np.array(r[q], dtype=object))
+            e64 = max(float(_fn(diff(np.array([float(v) for v in np.ravel(c[s][q])]), (hl[0].ravel(), hl[1].ravel())))) for c in copies)
+            ratio(R, "record " + q, float(_fn(diff(np.ravel(cons[q][s]), (hl[0].ravel(), hl[1].ravel())))), float(_bnd(e64, _fn(hl[0]))))
+        n, t1, t2 = cons["n"][s], cons["T"][s][:3], cons["T"][s][3:]
+        assert max(abs(n @ t1), abs(n @ t2), abs(t1 @ t2)) <= 8 * U, (s, "T not orthogonal")
+
+
+def records_as_data(recs):
+    """float records (what ctx.constraints() returns) of restated ones"""
+    f = lambda v: np.array([float(t) for t in v])
+    return dict(idx=np.array([r["idx"] for r in recs], np.int32).reshape(-1, 4), w=np.array([f(r["w"]) for r in recs]).reshape(-1, 3),
+                k=np.array([float(r["k"]) for r in recs]), mu=np.array([float(r["mu"]) for r in recs]),
+                dx0=np.array([f(r["dx0"]) for r in recs]).reshape(-1, 3), T=np.array([f(r["T"]) for r in recs]).reshape(-1, 6),
+                n=np.array([f(r["n"]) for r in recs]).reshape(-1, 3))
+
+
+def slot_rec(cons, s):
+    return {q: cons[q][s] for q in ("w", "k", "mu", "dx0", "T", "n")}
+
+
+# ------------------------------------------------------------------------------------------------ evaluation states
+def _geom(sc, recs_f):
+    """per active probe: (slot vertices, n, T rows, s2 = |t|^2, base position of the query vertex with u = 0 up to rounding, edge length L, smallest altitude alt)"""
+    out = []
+    for r in recs_f:
+        i = r["probe"]
+        vs = r["idx"]
+        n, T = np.array([float(v) for v in r["n"]]), np.array([float(v) for v in r["T"]]).reshape(2, 3)
+        w, dx0 = np.array([float(v) for v in r["w"]]), np.array([float(v) for v in r["dx0"]])
+        base = w @ sc.x[vs[:3]] + dx0
+        out.append(dict(vs=vs, n=n, T=T, s2=float(T[0] @ T[0]), base=base, L=np.linalg.norm(sc.x[vs[1]] - sc.x[vs[0]]), i=i,
+                        alt=np.linalg.norm(np.cross(sc.x[vs[1]] - sc.x[vs[0]], sc.x[vs[2]] - sc.x[vs[0]])) / max(np.linalg.norm(sc.x[vs[a]] - sc.x[vs[b]]) for a, b in ((0, 1), (1, 2), (2, 0)))))
+    return out
+
+
+def _dist(sc, x, g):
+    a, b, p = x[g["vs"][1]] - x[g["vs"][0]], x[g["vs"][2]] - x[g["vs"][0]], x[g["vs"][3]] - x[g["vs"][0]]
+    c = np.cross(a, b)
+    return c @ p / np.linalg.norm(c)
+
+
+def _set_d(sc, x, geo, dfac):
+    for g in geo:
+        x[g["vs"][3]] = x[g["vs"][3]] + (dfac * EPS - _dist(sc, x, g)) * g["n"]
+    return x
+
+
+def _slip(sc, geo, rfac, direction, dfac=0.5, r_abs=None):
+    """the query vertex where u = r (cos, sin)(direction) exactly up to the rounding of the positions: r = rfac eps_v dt (or r_abs), d = dfac eps"""
+    x = sc.x.copy()
+    for k, g in enumerate(geo):
+        r = EH * rfac if r_abs is None else r_abs
+        ang = {"t1": 0.0, "t2": np.pi / 2, "oblique": 0.4 + 0.9 * k}[direction]
+        x[g["vs"][3]] = g["base"] + (r * np.cos(ang) * g["T"][0] + r * np.sin(ang) * g["T"][1]) / g["s2"]
+    return _set_d(sc, x, geo, dfac)
+
+
+def _shear(sc, geo):
+    """the target triangle a sliver at the evaluation (vertex 2 of the slot brought to 1e-3 of an edge from the line 0-1), the records unchanged"""
+    x = sc.x.copy()
+    for g in geo:
+        v0, v1, v2 = (x[g["vs"][j]] for j in range(3))
+        e = (v1 - v0) / np.linalg.norm(v1 - v0)
+        perp = (v2 - v0) - ((v2 - v0) @ e) * e
+        x[g["vs"][2]] = v0 + 0.5 * (v1 - v0) + 1e-3 * np.linalg.norm(v1 - v0) * perp / np.linalg.norm(perp)
+    return x
+
+
+def _bump(sc, geo):
+    x = sc.x.copy()
+    rng = np.random.default_rng(11)
+    for g in geo:
+        for v in g["vs"]:
+            x[v] = x[v] + 0.05 * g["L"] * rng.uniform(-1, 1, 3)
+    return x
+
+
+STATES = {
+    "rest": lambda sc, geo: sc.x.copy(),
+    "d=eps(1-1e-6)": lambda sc, geo: _set_d(sc, sc.x.copy(), geo, 1 - 1e-6),
+    "d=eps(1+1e-6)": lambda sc, geo: _set_d(sc, sc.x.copy(), geo, 1 + 1e-6),
+    "d=0.5eps": lambda sc, geo: _set_d(sc, sc.x.copy(), geo, 0.5),
+    "d=+1e-9eps": lambda sc, geo: _set_d(sc, sc.x.copy(), geo, 1e-9),
+    "d=-1e-9eps": lambda sc, geo: _set_d(sc, sc.x.copy(), geo, -1e-9),
+    "d=-0.5eps": lambda sc, geo: _set_d(sc, sc.x.copy(), geo, -0.5),
+    "d=-3eps": lambda sc, geo: _set_d(sc, sc.x.copy(), geo, -3.0),
+    "d=2eps": lambda sc, geo: _set_d(sc, sc.x.copy(), geo, 2.0),
+    "r at rounding level": lambda sc, geo: _slip(sc, geo, 0.0, "t1"),
+    "r=1e-9(1-1e-3)": lambda sc, geo: _slip(sc, geo, None, "oblique", r_abs=R_GUARD * (1 - 1e-3)),
+    "r=1e-9(1+1e-3)": lambda sc, geo: _slip(sc, geo, None, "oblique", r_abs=R_GUARD * (1 + 1e-3)),
+    "r=eh(1-1e-6)": lambda sc, geo: _slip(sc, geo, 1 - 1e-6, "oblique"),
+    "r=eh(1+1e-6)": lambda sc, geo: _slip(sc, geo, 1 + 1e-6, "oblique"),
+    "r=0.3eh t1": lambda sc, geo: _slip(sc, geo, 0.3, "t1"),
+    "r=0.3eh oblique": lambda sc, geo: _slip(sc, geo, 0.3, "oblique"),
+    "r=10eh t2": lambda sc, geo: _slip(sc, geo, 10.0, "t2"),
+    "r=10eh oblique, d=2eps": lambda sc, geo: _slip(sc, geo, 10.0, "oblique", dfac=2.0),
+    "r=1e3eh t1": lambda sc, geo: _slip(sc, geo, 1e3, "t1"),
+    "r=1e3eh oblique, d=-0.5eps": lambda sc, geo: _slip(sc, geo, 1e3, "oblique", dfac=-0.5),
+    "sheared to a sliver": _shear,
+    "bump": _bump,
+}
+
+
+def _reverse_mix(sc, geo):
+    """the evaluation state x_2 of the reverse-step tests (records lagged at x_1 = the scene's positions, previous positions = positions): slot s sticks
+    (r = 0.3 eps_v dt, s % 4 == 0), slips (10 eps_v dt, 1), keeps all four vertices where they were at x_1, so that r == 0.0 exactly (2: x_p - x_c - dx0 is an
+    expression subtracted from itself; with proj_dir == 0 the swapped sum may differ in its last bit), is penetrated to -0.5 eps with 0.3 eps_v dt (3)"""
+    x = sc.x.copy()
+    for k, g in enumerate(geo):
+        if k % 4 == 2:
+            continue
+        r, d = [(0.3 * EH, 0.5), (10 * EH, 0.5), None, (0.3 * EH, -0.5)][k % 4]
+        ang = 0.4 + 0.9 * k
+        x[g["vs"][3]] = g["base"] + (r * np.cos(ang) * g["T"][0] + r * np.sin(ang) * g["T"][1]) / g["s2"]
+        x[g["vs"][3]] = x[g["vs"][3]] + (d * EPS - _dist(sc, x, g)) * g["n"]
+    return x
+
+
+STATES["reverse mix"] = _reverse_mix
+# detection with prev == pos and the evaluation at that very pos: r == 0.0 bit for bit on the slots with proj_dir == 1 (own_records(name, lagged=False))
+STATES["r == 0 exactly"] = lambda sc, geo: sc.x.copy()
+UNLAGGED = ("reverse mix", "r == 0 exactly")
+
+
+def exact_zero_slots(name, state):
+    """slots whose construction fixes r == 0.0 in float64: proj_dir == 1 (the barycentre is summed in the order of the detection) and all four vertices where
+    the unlagged detection saw them"""
+    sc = scene(name)
+    recs = own_records(name, False)
+    if state == "r == 0 exactly":
+        return [s for s, r in enumerate(recs) if sc.probes[r["probe"]].pdir == 1]
+    if state == "reverse mix":
+        return [s for s, r in enumerate(recs) if s % 4 == 2 and sc.probes[r["probe"]].pdir == 1]
+    return []
+
+
+@functools.lru_cache(maxsize=None)
+def own_records(name, lagged=True):
+    """float64 records of a scene by the restatement itself (slot order), as restated dicts; lagged False: previous positions = positions, as the reverse
+    step detects"""
+    sc = scene(name)
+    return scene_records(F64, sc, prev=None if lagged else sc.x)
+
+
+def state_positions(name, state, lagged=True):
+    sc = scene(name)
+    return STATES[state](sc, _geom(sc, own_records(name, lagged)))
+
+
+# ------------------------------------------------------------------------------------------------ float64 errors, expectations
+def _rot_rec(rec, R):
+    out = dict(rec)
+    out["dx0"], out["n"] = np.asarray(rec["dx0"], float) @ R.T, np.asarray(rec["n"], float) @ R.T
+    out["T"] = (np.asarray(rec["T"], float).reshape(2, 3) @ R.T).ravel()
+    return out
+
+
+def _arr(ev, zf=None):
+    """evaluation dict -> arrays: E, g (4, 3), H (4, 3, 4, 3), gn1, gf1 (4, 3)"""
+    dt = float if isinstance(ev["E"], (float, np.floating)) else object
+    out = dict(E=np.array(ev["E"], dtype=dt), g=np.array(ev["g"], dtype=dt).reshape(4, 3), H=np.array(ev["H"], dtype=dt).reshape(4, 3, 4, 3),
+               gn1=np.array(ev["gn1"], dtype=dt).reshape(4, 3), gf1=np.array(ev["gf1"], dtype=dt).reshape(4, 3))
+    if "acc" in ev:
+        out["acc"], out["fg"] = np.array(ev["acc"], dtype=dt).reshape(4, 3), np.array(ev["fg"], dtype=dt).reshape(4, 3)
+    return out
+
+
+def _back(a, R):
+    out = dict(a)
+    for q in ("g", "gn1", "gf1", "acc", "fg"):
+        if q in a:
+            out[q] = a[q] @ R
+    out["H"] = np.einsum("ja,ljmk,kb->lamb", R, a["H"], R)
+    return out
+
+
+def f64_copies(X, rec, spd, z=None, n_jit=8):
+    """the float64 restatement of one slot at the state, its six coordinate rotations (records turned with it) and n_jit copies with every coordinate
+    moved by one ulp; arrays turned back"""
+    out = []
+    with np.errstate(all="ignore"):
+        for R in rotations():
+            ev = slot_eval(F64, X @ R.T, _rot_rec(rec, R), SC, spd)
+            if z is not None:
+                ev.update(slot_reverse(F64, X @ R.T, _rot_rec(rec, R), (np.asarray(z).reshape(4, 3) @ R.T).ravel()))
+            out.append(_back(_arr(ev), R))
+        for Xj in jitters(X, n=n_jit, seed=int(abs(X).sum() * 1e9) % 1000):
+            ev = slot_eval(F64, Xj, rec, SC, spd)
+            if z is not None:
+                ev.update(slot_reverse(F64, Xj, rec, z))
+            out.append(_arr(ev))
+    return out
+
+
+def _fn(a, axes=None):
+    return np.sqrt((np.asarray(a, float) ** 2).sum(axis=axes))
+
+
+def _bnd(e64, norm, extra=0.0):
+    """tet_numpy.bound on arrays"""
+    return 8 * np.maximum(e64 + extra, 4 * U * norm)
+
+
+class SlotRef:
+    """mp values (as (hi, lo)), bounds of one slot at one state under one spd: E, Eb; g, gb (4); H, Hb (4, 4); with z: acc, accb (4), fg, fgb (4, 3 per dof);
+    gn1, gf1 with their bounds per vertex (for the key sums); f64: the copies (for the harness)"""
+    def __init__(self, X, rec, spd, z=None):
+        X = np.asarray(X, float)
+        with mp.workdps(50):
+            ev = slot_eval(MP, X, rec, SC, spd)
+            if z is not None:
+                ev.update(slot_reverse(MP, X, rec, z))
+            m = _arr(ev)
+            self.mp = m
+            self.hl = {q: split(v) for q, v in m.items()}
+            if spd:
+                un = _arr(slot_eval(MP, X, rec, SC, 0))
+                hl_un = split(un["H"])
+        self.f64 = f64_copies(X, rec, spd, z)
+        e = lambda q, axes: np.max([_fn(diff(c[q], self.hl[q]), axes) for c in self.f64], axis=0)
+        self.Eb = float(_bnd(e("E", None), abs(self.hl["E"][0])))
+        for q in ("g", "gn1", "gf1") + (("acc",) if z is not None else ()):
+            setattr(self, q + "b", _bnd(e(q, 1), _fn(self.hl[q][0], 1)))
+        if z is not None:
+            self.fgb = _bnd(np.max([np.abs(diff(c["fg"], self.hl["fg"])) for c in self.f64], axis=0), np.abs(self.hl["fg"][0]))
+        nH = _fn(self.hl["H"][0], (1, 3))
+        if spd:   # projected: every sub-block takes the whole block's float64 error (projected, and unprojected: the projection is non-expansive) + 64 u |block|
+            f_un = f64_copies(X, rec, 0, None, n_jit=2)
+            whole = max(float(e("H", None)), max(float(_fn(diff(c["H"], hl_un))) for c in f_un))
+            self.Hb = _bnd(np.full((4, 4), whole), nH, 64 * U * float(_fn(hl_un[0])))
+        else:
+            self.Hb = _bnd(e("H", (1, 3)), nH)
+
+
+def dofs(vs):
+    return (3 * np.asarray(vs)[:, None] + np.arange(3)).ravel()
+
+
+class Expected:
+    """what an assembly of `cons` (float records as ctx.constraints() returns them) at `pos` must give under `spd` and the frozen dofs"""
+    def __init__(self, cons, pos, spd, frozen=None, z=None):
+        pos = np.asarray(pos, float).reshape(-1, 3)
+        self.cons, self.nv, self.spd = cons, len(pos), spd
+        self.frozen = np.zeros(3 * self.nv, bool) if frozen is None else np.asarray(frozen, bool)
+        self.slots = [SlotRef(pos[cons["idx"][s]], slot_rec(cons, s), spd, None if z is None else np.asarray(z).reshape(-1, 3)[cons["idx"][s]].ravel())
+                      for s in range(len(cons["k"]))]
+
+
+def worst_ratio(err, bnd, tag=""):
+    """largest err / bnd; every err finite (a NaN would vanish in a max), and an exact zero where the bound is zero"""
+    err, bnd = np.asarray(err, float), np.asarray(bnd, float)
+    assert np.isfinite(err).all(), (tag, "not finite")
+    on = bnd > 0
+    assert not err[~on].any(), (tag, "must be exact where the bound is zero")
+    return float((err[on] / bnd[on]).max()) if on.any() else 0.0
+
+
+def check_assembly(exp, got, R, tag, frozen=None):
+    """got: dict(blocks (S, 12, 12) unmasked, masked (S, 12, 12), g (nv, 3) gradient or None, op (3 nv, 3 nv) dense contact part of the operator, E or None).
+    Per slot and 3 x 3 sub-block, per vertex and per vertex pair against mp; masked blocks exactly zero on frozen rows and columns; nothing
+    outside the slots' pairs; spd: every block PSD to 64 u |block|"""
+    cons, nv = exp.cons, exp.nv
+    fz = np.zeros(3 * nv, bool) if frozen is None else np.asarray(frozen, bool)
+    S = len(exp.slots)
+    assert len(got["blocks"]) == S and len(got["masked"]) == S, tag
+    gsum, gb = [np.zeros((nv, 3)), np.zeros((nv, 3))], np.zeros(nv)
+    osum, ob, pat = [np.zeros((nv, 3, nv, 3)), np.zeros((nv, 3, nv, 3))], np.zeros((nv, nv)), np.zeros((nv, nv), bool)
+    Esum, Eb = mp.mpf(0), 0.0
+    for s, ref in enumerate(exp.slots):
+        vs = cons["idx"][s]
+        f12 = fz[dofs(vs)]
+        B = np.asarray(got["blocks"][s]).reshape(4, 3, 4, 3)
+        err = _fn(diff(B, ref.hl["H"]), (1, 3))
+        R.add("block spd%d" % exp.spd, worst_ratio(err, ref.Hb, (tag, s)), 1.0)
+        M = np.asarray(got["masked"][s])
+        assert not M[f12, :].any() and not M[:, f12].any(), (tag, s, "masked block not zero on a frozen dof")
+        keep = np.outer(~f12, ~f12)
+        Mm = [np.where(keep, ref.hl["H"][0].reshape(12, 12), 0.0).reshape(4, 3, 4, 3), np.where(keep, ref.hl["H"][1].reshape(12, 12), 0.0).reshape(4, 3, 4, 3)]
+        errm = _fn(diff(M.reshape(4, 3, 4, 3), Mm), (1, 3))
+        R.add("masked block spd%d" % exp.spd, worst_ratio(errm, ref.Hb, (tag, s)), 1.0)
+        if exp.spd:
+            for blk in (B.reshape(12, 12), M):
+                assert np.linalg.eigvalsh(0.5 * (blk + blk.T)).min() >= -64 * U * _fn(blk), (tag, s, "not PSD")
+        fr = (~f12).reshape(4, 3)
+        for a in range(4):
+            gsum[0][vs[a]] += ref.hl["g"][0][a] * fr[a]; gsum[1][vs[a]] += ref.hl["g"][1][a] * fr[a]
+            gb[vs[a]] += ref.gb[a]
+            for b in range(4):
+                osum[0][vs[a], :, vs[b], :] += Mm[0][a, :, b, :]; osum[1][vs[a], :, vs[b], :] += Mm[1][a, :, b, :]
+                ob[vs[a], vs[b]] += ref.Hb[a, b]
+                pat[vs[a], vs[b]] = True
+        Esum, Eb = Esum + ref.mp["E"], Eb + ref.Eb
+    if got.get("g") is not None:
+        g = np.asarray(got["g"]).reshape(nv, 3)
+        assert not g[fz.reshape(nv, 3)].any(), (tag, "gradient on a frozen dof")
+        R.add("F", worst_ratio(_fn(diff(g, gsum), 1), gb, tag), 1.0)
+    if got.get("op") is not None:
+        O = np.asarray(got["op"]).reshape(nv, 3, nv, 3)
+        assert not O.transpose(0, 2, 1, 3)[~pat].any(), (tag, "operator has entries outside the slots' vertex pairs")
+        eo = _fn(diff(O, osum), (1, 3))
+        R.add("operator", worst_ratio(eo[pat], ob[pat], tag), 1.0)
+    if got.get("E") is not None:
+        with mp.workdps(50):
+            assert np.isfinite(got["E"]), tag
+            ratio(R, "energy", abs(float(mp.mpf(float(got["E"])) - Esum)), Eb)
+
+
+def expected_keys(exp, p, kinds, frozen=None):
+    """{key: (mp sum, bound)} of the three per-key sums for the vector p (3 nv), from an Expected at spd 0"""
+    nv = exp.nv
+    fz = np.zeros(3 * nv, bool) if frozen is None else np.asarray(frozen, bool)
+    p = np.asarray(p, float).reshape(nv, 3) * ~fz.reshape(nv, 3)
+    out = {k: [mp.mpf(0), 0.0] for k in KEYS}
+    with mp.workdps(50):
+        for s, ref in enumerate(exp.slots):
+            vs = exp.cons["idx"][s]
+            pe = p[vs]
+            pm = np.array([[mp.mpf(float(v)) for v in r] for r in pe], dtype=object)
+            sn, sf = (pm * ref.mp["gn1"]).sum(), (pm * ref.mp["gf1"]).sum()
+            bn, bf = float((_fn(pe, 1) * ref.gn1b).sum()) / 8, float((_fn(pe, 1) * ref.gf1b).sum()) / 8     # (the e64 parts; bound() multiplies by 8 again)
+            k = mp.mpf(float(exp.cons["k"][s]))
+            terms = {"k_contact": (-(sn + sf * (k / mp.mpf(K_CONTACT))), bn + bf * abs(float(k)) / K_CONTACT)}
+            if kinds[s] == 1:
+                terms["mu_cloth_elastic"] = (-sf * (k / mp.mpf(MU_CE)), bf * abs(float(k)) / MU_CE)
+            if kinds[s] == 2:
+                terms["mu_cloth_cloth"] = (-sf * (k / mp.mpf(MU_CC)), bf * abs(float(k)) / MU_CC)
+            for key, (v, b) in terms.items():
+                out[key][0] += v
+                out[key][1] += bound(mp.mpf(b), abs(v))
+    return {k: (v, b) for k, (v, b) in out.items()}
+
+
+def expected_reverse(exp, z, kinds, frozen=None):
+    """from an Expected built with z at spd 0: per vertex (mp sum of the slots' backprop entries (hi, lo), bound), tmp_z_frozen's contact part
+    ((hi, lo) (nv, 3), bound (nv, 3)), friction_grad (mp, bound)"""
+    nv = exp.nv
+    fz = np.zeros(3 * nv, bool) if frozen is None else np.asarray(frozen, bool)
+    z = np.asarray(z, float).reshape(nv, 3)
+    acc, accb = np.full((nv, 3), mp.mpf(0), dtype=object), np.zeros(nv)
+    zf, zfb = np.full((nv, 3), mp.mpf(0), dtype=object), np.zeros((nv, 3))
+    fg, fgb = mp.mpf(0), 0.0
+    with mp.workdps(50):
+        for s, ref in enumerate(exp.slots):
+            vs = exp.cons["idx"][s]
+            f12 = fz[dofs(vs)]
+            zs = z[vs].ravel()
+            zm = np.array([mp.mpf(float(v)) for v in zs], dtype=object)
+            H = ref.mp["H"].reshape(12, 12)
+            for a in range(4):
+                acc[vs[a]] += ref.mp["acc"][a]; accb[vs[a]] += ref.accb[a]
+                for c in range(3):
+                    if f12[3 * a + c]:
+                        col = H[:, 3 * a + c]
+                        zf[vs[a], c] -= sum(col[k] * zm[k] for k in range(12) if not f12[k])
+                        # |sum_k dH[k] z[k]| <= sum over the row blocks of |dH block| |z block|
+                        zfb[vs[a], c] += float(sum(ref.Hb[k, a] * _fn(zs[3 * k:3 * k + 3] * ~f12[3 * k:3 * k + 3]) for k in range(4)))
+            if kinds[s] == 2:
+                free = ~f12
+                t = sum(zm[k] * ref.mp["fg"].ravel()[k] for k in range(12) if free[k]) / mp.mpf(MU_CC)
+                fg += t
+                fgb += bound(mp.mpf(float((np.abs(zs) * ref.fgb.ravel() * free).sum()) / 8 / MU_CC), abs(t))
+    return dict(acc=split(acc), accb=accb, zf=split(zf), zfb=zfb, fg=fg, fgb=fgb)
+
+
+# ------------------------------------------------------------------------------------------------ the float64 restatement in the kernels' place
+def f64_kernels(sc_name, pos, spd, frozen=None, rot=1, with_E=True, lagged=True):
+    """what the engine returns, by the float64 restatement evaluated in a rotated frame (other rounding than the copy at the identity): records from the
+    construction, blocks, masked blocks, gradient, dense contact operator, energy"""
+    sc = scene(sc_name)
+    recs = own_records(sc_name, lagged)
+    cons = records_as_data(recs)
+    nv = sc.nv
+    fz = np.zeros(3 * nv, bool) if frozen is None else np.asarray(frozen, bool)
+    R = rotations()[rot]
+    blocks, masked, g, op, E = [], [], np.zeros((nv, 3)), np.zeros((nv, 3, nv, 3)), 0.0
+    for s in range(len(recs)):
+        vs = cons["idx"][s]
+        rec = slot_rec(cons, s)
+        with np.errstate(all="ignore"):
+            a = _back(_arr(slot_eval(F64, pos[vs] @ R.T, _rot_rec(rec, R), SC, spd)), R)
+        f12 = fz[dofs(vs)]
+        B = a["H"].reshape(12, 12)
+        M = np.where(np.outer(~f12, ~f12), B, 0.0)
+        blocks.append(B); masked.append(M)
+        E += float(a["E"])
+        for i in range(4):
+            g[vs[i]] += a["g"][i] * ~f12[3 * i:3 * i + 3]
+            for j in range(4):
+                op[vs[i], :, vs[j], :] += M.reshape(4, 3, 4, 3)[i, :, j, :]
+    return cons, dict(blocks=np.array(blocks), masked=np.array(masked), g=g, op=op.reshape(3 * nv, 3 * nv), E=E if with_E else None)
+
+
+# ------------------------------------------------------------------------------------------------ decisions
+def decisions(sc_name, state, xp, lagged=True):
+    """[(probe or slot, name, normalised distance)] of the records' decisions at the detection state and of every slot's at the evaluation state"""
+    sc = scene(sc_name)
+    out = []
+    with mp.workdps(50):
+        d = []
+        scene_records(xp, sc, dec=d, prev=None if lagged else sc.x)
+        for i, dd in d:
+            out += [("det", i, n, v) for n, v in dd]
+        cons = records_as_data(own_records(sc_name, lagged))
+        pos = state_positions(sc_name, state, lagged)
+        for s in range(len(cons["k"])):
+            dd = []
+            slot_eval(xp, pos[cons["idx"][s]], slot_rec(cons, s), SC, 0, dd)
+            out += [("eval", s, n, v) for n, v in dd]
+    return out
+
+
+def _same(a, b, tag):
+    assert len(a) == len(b)
+    for p, q in zip(a, b):
+        assert p[:3] == q[:3]
+        da, db = float(p[3]), float(q[3])
+        assert abs(da) >= SAFE and abs(db) >= SAFE and (da > 0) == (db > 0), (tag, p, q)
+
+
+def decisions_safe(sc_name, state, lagged=True):
+    """every decision has the same outcome, at least SAFE from its threshold, in mp, in float64 and in every rotated or jittered float64 copy that e64 is
+    taken from (the copies take the records as data: they repeat the evaluation's decisions only).  A condition on the inputs of a GPU test, not a
+    tolerance.  The exception: on the slots of exact_zero_slots() the construction fixes r == 0.0; that is asserted bit for bit on the float64 evaluation
+    of the state itself (both friction decisions at exactly -1), mp sees the rounding of the exported dx0 (1e-18), and the jittered and rotated copies,
+    which leave the construction, only have to stay below both thresholds"""
+    sc = scene(sc_name)
+    dm = decisions(sc_name, state, MP, lagged)
+    _same(dm, decisions(sc_name, state, F64, lagged), (sc_name, state))
+    cons = records_as_data(own_records(sc_name, lagged))
+    pos = state_positions(sc_name, state, lagged)
+    ev = [t for t in dm if t[0] == "eval"]
+    exact = exact_zero_slots(sc_name, state) if not lagged else []
+    assert lagged or state not in UNLAGGED or exact, (sc_name, state, "no slot with r == 0.0")
+    for s in exact:
+        dd = []
+        ev0 = slot_eval(F64, pos[cons["idx"][s]], slot_rec(cons, s), SC, 0, dd)
+        assert ev0["r"] == 0.0 and [float(v) for n, v in dd if n in ("r_eh", "r_guard")] == [-1.0, -1.0], (sc_name, state, s)
+    for s in range(len(cons["k"])):
+        X, rec = pos[cons["idx"][s]], slot_rec(cons, s)
+        mine = [t for t in ev if t[1] == s]
+        copies = [(X @ R.T, _rot_rec(rec, R)) for R in rotations()] + [(Xj, rec) for Xj in jitters(X, n=8, seed=int(abs(X).sum() * 1e9) % 1000)]
+        for Xc, rc in copies:
+            dd = []
+            slot_eval(F64, Xc, rc, SC, 0, dd)
+            _same(mine, [("eval", s, n, v) for n, v in dd], (sc_name, state, s))
+    return True
