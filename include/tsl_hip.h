@@ -103,13 +103,15 @@ int tsl_ctx_create(const tsl_scene_desc* desc, tsl_ctx** out);
 void tsl_ctx_destroy(tsl_ctx* ctx);
 int tsl_set_stream(tsl_ctx* ctx, void* hip_stream);
 
-/* 0-d field writes of the reference and the engine's own switches (43 keys + three patterns; an unknown key is an error).
+/* 0-d field writes of the reference and the engine's own switches (44 keys + three patterns; an unknown key is an error).
  *  Scene (trajopt_folding.py:50,66; Scene_folding.py:30-31; geometry.py:8-19; geometry_self.py:166-230):
  *   "cloth<i>.Kb|Kl|Ka|k_angle", "elastic<i>.mu|lam|alpha", "mu_cloth_elastic", "mu_cloth_cloth", "k_contact", "eps_contact", "eps_v", "damping",
  *   "k_handle" (0 default: stiffness in N/m of the soft handles of tsl_set_handles; negative fails; with 0, or with no handles, no handle kernel is launched),
  *   "k_tie" (0 default: stiffness in N/m of the ties of tsl_set_ties; negative fails; with 0, or with no ties, no tie slot exists and no tie kernel is launched),
  *   "k_collider" (0 default: stiffness in N/m shared by the half-space colliders of tsl_set_colliders; negative or non-finite fails; with 0, or with no
  *   colliders, no collider kernel is launched),
+ *   "k_sphere" (0 default: stiffness in N/m shared by the sphere colliders of tsl_set_spheres; negative or non-finite fails; with 0, or with no
+ *   spheres, no sphere kernel is launched),
  *   "cloth<i>.membrane" (0 default: edge springs Kl + area term Ka, as the reference; 1: a St. Venant-Kirchhoff membrane per face, A0 Psi(F) with
  *   F = [x1 - x0, x2 - x0] Dm^-1, Dm the rest triangle rebuilt from the face's rest lengths (fails naming a face whose lengths violate the triangle
  *   inequality), Psi = mu |E|^2 + lam/2 tr(E)^2, E = (F^T F - I) / 2, A0 the rest area; it replaces the springs and the area term of the cloth's
@@ -280,6 +282,47 @@ int tsl_set_collider_offsets(tsl_ctx* ctx, const double* offsets_host);
 int tsl_collider_count(tsl_ctx* ctx, int32_t* out_host);
 int tsl_collider_force(tsl_ctx* ctx, const double* pos_dev, const double* prev_pos_dev, double* out_host);
 int tsl_collider_grad(tsl_ctx* ctx, const double* pos_dev, const double* prev_pos_dev, const double* p_dev, double* out_host);
+
+/* Sphere colliders (no reference counterpart: its balls are meshed bodies): up to TSL_MAX_SPHERES solid balls with the cloth outside.  Sphere j has a
+ * centre c_j that may be set before every step, a previous centre cp_j (where the ball was at the start of the step), a radius R_j > 0, fixed once
+ * the list is set, and a friction coefficient mu_j >= 0; the stiffness "k_sphere" of tsl_set_param is shared (0 by default: off), the thickness of
+ * the shell is eps_contact, the friction regularisation eh = eps_v dt.  A per-vertex 8-bit mask of its own says which spheres act on a vertex.  For
+ * vertex v and sphere j, with x_prev the start-of-step positions (the prev_pos argument of tsl_energy / tsl_assemble; x_{s-1} in a reverse step):
+ *   q  = x - c,       rho  = |q|,  n  = q / rho,   d  = rho - R
+ *   q0 = x_prev - cp, rho0 = |q0|, n0 = q0 / rho0, d0 = rho0 - R
+ *   lam = mu k max(0, eps - d0),  P0 = I - n0 n0^T,  D = (x - x_prev) - (c - cp),  w = P0 D,  r = |w|,  a = f1(r)
+ *   E = [d < eps] 1/2 k (d - eps)^2 + lam f0(r),  g = [d < eps] k (d - eps) n + lam a w,
+ *   H = H_n + lam M on the vertex's own diagonal block,  H_n = [d < eps] (k n n^T + k (d - eps) / rho (I - n n^T)),
+ *   M = a P0 + [r > 1e-9] (f2 / r) w w^T.
+ * The slip is relative to the ball: a ball that moves sideways drags the cloth, one that moves along n0 adds no slip.  The second part of H_n is
+ * negative in the tangent plane: tsl_assemble with spd = 0 (the reverse step's operator) adds H_n exact, every other mode, with and without
+ * "spd_literal", adds [d < eps] k n n^T (the eigen-clamp in closed form) and the same numbers; lam M is positive semi-definite as it stands.  No
+ * constraint slot, no row list: the plans of the factorisation and tsl_contact_counts do not depend on spheres.  Nothing is stored per step.  A
+ * pair with rho < 1e-12 contributes nothing, one with rho0 < 1e-12 has no friction.  Frozen dofs follow the mask rule.  One lane per vertex, no
+ * atomics: the same bits run to run.  With no spheres or k_sphere = 0 every launch is the one it was.
+ *   tsl_set_spheres: centres_host (n x 3), radii_host (n), mu_host (n), vertex_mask_host (tot_NV bytes, bit j: sphere j acts on the vertex; NULL:
+ *     every sphere on every vertex); host pointers, copied; cp := c; the stream is synchronised; n = 0 removes the spheres.  Fails, naming the
+ *     offender, and leaves the previous list in place for more than TSL_MAX_SPHERES spheres or n < 0, a non-finite centre, a radius that is not
+ *     finite and positive, a negative or non-finite mu, a mask byte that names a sphere at or above n.
+ *   tsl_set_sphere_centres: centres_host (n x 3) and prev_centres_host (n x 3; NULL: cp := c) for the next energy, assemble, step or adjoint step;
+ *     set those of step s before the reverse step s and before tsl_sphere_grad.  A non-finite entry fails, naming the sphere, and leaves both in place.
+ *   tsl_sphere_count: n.
+ *   tsl_sphere_force: out_host (n x 3) = -sum_v g_v of sphere j at the state (pos, prev_pos): the net force the ball applies to the cloth, in the
+ *     sign of tsl_collider_force; frozen dofs are NOT masked; k_sphere = 0: zeros.
+ *   tsl_sphere_grad: out_host (n x 8) at the tape state (pos = x_s, prev_pos = x_{s-1}), sign of tsl_collider_grad, p the adjoint solution on its free
+ *     dofs (p_dev == NULL: the solution of the last tsl_adjoint_step): the share of one reverse step in
+ *       [0:3] d(loss)/d(c_j)  = -sum_v (dg/dc)^T p_v = sum_v (H_n + lam M) p_v  (H_n exact),
+ *       [3:6] d(loss)/d(cp_j) = -sum_v (dg/dcp)^T p_v = -sum_v (lam M - L)^T p_v,
+ *       [6]   d(loss)/d(mu_j) = -sum_v p_v . k max(0, eps - d0) a w,
+ *       [7]   d(loss)/d(R_j)  = -sum_v p_v . (-[d < eps] k n + [d0 < eps] mu k a w),
+ *     with L = dg/d(q0) at fixed D = -[d0 < eps] mu k (a w) n0^T + lam J_n P0 / rho0,  J_n = -B ((n0 . D) I + n0 D^T),  B = a I + [r > 1e-9] (f2 / r) w w^T.
+ *     The reverse step itself adds -(dg/dx_prev)^T p_v = lam M p_v - L^T p_v to the free dofs of the vertex's row of pos_grad[s-1]. */
+#define TSL_MAX_SPHERES 8
+int tsl_set_spheres(tsl_ctx* ctx, const double* centres_host, const double* radii_host, const double* mu_host, int32_t n, const uint8_t* vertex_mask_host);
+int tsl_set_sphere_centres(tsl_ctx* ctx, const double* centres_host, const double* prev_centres_host);
+int tsl_sphere_count(tsl_ctx* ctx, int32_t* out_host);
+int tsl_sphere_force(tsl_ctx* ctx, const double* pos_dev, const double* prev_pos_dev, double* out_host);
+int tsl_sphere_grad(tsl_ctx* ctx, const double* pos_dev, const double* prev_pos_dev, const double* p_dev, double* out_host);
 
 /* BaseScene.compute_energy (BaseScene.py:427-451) at the given state, constraints as last detected. */
 int tsl_energy(tsl_ctx* ctx, const double* pos_dev, const double* prev_pos_dev, const double* vel_dev,

@@ -293,6 +293,49 @@ class TslContext:
         check(self.L.tsl_collider_grad(self.h, _ptr(pos), _ptr(prev_pos), _ptr(p), out.ctypes.data), "tsl_collider_grad")
         return out
 
+    # ---- sphere colliders (tsl_set_spheres; stiffness: set_param("k_sphere", k))
+    def set_spheres(self, centres, radii, mu, vertex_mask=None):
+        """n solid balls (centre c_j, radius R_j, friction mu_j) with the cloth outside; vertex_mask (tot_NV,) uint8, bit j: sphere j acts on the vertex,
+        None: all on all; an empty list removes them.  The previous centres are set to the centres; the radii stay fixed."""
+        r = _np(radii, np.float64).reshape(-1)
+        n = len(r)
+        ce = _np(centres, np.float64).reshape(-1, 3)
+        m = _np(mu, np.float64).reshape(-1)
+        assert ce.shape == (n, 3) and m.shape == (n,), (ce.shape, r.shape, m.shape)
+        vm = None if vertex_mask is None else _np(vertex_mask, np.uint8).reshape(-1)
+        assert vm is None or vm.shape == (self.tot_NV,), vm.shape
+        check(self.L.tsl_set_spheres(self.h, ce.ctypes.data if n else None, r.ctypes.data if n else None, m.ctypes.data if n else None, n,
+                                     None if vm is None else vm.ctypes.data), "tsl_set_spheres")
+
+    def set_sphere_centres(self, centres, prev_centres=None):
+        """the centres of the next energy / assembly / step / reverse step and where the balls were at the start of that step (None: the centres)"""
+        n = self.sphere_count()
+        ce = _np(centres, np.float64).reshape(-1, 3)
+        cp = None if prev_centres is None else _np(prev_centres, np.float64).reshape(-1, 3)
+        assert ce.shape == (n, 3) and (cp is None or cp.shape == (n, 3)), (ce.shape, n)
+        if n:
+            check(self.L.tsl_set_sphere_centres(self.h, ce.ctypes.data, None if cp is None else cp.ctypes.data), "tsl_set_sphere_centres")
+
+    def sphere_count(self):
+        out = C.c_int32(0)
+        check(self.L.tsl_sphere_count(self.h, C.byref(out)), "tsl_sphere_count")
+        return int(out.value)
+
+    def sphere_force(self, pos, prev_pos):
+        """(n, 3) -sum_v g_v: the net force every ball applies to the cloth at the state (pos, prev_pos) (frozen dofs not masked)"""
+        self.refresh_stream()
+        out = np.zeros((self.sphere_count(), 3))
+        check(self.L.tsl_sphere_force(self.h, _ptr(pos), _ptr(prev_pos), out.ctypes.data), "tsl_sphere_force")
+        return out
+
+    def sphere_grad(self, pos, prev_pos, p=None):
+        """(n, 8) contribution of one reverse step to d(loss)/d(centre (3), previous centre (3), mu, R) of every sphere at the tape state (x_s, x_{s-1}) with
+        the centres of step s in place; p None: the solution of the last adjoint_step, else a 3 * tot_NV device vector"""
+        self.refresh_stream()
+        out = np.zeros((self.sphere_count(), 8))
+        check(self.L.tsl_sphere_grad(self.h, _ptr(pos), _ptr(prev_pos), _ptr(p), out.ctypes.data), "tsl_sphere_grad")
+        return out
+
     # ---- engine calls
     def energy(self, pos, prev_pos, vel, ref_angle):
         self.refresh_stream()

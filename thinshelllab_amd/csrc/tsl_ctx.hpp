@@ -14,6 +14,7 @@
 
 #include "../../include/tsl_hip.h"
 #include "collider_host.hpp"
+#include "sphere_host.hpp"
 #include "k_body.hpp"
 #include "direct_plan.hpp"
 #include "scene_tables.hpp"   // ClothDev, ElasticDev (the per-cloth / per-body constants the kernels read) and the host tables of a scene
@@ -405,6 +406,12 @@ struct tsl_ctx {
   double k_collider = 0.0;
   DevBuf<unsigned char> col_mask;      // NV
   DevBuf<double> col_part, col_out;    // COLLIDER_SLOTS per workgroup of 256 vertices; COLLIDER_SLOTS
+  // ---- sphere colliders (tsl_set_spheres, k_sphere.hpp): the table (sph.n balls, centres and previous centres; its k, eps, eh are filled in per
+  // launch), the per-vertex mask, and the partials and the result of the read-outs.  The sphere kernels run while sph.n > 0 and k_sphere != 0
+  SphereTable sph{};
+  double k_sphere = 0.0;
+  DevBuf<unsigned char> sph_mask;      // NV
+  DevBuf<double> sph_part, sph_out;    // SPHERE_SLOTS per workgroup of 256 vertices; SPHERE_SLOTS
 
   // ---- multigrid preconditioner
   std::vector<MgCloth*> mg;

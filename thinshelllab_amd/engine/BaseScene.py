@@ -170,6 +170,46 @@ def validate_colliders(tot_NV, normals, offsets, mu, vertex_ids=None):
     return unit, o.copy(), m.copy(), mask
 
 
+TSL_MAX_SPHERES = 8
+
+
+def validate_spheres(tot_NV, centres, radii, mu, vertex_ids=None):
+    """The checks of tsl_set_spheres on the host, with the messages of csrc/sphere_host.hpp: returns (centres (n, 3), radii (n), mu (n), uint8 mask
+    (tot_NV)) or raises ValueError naming the offender -- more than TSL_MAX_SPHERES spheres, a non-finite centre, a radius that is not finite and
+    positive, a negative or non-finite friction coefficient, a vertex id out of range.  vertex_ids None: every sphere acts on every vertex; else one
+    entry per sphere, None (all vertices) or a list of global vertex ids."""
+    r = np.asarray(radii, dtype=np.float64).reshape(-1)
+    n = len(r)
+    c = np.asarray(centres, dtype=np.float64).reshape(-1, 3) if n else np.zeros((0, 3))
+    m = np.asarray(mu, dtype=np.float64).reshape(-1)
+    if c.shape != (n, 3) or m.shape != (n,):
+        raise ValueError(f"set_spheres: {len(c)} centres and {m.size} friction coefficients for {n} radii")
+    if n > TSL_MAX_SPHERES:
+        raise ValueError(f"set_spheres: {n} spheres: at most {TSL_MAX_SPHERES}")
+    for j in range(n):
+        if not np.isfinite(c[j]).all():
+            raise ValueError(f"set_spheres: centre ({c[j, 0]:g}, {c[j, 1]:g}, {c[j, 2]:g}) of sphere {j} is not finite")
+        if not (np.isfinite(r[j]) and r[j] > 0.0):
+            raise ValueError(f"set_spheres: radius {r[j]:g} of sphere {j} is not finite and positive")
+        if not (m[j] >= 0.0 and np.isfinite(m[j])):
+            raise ValueError(f"set_spheres: friction coefficient {m[j]:g} of sphere {j} is negative or not finite")
+    mask = np.full(tot_NV, (1 << n) - 1, np.uint8)
+    if vertex_ids is not None:
+        if len(vertex_ids) != n:
+            raise ValueError(f"set_spheres: {len(vertex_ids)} vertex lists for {n} spheres")
+        mask[:] = 0
+        for j, ids in enumerate(vertex_ids):
+            if ids is None:
+                mask |= np.uint8(1 << j)
+                continue
+            v = np.asarray(ids, dtype=np.int64).reshape(-1)
+            for vi in v.tolist():
+                if vi < 0 or vi >= tot_NV:
+                    raise ValueError(f"set_spheres: vertex {vi} of sphere {j} out of range [0, {tot_NV})")
+            mask[v] |= np.uint8(1 << j)
+    return c.copy(), r.copy(), m.copy(), mask
+
+
 class _SystemMatrix:
     """Stand-in for ``SparseMatrix`` (sparse_solver.py): the matrix itself lives inside the context."""
 
@@ -241,6 +281,16 @@ class BaseScene:
         self._col_mu = np.zeros(0)
         self._col_mask = np.zeros(0, np.uint8)
         self.k_collider = 0.0
+        # sphere colliders (set_spheres): _sph_c the centres for the next step, _sph_cp the centres of the last completed step (where the balls are at the
+        # start of the next one), _sph_cp_step the previous centres that the last completed step used (the tape records it); radii, friction
+        # coefficients, the per-vertex mask and the stiffness k_sphere, kept here and pushed to the engine context lazily
+        self._sph_c = np.zeros((0, 3))
+        self._sph_cp = np.zeros((0, 3))
+        self._sph_cp_step = np.zeros((0, 3))
+        self._sph_R = np.zeros(0)
+        self._sph_mu = np.zeros(0)
+        self._sph_mask = np.zeros(0, np.uint8)
+        self.k_sphere = 0.0
         # rigid frames of the handles (set_handle_frames): frame and local point of every handle, position and unit quaternion of every frame
         self._frame_of = np.zeros(0, np.int32)
         self._frame_local = np.zeros((0, 3))
@@ -520,6 +570,8 @@ class BaseScene:
                 self._push_ties()
             if self.n_collider:
                 self._push_colliders()
+            if self.n_sphere:
+                self._push_spheres()
             self._dirty.clear()
         if self._dirty:
             if "ties" in self._dirty:
@@ -528,6 +580,10 @@ class BaseScene:
                 self._push_colliders()
             elif "collider_offsets" in self._dirty:
                 self._ctx.set_collider_offsets(self._col_o)
+            if "spheres" in self._dirty:
+                self._push_spheres()
+            elif "sphere_centres" in self._dirty:
+                self._ctx.set_sphere_centres(self._sph_c, self._sph_cp)
             if "handles" in self._dirty:
                 self._push_handles()
             else:
@@ -719,6 +775,60 @@ class BaseScene:
         self._ctx.set_colliders(self._col_n, self._col_o, self._col_mu, self._col_mask if self.n_collider else None)
         self._ctx.set_param("k_collider", self.k_collider)
 
+    # ------------------------------------------------------------------ sphere colliders (no counterpart in the reference)
+    @property
+    def n_sphere(self):
+        return len(self._sph_R)
+
+    def set_spheres(self, centres, radii, mu, k, vertex_ids=None):
+        """Up to 8 solid balls (centre, radius > 0, friction coefficient mu_j >= 0) with the cloth outside and one stiffness k >= 0 in N/m: a
+        fingertip, a pusher, a mandrel, a roller that drags the sheet (set_sphere_centres before every step).  The shell is eps_contact thick, the
+        friction is regularised with eps_v dt and acts on the slip relative to the ball.  vertex_ids None: every sphere acts on every vertex; else
+        one entry per sphere, None or a list of global vertex ids.  The balls start at rest (previous centres = centres); the radii stay fixed; an
+        empty list removes the spheres.  The lists are checked here, before any library call."""
+        c, r, m, mask = validate_spheres(self.tot_NV, centres, radii, mu, vertex_ids)
+        k = float(k)
+        if not (k >= 0.0 and np.isfinite(k)):
+            raise ValueError(f"set_spheres: k_sphere must be finite and >= 0 (got {k:g})")
+        self._sph_c, self._sph_cp, self._sph_cp_step = c, c.copy(), c.copy()
+        self._sph_R, self._sph_mu, self._sph_mask, self.k_sphere = r, m, mask, k
+        self._dirty.add("spheres")
+
+    def _check_centres(self, what, centres):
+        c = np.asarray(centres, dtype=np.float64).reshape(-1, 3)
+        if c.shape != (self.n_sphere, 3):
+            raise ValueError(f"set_sphere_centres: {len(c)} {what}s for {self.n_sphere} spheres")
+        for j in range(len(c)):
+            if not np.isfinite(c[j]).all():
+                raise ValueError(f"set_sphere_centres: {what} ({c[j, 0]:g}, {c[j, 1]:g}, {c[j, 2]:g}) of sphere {j} is not finite")
+        return c.copy()
+
+    def set_sphere_centres(self, centres, prev_centres=None):
+        """the centres c_j of the next step (or energy, assembly, reverse step).  Where the balls were at the start of that step is kept by the scene:
+        the centres of the last completed step.  prev_centres overrides it (a tape puts a recorded step back; a caller restarts a rollout)."""
+        c = self._check_centres("centre", centres)
+        if prev_centres is not None:
+            self._sph_cp = self._check_centres("previous centre", prev_centres)
+        self._sph_c = c
+        self._dirty.add("sphere_centres")
+
+    def sphere_force(self):
+        """(n, 3): the net force every ball applies to the cloth at the current positions and start-of-step positions (a ball under a resting cloth
+        reads the weight it carries)"""
+        return self._ensure_ctx().sphere_force(self.pos.t, self.prev_pos.t)
+
+    def _push_spheres(self):
+        self._ctx.set_spheres(self._sph_c, self._sph_R, self._sph_mu, self._sph_mask if self.n_sphere else None)
+        self._ctx.set_sphere_centres(self._sph_c, self._sph_cp)
+        self._ctx.set_param("k_sphere", self.k_sphere)
+
+    def _spheres_step_done(self):
+        """a step is complete: its centres are where the balls are at the start of the next one"""
+        if self.n_sphere:
+            self._sph_cp_step = self._sph_cp
+            self._sph_cp = self._sph_c.copy()
+            self._dirty.add("sphere_centres")
+
     # ------------------------------------------------------------------ rigid frames for the handles (no counterpart in the reference)
     @property
     def n_frame(self):
@@ -846,6 +956,7 @@ class BaseScene:
         ctx = self._ensure_ctx()
         ctx.set_param("contact", 0.0 if f_contact is None else 1.0)
         st = ctx.step(*self._state())
+        self._spheres_step_done()
         self.last_stats = st
         self.nc[None] = st["nc"]
         self.E[None] = st["energy"]

@@ -35,6 +35,26 @@ def handle_tape_init(grad, sys, T):
     if grad.n_collider:
         grad.collider_offsets = Field(torch.zeros((T, grad.n_collider), dtype=torch.float64))
         grad.collider_grad = Field(torch.zeros((T, grad.n_collider, 2), dtype=torch.float64))
+    # sphere colliders (BaseScene.set_spheres): the centres and previous centres of every step and d(loss)/d(c, cp, mu, R) per reverse step
+    grad.n_sphere = getattr(sys, "n_sphere", 0)
+    if grad.n_sphere:
+        grad.sphere_centres = Field(torch.zeros((T, grad.n_sphere, 3), dtype=torch.float64))
+        grad.sphere_centres_prev = Field(torch.zeros((T, grad.n_sphere, 3), dtype=torch.float64))
+        grad.sphere_grad = Field(torch.zeros((T, grad.n_sphere, 8), dtype=torch.float64))
+
+
+def sphere_centre_grad(grad):
+    """(T, n, 3) d(loss)/d(centre trajectory) when each step's previous centre was the centre of the step before: row s is
+    sphere_grad[s, :, 0:3] + sphere_grad[s + 1, :, 3:6].  Raises if the tape shows another trajectory."""
+    if not grad.n_sphere:
+        raise ValueError("sphere_centre_grad: the scene has no spheres")
+    c, cp, g = grad.sphere_centres.t, grad.sphere_centres_prev.t, grad.sphere_grad.t
+    if not torch.equal(cp[1:], c[:-1]):
+        s = int((cp[1:] != c[:-1]).reshape(len(c) - 1, -1).any(dim=1).nonzero()[0, 0]) + 1
+        raise ValueError(f"sphere_centre_grad: the previous centres of step {s} are not the centres of step {s - 1}")
+    out = g[:, :, 0:3].clone()
+    out[:-1] += g[1:, :, 3:6]
+    return out
 
 
 def handle_tape_reset(grad):
@@ -43,6 +63,10 @@ def handle_tape_reset(grad):
     if grad.n_collider:
         grad.collider_offsets.fill(0)
         grad.collider_grad.fill(0)
+    if grad.n_sphere:
+        grad.sphere_centres.fill(0)
+        grad.sphere_centres_prev.fill(0)
+        grad.sphere_grad.fill(0)
     if grad.n_handle:
         grad.handle_targets.fill(0)
         grad.handle_grad.fill(0)
@@ -61,6 +85,9 @@ def handle_tape_record(grad, sys, step):
         grad.frame_quat.t[step] = torch.as_tensor(sys._frame_quat)
     if grad.n_collider:
         grad.collider_offsets.t[step] = torch.as_tensor(sys._col_o)
+    if grad.n_sphere:   # the step just completed: its centres, and where the balls were when it started
+        grad.sphere_centres.t[step] = torch.as_tensor(sys._sph_cp)
+        grad.sphere_centres_prev.t[step] = torch.as_tensor(sys._sph_cp_step)
 
 
 def handle_tape_push(grad, sys, step):
@@ -72,6 +99,8 @@ def handle_tape_push(grad, sys, step):
         sys.set_frame_poses(grad.frame_pos.t[step].numpy(), grad.frame_quat.t[step].numpy())
     if grad.n_collider:   # the offsets of step `step`: the reverse step evaluates d, d0 and the blocks with them
         sys.set_collider_offsets(grad.collider_offsets.t[step].numpy())
+    if grad.n_sphere:   # the centres and previous centres of step `step`: the reverse step evaluates the contact frame with them
+        sys.set_sphere_centres(grad.sphere_centres.t[step].numpy(), grad.sphere_centres_prev.t[step].numpy())
 
 
 def handle_tape_pull(grad, ctx, step):
@@ -84,6 +113,8 @@ def handle_tape_pull(grad, ctx, step):
         grad.tie_grad.t[step] += torch.as_tensor(ctx.tie_grad(grad.pos_buffer.t[step]))
     if grad.n_collider:   # collider_grad[step] += d(loss)/d(offsets of step `step`, mu) of the reverse step just taken, at the tape state (x_step, x_{step-1})
         grad.collider_grad.t[step] += torch.as_tensor(ctx.collider_grad(grad.pos_buffer.t[step], grad.pos_buffer.t[step - 1]))
+    if grad.n_sphere:   # sphere_grad[step] += d(loss)/d(c, cp of step `step`, mu, R) of the reverse step just taken, at the tape state (x_step, x_{step-1})
+        grad.sphere_grad.t[step] += torch.as_tensor(ctx.sphere_grad(grad.pos_buffer.t[step], grad.pos_buffer.t[step - 1]))
 
 
 class Grad:
@@ -126,6 +157,10 @@ class Grad:
 
     def init_mass(self, sys):
         self.mass.copy_from(sys.mass)
+
+    def sphere_centre_grad(self):
+        """(T, n, 3) d(loss)/d(centre trajectory of the spheres); raises if a step's previous centres were not the centres of the step before"""
+        return sphere_centre_grad(self)
 
     # :37-51
     def copy_pos(self, sys, step):

@@ -13,7 +13,7 @@ Beyond the reference: ``param_keys`` names further scalars, spelled as ``tsl_set
 """
 import torch
 
-from .analytic_grad_single import handle_tape_init, handle_tape_pull, handle_tape_push, handle_tape_record, handle_tape_reset
+from .analytic_grad_single import handle_tape_init, handle_tape_pull, handle_tape_push, handle_tape_record, handle_tape_reset, sphere_centre_grad
 from .field import Field, ScalarField
 
 
@@ -64,6 +64,10 @@ class Grad:
 
     def init_mass(self, sys):  # :41-44
         self.mass.copy_from(sys.mass)
+
+    def sphere_centre_grad(self):
+        """(T, n, 3) d(loss)/d(centre trajectory of the spheres); raises if a step's previous centres were not the centres of the step before"""
+        return sphere_centre_grad(self)
 
     def copy_pos(self, sys, step):  # :46-59
         self.pos_buffer.t[step].copy_(sys.pos.t)

@@ -63,6 +63,7 @@ class SceneGroup:
         out = []
         for s, r in zip(self.scenes, st):
             d = r.as_dict()
+            s._spheres_step_done()
             s.last_stats = d
             s.nc[None] = d["nc"]
             s.E[None] = d["energy"]
