@@ -103,7 +103,7 @@ int tsl_ctx_create(const tsl_scene_desc* desc, tsl_ctx** out);
 void tsl_ctx_destroy(tsl_ctx* ctx);
 int tsl_set_stream(tsl_ctx* ctx, void* hip_stream);
 
-/* 0-d field writes of the reference and the engine's own switches (44 keys + three patterns; an unknown key is an error).
+/* 0-d field writes of the reference and the engine's own switches (45 keys + three patterns; an unknown key is an error).
  *  Scene (trajopt_folding.py:50,66; Scene_folding.py:30-31; geometry.py:8-19; geometry_self.py:166-230):
  *   "cloth<i>.Kb|Kl|Ka|k_angle", "elastic<i>.mu|lam|alpha", "mu_cloth_elastic", "mu_cloth_cloth", "k_contact", "eps_contact", "eps_v", "damping",
  *   "k_handle" (0 default: stiffness in N/m of the soft handles of tsl_set_handles; negative fails; with 0, or with no handles, no handle kernel is launched),
@@ -112,6 +112,8 @@ int tsl_set_stream(tsl_ctx* ctx, void* hip_stream);
  *   colliders, no collider kernel is launched),
  *   "k_sphere" (0 default: stiffness in N/m shared by the sphere colliders of tsl_set_spheres; negative or non-finite fails; with 0, or with no
  *   spheres, no sphere kernel is launched),
+ *   "k_capsule" (0 default: stiffness in N/m shared by the capsule colliders of tsl_set_capsules; negative or non-finite fails; with 0, or with no
+ *   capsules, no capsule kernel is launched),
  *   "cloth<i>.membrane" (0 default: edge springs Kl + area term Ka, as the reference; 1: a St. Venant-Kirchhoff membrane per face, A0 Psi(F) with
  *   F = [x1 - x0, x2 - x0] Dm^-1, Dm the rest triangle rebuilt from the face's rest lengths (fails naming a face whose lengths violate the triangle
  *   inequality), Psi = mu |E|^2 + lam/2 tr(E)^2, E = (F^T F - I) / 2, A0 the rest area; it replaces the springs and the area term of the cloth's
@@ -323,6 +325,59 @@ int tsl_set_sphere_centres(tsl_ctx* ctx, const double* centres_host, const doubl
 int tsl_sphere_count(tsl_ctx* ctx, int32_t* out_host);
 int tsl_sphere_force(tsl_ctx* ctx, const double* pos_dev, const double* prev_pos_dev, double* out_host);
 int tsl_sphere_grad(tsl_ctx* ctx, const double* pos_dev, const double* prev_pos_dev, const double* p_dev, double* out_host);
+
+/* Capsule colliders (no reference counterpart: its rods are meshed bodies): up to TSL_MAX_CAPSULES solid rods with round ends and the cloth outside.
+ * Capsule j has endpoints a_j, b_j that may be set before every step, previous endpoints ap_j, bp_j (where the rod was at the start of the step), a
+ * radius R_j > 0, fixed once the list is set, and a friction coefficient mu_j >= 0; the stiffness "k_capsule" of tsl_set_param is shared (0 by
+ * default: off), the thickness of the shell is eps_contact, the friction regularisation eh = eps_v dt.  A per-vertex 8-bit mask of its own says
+ * which capsules act on a vertex.  The endpoints are independent: the rod may translate, rotate and change its length.  For vertex v and capsule
+ * j, with x_prev the start-of-step positions (the prev_pos argument of tsl_energy / tsl_assemble; x_{s-1} in a reverse step):
+ *   e  = b - a,    s  = (x - a) . e / (e . e),           t  = clamp(s, 0, 1),   in  = [0 < s < 1],   u  = e / |e|
+ *   c  = a + t e,  q  = x - c,  rho = |q|,  n = q / rho,  d = rho - R
+ *   e0 = bp - ap,  s0 = (x_prev - ap) . e0 / (e0 . e0),  t0 = clamp(s0, 0, 1),  in0 = [0 < s0 < 1],  u0 = e0 / |e0|
+ *   c0 = ap + t0 e0,  q0 = x_prev - c0,  rho0, n0, d0 = rho0 - R
+ *   lam = mu k max(0, eps - d0),  D = (x - x_prev) - ((1 - t0)(a - ap) + t0 (b - bp)),  P0 = I - n0 n0^T,  w = P0 D,  r = |w|,  a1 = f1(r)
+ *   E = [d < eps] 1/2 k (d - eps)^2 + lam f0(r),  g = [d < eps] k (d - eps) n + lam a1 w,
+ *   H = H_n + lam M on the vertex's own diagonal block,  H_n = [d < eps] (k n n^T + k (d - eps) / rho (I - n n^T - in u u^T)),
+ *   M = a1 P0 + [r > 1e-9] (f2 / r) w w^T.
+ * The slip is relative to the material point of the rod under the vertex at the start of the step: a rod that turns drags the cloth differently
+ * along its length.  t0, n0 and lam are constants of the step.  tsl_assemble with spd = 0 (the reverse step's operator) adds H_n exact, every other
+ * mode, with and without "spd_literal", adds [d < eps] k n n^T (the eigen-clamp in closed form: the eigenvectors are n, u and n x u); lam M is
+ * positive semi-definite as it stands.  No constraint slot, no row list: the plans of the factorisation and tsl_contact_counts do not depend on
+ * capsules.  Nothing is stored per step.  A pair with rho < 1e-12 contributes nothing, one with rho0 < 1e-12 has no friction.  Frozen dofs follow
+ * the mask rule.  One lane per vertex, no atomics: the same bits run to run.  With no capsules or k_capsule = 0 every launch is the one it was.
+ *   tsl_set_capsules: a_host, b_host (n x 3 each), radii_host (n), mu_host (n), vertex_mask_host (tot_NV bytes, bit j: capsule j acts on the vertex;
+ *     NULL: every capsule on every vertex); host pointers, copied; ap := a, bp := b; the stream is synchronised; n = 0 removes the capsules.  Fails,
+ *     naming the offender, and leaves the previous list in place for more than TSL_MAX_CAPSULES capsules or n < 0, a non-finite endpoint, a segment
+ *     |b - a| shorter than 1e-9 m (a ball is what tsl_set_spheres is for), a radius that is not finite and positive, a negative or non-finite mu, a
+ *     mask byte that names a capsule at or above n.
+ *   tsl_set_capsule_ends: a_host, b_host and prev_a_host, prev_b_host (n x 3 each; both NULL: ap := a, bp := b; exactly one NULL fails) for the
+ *     next energy, assemble, step or adjoint step; set those of step s before the reverse step s and before tsl_capsule_grad.  A non-finite entry
+ *     or a segment or previous segment shorter than 1e-9 m fails, naming the capsule, and leaves all four in place.
+ *   tsl_capsule_count: n.
+ *   tsl_capsule_force: out_host (n x 6) at the state (pos, prev_pos): [0:3] -sum_v g_v of capsule j, the net force the rod applies to the cloth, in
+ *     the sign of tsl_sphere_force; [3:6] -sum_v (x_v - m) x g_v with m = (a + b) / 2, its torque about the rod's midpoint in the same sign; frozen
+ *     dofs are NOT masked; k_capsule = 0: zeros.
+ *   tsl_capsule_grad: out_host (n x 14) at the tape state (pos = x_s, prev_pos = x_{s-1}), sign of tsl_sphere_grad, p the adjoint solution on its
+ *     free dofs (p_dev == NULL: the solution of the last tsl_adjoint_step): the share of one reverse step in
+ *       [0:3]  d(loss)/d(a_j)  = -sum_v (dg/da)^T p_v,    dg/da = -(1 - t) H_n + phi' tau n^T - (1 - t0) lam M   (H_n exact),
+ *       [3:6]  d(loss)/d(b_j)  = -sum_v (dg/db)^T p_v,    dg/db = -t H_n - phi' tau n^T - t0 lam M,
+ *       [6:9]  d(loss)/d(ap_j) = -sum_v (dg/dap)^T p_v,   [9:12] d(loss)/d(bp_j) = -sum_v (dg/dbp)^T p_v,
+ *       [12]   d(loss)/d(mu_j) = -sum_v p_v . k max(0, eps - d0) a1 w,
+ *       [13]   d(loss)/d(R_j)  = -sum_v p_v . (-[d < eps] k n + [d0 < eps] mu k a1 w),
+ *     with phi' = [d < eps] k (d - eps), tau = in e / (e . e), tau0 = in0 e0 / (e0 . e0), Delta = (b - bp) - (a - ap), B = a1 I + [r > 1e-9] (f2 / r) w w^T,
+ *     J_n = -B ((n0 . D) I + n0 D^T), G0 = I - n0 n0^T - in0 u0 u0^T and
+ *       lagged(dd0, dn0, dt0, dD) = -[d0 < eps] mu k (a1 w) dd0^T + lam (M (dD - Delta dt0^T) + J_n dn0),
+ *       dg/dx_prev = lagged(n0, G0 / rho0, tau0, -I),
+ *       dg/dap = lagged(-(1 - t0) n0, -(1 - t0) G0 / rho0 + tau0 n0^T, in0 (-q0 - (1 - s0) e0) / (e0 . e0), (1 - t0) I),
+ *       dg/dbp = lagged(-t0 n0, -t0 G0 / rho0 - tau0 n0^T, in0 (q0 - s0 e0) / (e0 . e0), t0 I).
+ *     The reverse step itself adds -(dg/dx_prev)^T p_v to the free dofs of the vertex's row of pos_grad[s-1]. */
+#define TSL_MAX_CAPSULES 8
+int tsl_set_capsules(tsl_ctx* ctx, const double* a_host, const double* b_host, const double* radii_host, const double* mu_host, int32_t n, const uint8_t* vertex_mask_host);
+int tsl_set_capsule_ends(tsl_ctx* ctx, const double* a_host, const double* b_host, const double* prev_a_host, const double* prev_b_host);
+int tsl_capsule_count(tsl_ctx* ctx, int32_t* out_host);
+int tsl_capsule_force(tsl_ctx* ctx, const double* pos_dev, const double* prev_pos_dev, double* out_host);
+int tsl_capsule_grad(tsl_ctx* ctx, const double* pos_dev, const double* prev_pos_dev, const double* p_dev, double* out_host);
 
 /* BaseScene.compute_energy (BaseScene.py:427-451) at the given state, constraints as last detected. */
 int tsl_energy(tsl_ctx* ctx, const double* pos_dev, const double* prev_pos_dev, const double* vel_dev,

@@ -336,6 +336,54 @@ class TslContext:
         check(self.L.tsl_sphere_grad(self.h, _ptr(pos), _ptr(prev_pos), _ptr(p), out.ctypes.data), "tsl_sphere_grad")
         return out
 
+    # ---- capsule colliders (tsl_set_capsules; stiffness: set_param("k_capsule", k))
+    def set_capsules(self, ends_a, ends_b, radii, mu, vertex_mask=None):
+        """n solid rods with round ends (endpoints a_j, b_j, radius R_j, friction mu_j) with the cloth outside; vertex_mask (tot_NV,) uint8, bit j: capsule
+        j acts on the vertex, None: all on all; an empty list removes them.  The previous endpoints are set to the endpoints; the radii stay fixed."""
+        r = _np(radii, np.float64).reshape(-1)
+        n = len(r)
+        a = _np(ends_a, np.float64).reshape(-1, 3)
+        b = _np(ends_b, np.float64).reshape(-1, 3)
+        m = _np(mu, np.float64).reshape(-1)
+        assert a.shape == (n, 3) and b.shape == (n, 3) and m.shape == (n,), (a.shape, b.shape, r.shape, m.shape)
+        vm = None if vertex_mask is None else _np(vertex_mask, np.uint8).reshape(-1)
+        assert vm is None or vm.shape == (self.tot_NV,), vm.shape
+        check(self.L.tsl_set_capsules(self.h, a.ctypes.data if n else None, b.ctypes.data if n else None, r.ctypes.data if n else None,
+                                      m.ctypes.data if n else None, n, None if vm is None else vm.ctypes.data), "tsl_set_capsules")
+
+    def set_capsule_ends(self, ends_a, ends_b, prev_a=None, prev_b=None):
+        """the endpoints of the next energy / assembly / step / reverse step and where the rods were at the start of that step (both None: the endpoints)"""
+        n = self.capsule_count()
+        a = _np(ends_a, np.float64).reshape(-1, 3)
+        b = _np(ends_b, np.float64).reshape(-1, 3)
+        pa = None if prev_a is None else _np(prev_a, np.float64).reshape(-1, 3)
+        pb = None if prev_b is None else _np(prev_b, np.float64).reshape(-1, 3)
+        assert a.shape == (n, 3) and b.shape == (n, 3) and (pa is None or pa.shape == (n, 3)) and (pb is None or pb.shape == (n, 3)), (a.shape, b.shape, n)
+        if n:
+            check(self.L.tsl_set_capsule_ends(self.h, a.ctypes.data, b.ctypes.data, None if pa is None else pa.ctypes.data, None if pb is None else pb.ctypes.data),
+                  "tsl_set_capsule_ends")
+
+    def capsule_count(self):
+        out = C.c_int32(0)
+        check(self.L.tsl_capsule_count(self.h, C.byref(out)), "tsl_capsule_count")
+        return int(out.value)
+
+    def capsule_force(self, pos, prev_pos):
+        """(n, 6): [0:3] -sum_v g_v, the net force every rod applies to the cloth at the state (pos, prev_pos), [3:6] -sum_v (x_v - m) x g_v, its torque
+        about the rod's midpoint (frozen dofs not masked)"""
+        self.refresh_stream()
+        out = np.zeros((self.capsule_count(), 6))
+        check(self.L.tsl_capsule_force(self.h, _ptr(pos), _ptr(prev_pos), out.ctypes.data), "tsl_capsule_force")
+        return out
+
+    def capsule_grad(self, pos, prev_pos, p=None):
+        """(n, 14) contribution of one reverse step to d(loss)/d(a (3), b (3), previous a (3), previous b (3), mu, R) of every capsule at the tape state
+        (x_s, x_{s-1}) with the endpoints of step s in place; p None: the solution of the last adjoint_step, else a 3 * tot_NV device vector"""
+        self.refresh_stream()
+        out = np.zeros((self.capsule_count(), 14))
+        check(self.L.tsl_capsule_grad(self.h, _ptr(pos), _ptr(prev_pos), _ptr(p), out.ctypes.data), "tsl_capsule_grad")
+        return out
+
     # ---- engine calls
     def energy(self, pos, prev_pos, vel, ref_angle):
         self.refresh_stream()

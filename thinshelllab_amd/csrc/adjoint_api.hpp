@@ -97,6 +97,8 @@ static int adjoint_post(tsl_ctx* c, const AdjStep& t) {
   collider_backprop_launch(c, s, t.x_s, t.x_prev, c->pdir.p, t.pg_prev);
   // the spheres' lagged friction and lagged contact frame, likewise
   sphere_backprop_launch(c, s, t.x_s, t.x_prev, c->pdir.p, t.pg_prev);
+  // the capsules' lagged friction, lagged contact frame and lagged rod parameter, likewise
+  capsule_backprop_launch(c, s, t.x_s, t.x_prev, c->pdir.p, t.pg_prev);
   // get_prev_grad / get_prev_prev_grad
   hipLaunchKernelGGL(k_adj_prev, dim3(gsz(t.n3)), dim3(256), 0, s, NV, c->pdir.p, c->mass.p, c->frozen.p, c->dt, t.adj_damping, t.pg_prev, t.pg_prev2);
   HIP_OK(hipGetLastError());

@@ -15,6 +15,7 @@
 #include "../../include/tsl_hip.h"
 #include "collider_host.hpp"
 #include "sphere_host.hpp"
+#include "capsule_host.hpp"
 #include "k_body.hpp"
 #include "direct_plan.hpp"
 #include "scene_tables.hpp"   // ClothDev, ElasticDev (the per-cloth / per-body constants the kernels read) and the host tables of a scene
@@ -412,6 +413,12 @@ struct tsl_ctx {
   double k_sphere = 0.0;
   DevBuf<unsigned char> sph_mask;      // NV
   DevBuf<double> sph_part, sph_out;    // SPHERE_SLOTS per workgroup of 256 vertices; SPHERE_SLOTS
+  // ---- capsule colliders (tsl_set_capsules, k_capsule.hpp): the table (cap.n rods, endpoints and previous endpoints; its k, eps, eh are filled in per
+  // launch), the per-vertex mask, and the partials and the result of the read-outs.  The capsule kernels run while cap.n > 0 and k_capsule != 0
+  CapsuleTable cap{};
+  double k_capsule = 0.0;
+  DevBuf<unsigned char> cap_mask;      // NV
+  DevBuf<double> cap_part, cap_out;    // CAPSULE_SLOTS per workgroup of 256 vertices; CAPSULE_SLOTS
 
   // ---- multigrid preconditioner
   std::vector<MgCloth*> mg;

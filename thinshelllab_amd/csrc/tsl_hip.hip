@@ -55,6 +55,7 @@ static inline int gsz(size_t n) { size_t b = (n + 255) / 256; return (int)std::m
 #include "tie_api.hpp"
 #include "collider_api.hpp"
 #include "sphere_api.hpp"
+#include "capsule_api.hpp"
 #include "k_scene.hpp"
 
 // ------------------------------------------------------------------------------------------------
@@ -291,6 +292,10 @@ extern "C" int tsl_set_param(tsl_ctx* c, const char* key, double v) {
     if (!(v >= 0.0) || !std::isfinite(v)) return tsl_fail("tsl_set_param: k_sphere must be finite and >= 0 (got %g)", v);
     c->k_sphere = v;
   }
+  else if (k == "k_capsule") {
+    if (!(v >= 0.0) || !std::isfinite(v)) return tsl_fail("tsl_set_param: k_capsule must be finite and >= 0 (got %g)", v);
+    c->k_capsule = v;
+  }
   else if (k == "cg_tol") c->cg_tol = v;
   else if (k == "cg_maxit") c->cg_maxit = (int)v;
   else if (k == "newton_cap") c->newton_cap = (int)v;
@@ -371,8 +376,9 @@ static int energy_async(tsl_ctx* c, const double* pos, const double* prev, const
   const int nb5 = ties_on(c) ? nblk(c->n_tie, 64) : 0;          // ties: one partial per wave, behind the handle ones
   const int nb6 = colliders_on(c) ? collider_nblk(c) : 0;       // colliders: one partial per workgroup of 256 vertices, behind the tie ones
   const int nb7 = spheres_on(c) ? sphere_nblk(c) : 0;           // spheres: one partial per workgroup of 256 vertices, behind the collider ones
+  const int nb8 = capsules_on(c) ? capsule_nblk(c) : 0;         // capsules: likewise, behind the sphere ones
   const size_t n_part = (size_t)nb1 + (size_t)nblk(c->max_n_constraints, 64) + 1 + (size_t)nblk(c->n_handle, 256) + (size_t)nblk(c->n_tie, 64) + (size_t)(c->col.n > 0 ? collider_nblk(c) : 0) +
-                        (size_t)(c->sph.n > 0 ? sphere_nblk(c) : 0);
+                        (size_t)(c->sph.n > 0 ? sphere_nblk(c) : 0) + (size_t)(c->cap.n > 0 ? capsule_nblk(c) : 0);
   if (c->e_part.n < n_part) { if (c->e_part.alloc(n_part)) return -1; }
   if (c->n_stvk > 0) hipLaunchKernelGGL(k_energy_stvk, dim3(nb1), dim3(256), 0, s, vert_args(c), cloth_args(c), tet_args(c), pos, prev, vel, ref, c->e_part.p, stvk_args(c));
   else hipLaunchKernelGGL(k_energy, dim3(nb1), dim3(256), 0, s, vert_args(c), cloth_args(c), tet_args(c), pos, prev, vel, ref, c->e_part.p);
@@ -382,7 +388,8 @@ static int energy_async(tsl_ctx* c, const double* pos, const double* prev, const
   if (nb5 > 0) hipLaunchKernelGGL(k_tie_energy, dim3(nblk(c->n_tie, 256)), dim3(256), 0, s, tie_args(c), pos, c->e_part.p + nb1 + nb2 + nb3 + nb4);
   if (nb6 > 0) collider_energy_launch(c, s, pos, prev, c->e_part.p + nb1 + nb2 + nb3 + nb4 + nb5);
   if (nb7 > 0) sphere_energy_launch(c, s, pos, prev, c->e_part.p + nb1 + nb2 + nb3 + nb4 + nb5 + nb6);
-  hipLaunchKernelGGL(k_energy_final, dim3(1), dim3(256), 0, s, nb1 + nb2 + nb3 + nb4 + nb5 + nb6 + nb7, (const double*)c->e_part.p, &SC(c)->energy);
+  if (nb8 > 0) capsule_energy_launch(c, s, pos, prev, c->e_part.p + nb1 + nb2 + nb3 + nb4 + nb5 + nb6 + nb7);
+  hipLaunchKernelGGL(k_energy_final, dim3(1), dim3(256), 0, s, nb1 + nb2 + nb3 + nb4 + nb5 + nb6 + nb7 + nb8, (const double*)c->e_part.p, &SC(c)->energy);
   return 0;
 }
 static int energy_sync(tsl_ctx* c, const double* pos, const double* prev, const double* vel, const double* ref, double* E) {
@@ -460,6 +467,7 @@ static int assemble_enqueue(tsl_ctx* c, const double* pos, const double* prev, c
   handle_assemble_launch(c, s, pos, grad);
   collider_assemble_launch(c, s, pos, prev, grad);
   sphere_assemble_launch(c, s, spd, pos, prev, grad);
+  capsule_assemble_launch(c, s, spd, pos, prev, grad);
   if (grad) {
     if (c->n_cface) cloth_grad_face_launch(c, s, CA, pos);
     if (c->n_hinge) hipLaunchKernelGGL(k_cloth_grad_hinge, dim3(nblk(c->n_hinge, 256)), dim3(256), 0, s, CA, pos, ref);
@@ -534,6 +542,7 @@ static int assemble_enqueue_early(tsl_ctx* c, const double* pos, const double* p
   handle_assemble_launch(c, s, pos, grad);   // (on the stream of the vertex terms, in front of ev_fork: the gathers and masks of the other streams wait for it as they do for those)
   collider_assemble_launch(c, s, pos, prev, grad);
   sphere_assemble_launch(c, s, spd, pos, prev, grad);
+  capsule_assemble_launch(c, s, spd, pos, prev, grad);
   HIP_OK(hipEventRecord(c->ev_fork, s));   // normals, vertex gradient and mass diagonal are in place
   if (c->n_cface) {
     const int nq = (int)c->h_cloth.size() * 9;

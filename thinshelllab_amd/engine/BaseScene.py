@@ -210,6 +210,60 @@ def validate_spheres(tot_NV, centres, radii, mu, vertex_ids=None):
     return c.copy(), r.copy(), m.copy(), mask
 
 
+TSL_MAX_CAPSULES = 8
+CAPSULE_MIN_LEN = 1e-9
+
+
+def _capsule_ends_check(who, what, a, b, j):
+    """the message of csrc/capsule_host.hpp for the endpoints of capsule j (what: "" or "previous "), or None"""
+    for name, e in (("a", a), ("b", b)):
+        if not np.isfinite(e).all():
+            return f"{who}: {what}endpoint {name} ({e[0]:g}, {e[1]:g}, {e[2]:g}) of capsule {j} is not finite"
+    ln = float(np.sqrt(((b - a) ** 2).sum()))
+    if not ln >= CAPSULE_MIN_LEN:
+        return f"{who}: {what}segment of capsule {j} is {ln:g} m long: at least {CAPSULE_MIN_LEN:g} m"
+    return None
+
+
+def validate_capsules(tot_NV, ends_a, ends_b, radii, mu, vertex_ids=None):
+    """The checks of tsl_set_capsules on the host, with the messages of csrc/capsule_host.hpp: returns (a (n, 3), b (n, 3), radii (n), mu (n), uint8
+    mask (tot_NV)) or raises ValueError naming the offender -- more than TSL_MAX_CAPSULES capsules, a non-finite endpoint, a segment shorter than
+    1e-9 m, a radius that is not finite and positive, a negative or non-finite friction coefficient, a vertex id out of range.  vertex_ids None:
+    every capsule acts on every vertex; else one entry per capsule, None (all vertices) or a list of global vertex ids."""
+    r = np.asarray(radii, dtype=np.float64).reshape(-1)
+    n = len(r)
+    a = np.asarray(ends_a, dtype=np.float64).reshape(-1, 3) if n else np.zeros((0, 3))
+    b = np.asarray(ends_b, dtype=np.float64).reshape(-1, 3) if n else np.zeros((0, 3))
+    m = np.asarray(mu, dtype=np.float64).reshape(-1)
+    if a.shape != (n, 3) or b.shape != (n, 3) or m.shape != (n,):
+        raise ValueError(f"set_capsules: {len(a)} endpoints a, {len(b)} endpoints b and {m.size} friction coefficients for {n} radii")
+    if n > TSL_MAX_CAPSULES:
+        raise ValueError(f"set_capsules: {n} capsules: at most {TSL_MAX_CAPSULES}")
+    for j in range(n):
+        bad = _capsule_ends_check("set_capsules", "", a[j], b[j], j)
+        if bad:
+            raise ValueError(bad)
+        if not (np.isfinite(r[j]) and r[j] > 0.0):
+            raise ValueError(f"set_capsules: radius {r[j]:g} of capsule {j} is not finite and positive")
+        if not (m[j] >= 0.0 and np.isfinite(m[j])):
+            raise ValueError(f"set_capsules: friction coefficient {m[j]:g} of capsule {j} is negative or not finite")
+    mask = np.full(tot_NV, (1 << n) - 1, np.uint8)
+    if vertex_ids is not None:
+        if len(vertex_ids) != n:
+            raise ValueError(f"set_capsules: {len(vertex_ids)} vertex lists for {n} capsules")
+        mask[:] = 0
+        for j, ids in enumerate(vertex_ids):
+            if ids is None:
+                mask |= np.uint8(1 << j)
+                continue
+            v = np.asarray(ids, dtype=np.int64).reshape(-1)
+            for vi in v.tolist():
+                if vi < 0 or vi >= tot_NV:
+                    raise ValueError(f"set_capsules: vertex {vi} of capsule {j} out of range [0, {tot_NV})")
+            mask[v] |= np.uint8(1 << j)
+    return a.copy(), b.copy(), r.copy(), m.copy(), mask
+
+
 class _SystemMatrix:
     """Stand-in for ``SparseMatrix`` (sparse_solver.py): the matrix itself lives inside the context."""
 
@@ -291,6 +345,16 @@ class BaseScene:
         self._sph_mu = np.zeros(0)
         self._sph_mask = np.zeros(0, np.uint8)
         self.k_sphere = 0.0
+        # capsule colliders (set_capsules): _cap_e the endpoints (n, 2, 3) for the next step, _cap_ep those of the last completed step (where the rods are
+        # at the start of the next one), _cap_ep_step the previous endpoints that the last completed step used (the tape records it); radii, friction
+        # coefficients, the per-vertex mask and the stiffness k_capsule, kept here and pushed to the engine context lazily
+        self._cap_e = np.zeros((0, 2, 3))
+        self._cap_ep = np.zeros((0, 2, 3))
+        self._cap_ep_step = np.zeros((0, 2, 3))
+        self._cap_R = np.zeros(0)
+        self._cap_mu = np.zeros(0)
+        self._cap_mask = np.zeros(0, np.uint8)
+        self.k_capsule = 0.0
         # rigid frames of the handles (set_handle_frames): frame and local point of every handle, position and unit quaternion of every frame
         self._frame_of = np.zeros(0, np.int32)
         self._frame_local = np.zeros((0, 3))
@@ -572,6 +636,8 @@ class BaseScene:
                 self._push_colliders()
             if self.n_sphere:
                 self._push_spheres()
+            if self.n_capsule:
+                self._push_capsules()
             self._dirty.clear()
         if self._dirty:
             if "ties" in self._dirty:
@@ -584,6 +650,10 @@ class BaseScene:
                 self._push_spheres()
             elif "sphere_centres" in self._dirty:
                 self._ctx.set_sphere_centres(self._sph_c, self._sph_cp)
+            if "capsules" in self._dirty:
+                self._push_capsules()
+            elif "capsule_ends" in self._dirty:
+                self._ctx.set_capsule_ends(self._cap_e[:, 0], self._cap_e[:, 1], self._cap_ep[:, 0], self._cap_ep[:, 1])
             if "handles" in self._dirty:
                 self._push_handles()
             else:
@@ -829,6 +899,67 @@ class BaseScene:
             self._sph_cp = self._sph_c.copy()
             self._dirty.add("sphere_centres")
 
+    # ------------------------------------------------------------------ capsule colliders (no counterpart in the reference)
+    @property
+    def n_capsule(self):
+        return len(self._cap_R)
+
+    def set_capsules(self, ends_a, ends_b, radii, mu, k, vertex_ids=None):
+        """Up to 8 solid rods with round ends (endpoints a_j, b_j at least 1e-9 m apart, radius > 0, friction coefficient mu_j >= 0) with the cloth
+        outside and one stiffness k >= 0 in N/m: a finger, a rod the cloth is folded over, a roller of finite length, a bar that sweeps a sheet
+        (set_capsule_ends before every step; the two endpoints move independently).  The shell is eps_contact thick, the friction is regularised
+        with eps_v dt and acts on the slip relative to the rod's material point under the vertex.  vertex_ids None: every capsule acts on every
+        vertex; else one entry per capsule, None or a list of global vertex ids.  The rods start at rest (previous endpoints = endpoints); the radii
+        stay fixed; an empty list removes the capsules.  The lists are checked here, before any library call."""
+        a, b, r, m, mask = validate_capsules(self.tot_NV, ends_a, ends_b, radii, mu, vertex_ids)
+        k = float(k)
+        if not (k >= 0.0 and np.isfinite(k)):
+            raise ValueError(f"set_capsules: k_capsule must be finite and >= 0 (got {k:g})")
+        e = np.stack([a, b], axis=1)
+        self._cap_e, self._cap_ep, self._cap_ep_step = e, e.copy(), e.copy()
+        self._cap_R, self._cap_mu, self._cap_mask, self.k_capsule = r, m, mask, k
+        self._dirty.add("capsules")
+
+    def _check_ends(self, what, a, b):
+        a = np.asarray(a, dtype=np.float64).reshape(-1, 3)
+        b = np.asarray(b, dtype=np.float64).reshape(-1, 3)
+        if a.shape != (self.n_capsule, 3) or b.shape != (self.n_capsule, 3):
+            raise ValueError(f"set_capsule_ends: {len(a)} {what}endpoints a and {len(b)} {what}endpoints b for {self.n_capsule} capsules")
+        for j in range(len(a)):
+            bad = _capsule_ends_check("set_capsule_ends", what, a[j], b[j], j)
+            if bad:
+                raise ValueError(bad)
+        return np.stack([a, b], axis=1)
+
+    def set_capsule_ends(self, a, b, prev_a=None, prev_b=None):
+        """the endpoints a_j, b_j of the next step (or energy, assembly, reverse step).  Where the rods were at the start of that step is kept by the
+        scene: the endpoints of the last completed step.  prev_a and prev_b together override it (a tape puts a recorded step back; a caller
+        restarts a rollout); one without the other is refused."""
+        if (prev_a is None) != (prev_b is None):
+            raise ValueError("set_capsule_ends: previous endpoints " + ("a without previous endpoints b" if prev_b is None else "b without previous endpoints a"))
+        e = self._check_ends("", a, b)
+        if prev_a is not None:
+            self._cap_ep = self._check_ends("previous ", prev_a, prev_b)
+        self._cap_e = e
+        self._dirty.add("capsule_ends")
+
+    def capsule_force(self):
+        """(n, 6): the net force every rod applies to the cloth at the current positions and start-of-step positions, and its torque about the rod's
+        midpoint (a level rod under a resting cloth reads the weight it carries and how unevenly it carries it)"""
+        return self._ensure_ctx().capsule_force(self.pos.t, self.prev_pos.t)
+
+    def _push_capsules(self):
+        self._ctx.set_capsules(self._cap_e[:, 0], self._cap_e[:, 1], self._cap_R, self._cap_mu, self._cap_mask if self.n_capsule else None)
+        self._ctx.set_capsule_ends(self._cap_e[:, 0], self._cap_e[:, 1], self._cap_ep[:, 0], self._cap_ep[:, 1])
+        self._ctx.set_param("k_capsule", self.k_capsule)
+
+    def _capsules_step_done(self):
+        """a step is complete: its endpoints are where the rods are at the start of the next one"""
+        if self.n_capsule:
+            self._cap_ep_step = self._cap_ep
+            self._cap_ep = self._cap_e.copy()
+            self._dirty.add("capsule_ends")
+
     # ------------------------------------------------------------------ rigid frames for the handles (no counterpart in the reference)
     @property
     def n_frame(self):
@@ -957,6 +1088,7 @@ class BaseScene:
         ctx.set_param("contact", 0.0 if f_contact is None else 1.0)
         st = ctx.step(*self._state())
         self._spheres_step_done()
+        self._capsules_step_done()
         self.last_stats = st
         self.nc[None] = st["nc"]
         self.E[None] = st["energy"]

@@ -41,6 +41,26 @@ def handle_tape_init(grad, sys, T):
         grad.sphere_centres = Field(torch.zeros((T, grad.n_sphere, 3), dtype=torch.float64))
         grad.sphere_centres_prev = Field(torch.zeros((T, grad.n_sphere, 3), dtype=torch.float64))
         grad.sphere_grad = Field(torch.zeros((T, grad.n_sphere, 8), dtype=torch.float64))
+    # capsule colliders (BaseScene.set_capsules): the endpoints (a, b) and previous endpoints of every step and d(loss)/d(a, b, ap, bp, mu, R) per reverse step
+    grad.n_capsule = getattr(sys, "n_capsule", 0)
+    if grad.n_capsule:
+        grad.capsule_ends = Field(torch.zeros((T, grad.n_capsule, 2, 3), dtype=torch.float64))
+        grad.capsule_ends_prev = Field(torch.zeros((T, grad.n_capsule, 2, 3), dtype=torch.float64))
+        grad.capsule_grad = Field(torch.zeros((T, grad.n_capsule, 14), dtype=torch.float64))
+
+
+def capsule_end_grad(grad):
+    """(T, n, 2, 3) d(loss)/d(endpoint trajectory) when each step's previous endpoints were the endpoints of the step before: row s is
+    capsule_grad[s, :, 0:6] + capsule_grad[s + 1, :, 6:12].  Raises if the tape shows another trajectory."""
+    if not grad.n_capsule:
+        raise ValueError("capsule_end_grad: the scene has no capsules")
+    e, ep, g = grad.capsule_ends.t, grad.capsule_ends_prev.t, grad.capsule_grad.t
+    if not torch.equal(ep[1:], e[:-1]):
+        s = int((ep[1:] != e[:-1]).reshape(len(e) - 1, -1).any(dim=1).nonzero()[0, 0]) + 1
+        raise ValueError(f"capsule_end_grad: the previous endpoints of step {s} are not the endpoints of step {s - 1}")
+    out = g[:, :, 0:6].clone()
+    out[:-1] += g[1:, :, 6:12]
+    return out.reshape(len(g), -1, 2, 3)
 
 
 def sphere_centre_grad(grad):
@@ -67,6 +87,10 @@ def handle_tape_reset(grad):
         grad.sphere_centres.fill(0)
         grad.sphere_centres_prev.fill(0)
         grad.sphere_grad.fill(0)
+    if grad.n_capsule:
+        grad.capsule_ends.fill(0)
+        grad.capsule_ends_prev.fill(0)
+        grad.capsule_grad.fill(0)
     if grad.n_handle:
         grad.handle_targets.fill(0)
         grad.handle_grad.fill(0)
@@ -88,6 +112,9 @@ def handle_tape_record(grad, sys, step):
     if grad.n_sphere:   # the step just completed: its centres, and where the balls were when it started
         grad.sphere_centres.t[step] = torch.as_tensor(sys._sph_cp)
         grad.sphere_centres_prev.t[step] = torch.as_tensor(sys._sph_cp_step)
+    if grad.n_capsule:   # likewise: the endpoints of the step just completed, and where the rods were when it started
+        grad.capsule_ends.t[step] = torch.as_tensor(sys._cap_ep)
+        grad.capsule_ends_prev.t[step] = torch.as_tensor(sys._cap_ep_step)
 
 
 def handle_tape_push(grad, sys, step):
@@ -101,6 +128,9 @@ def handle_tape_push(grad, sys, step):
         sys.set_collider_offsets(grad.collider_offsets.t[step].numpy())
     if grad.n_sphere:   # the centres and previous centres of step `step`: the reverse step evaluates the contact frame with them
         sys.set_sphere_centres(grad.sphere_centres.t[step].numpy(), grad.sphere_centres_prev.t[step].numpy())
+    if grad.n_capsule:   # the endpoints and previous endpoints of step `step`: the reverse step evaluates t0, the contact frame and the slip with them
+        e, ep = grad.capsule_ends.t[step].numpy(), grad.capsule_ends_prev.t[step].numpy()
+        sys.set_capsule_ends(e[:, 0], e[:, 1], ep[:, 0], ep[:, 1])
 
 
 def handle_tape_pull(grad, ctx, step):
@@ -115,6 +145,8 @@ def handle_tape_pull(grad, ctx, step):
         grad.collider_grad.t[step] += torch.as_tensor(ctx.collider_grad(grad.pos_buffer.t[step], grad.pos_buffer.t[step - 1]))
     if grad.n_sphere:   # sphere_grad[step] += d(loss)/d(c, cp of step `step`, mu, R) of the reverse step just taken, at the tape state (x_step, x_{step-1})
         grad.sphere_grad.t[step] += torch.as_tensor(ctx.sphere_grad(grad.pos_buffer.t[step], grad.pos_buffer.t[step - 1]))
+    if grad.n_capsule:   # capsule_grad[step] += d(loss)/d(a, b, ap, bp of step `step`, mu, R) of the reverse step just taken, at the tape state (x_step, x_{step-1})
+        grad.capsule_grad.t[step] += torch.as_tensor(ctx.capsule_grad(grad.pos_buffer.t[step], grad.pos_buffer.t[step - 1]))
 
 
 class Grad:
@@ -161,6 +193,10 @@ class Grad:
     def sphere_centre_grad(self):
         """(T, n, 3) d(loss)/d(centre trajectory of the spheres); raises if a step's previous centres were not the centres of the step before"""
         return sphere_centre_grad(self)
+
+    def capsule_end_grad(self):
+        """(T, n, 2, 3) d(loss)/d(endpoint trajectory of the capsules); raises if a step's previous endpoints were not the endpoints of the step before"""
+        return capsule_end_grad(self)
 
     # :37-51
     def copy_pos(self, sys, step):

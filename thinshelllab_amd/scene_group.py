@@ -64,6 +64,7 @@ class SceneGroup:
         for s, r in zip(self.scenes, st):
             d = r.as_dict()
             s._spheres_step_done()
+            s._capsules_step_done()
             s.last_stats = d
             s.nc[None] = d["nc"]
             s.E[None] = d["energy"]
