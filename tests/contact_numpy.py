@@ -111,9 +111,16 @@ def _unit(j, xp):
 
 def normal_part(xp, X, sc=SC, dec=None):
     """(d, active, energy, g9, H9) of the normal part in the relative coordinates (a, b, p); g9, H9 zero where the slot is off"""
-    a, b, p = _sub(X[1], X[0]), _sub(X[2], X[0]), _sub(X[3], X[0])
+    return normal_part_q(xp, _sub(X[1], X[0]), _sub(X[2], X[0]), _sub(X[3], X[0]), sc, dec)
+
+
+def normal_part_q(xp, a, b, p, sc=SC, dec=None):
+    """normal_part from the relative coordinates themselves (the edge-edge slot of tests/ee_elements_numpy.py has others).  Rule for C == 0 exactly (a x b
+    zero bit for bit: edges that are exactly parallel): d = 0 / 0 compares false with eps, the normal part is off and no decision is recorded"""
     cr = _cross(a, b)
     C, D = _norm(xp, cr), _dot(cr, p)
+    if C == 0:
+        return xp.num(float("nan")), False, xp.num(0), [xp.num(0)] * 9, _z(xp, 9, 9)
     d, eps, kc = D / C, xp.num(sc.eps), xp.num(sc.k_contact)
     if dec is not None:
         dec.append(("active", d / eps - 1))
@@ -193,10 +200,16 @@ def to12(xp, g9, H9):
 
 def friction_part(xp, X, rec, sc=SC, spd=0, dec=None):
     """dict(r, u, f1, e, g1 (3: k f1 T^T u), h1 (3 x 3: k T^T core T), w1): the friction term of a slot with its records as data"""
-    w, T, dx0, k = _V(xp, rec["w"]), _V(xp, rec["T"]), _V(xp, rec["dx0"]), xp.num(rec["k"])
-    eh = xp.num(sc.eh)
+    w, dx0 = _V(xp, rec["w"]), _V(xp, rec["dx0"])
     xc = [X[0][j] * w[0] + X[1][j] * w[1] + X[2][j] * w[2] for j in range(3)]
     dx = [X[3][j] - xc[j] - dx0[j] for j in range(3)]
+    return friction_core(xp, dx, [-w[0], -w[1], -w[2], xp.num(1)], rec, sc, spd, dec)
+
+
+def friction_core(xp, dx, w1, rec, sc=SC, spd=0, dec=None):
+    """friction_part from the lagged slip dx and the weights w1 of the four vertices in it"""
+    T, k = _V(xp, rec["T"]), xp.num(rec["k"])
+    eh = xp.num(sc.eh)
     u = [T[0] * dx[0] + T[1] * dx[1] + T[2] * dx[2], T[3] * dx[0] + T[4] * dx[1] + T[5] * dx[2]]
     r = xp.sqrt(u[0] * u[0] + u[1] * u[1])
     if dec is not None:
@@ -211,7 +224,7 @@ def friction_part(xp, X, rec, sc=SC, spd=0, dec=None):
     g1 = [k * v1 * (u[0] * T[j] + u[1] * T[3 + j]) for j in range(3)]
     h1 = [[k * (T[a] * (core[0][0] * T[b] + core[0][1] * T[3 + b]) + T[3 + a] * (core[1][0] * T[b] + core[1][1] * T[3 + b])) for b in range(3)]
           for a in range(3)]
-    return dict(r=r, u=u, f1=v1, e=k * f0(xp, r, eh), g1=g1, h1=h1, w1=[-w[0], -w[1], -w[2], xp.num(1)], tu=[v1 * (u[0] * T[j] + u[1] * T[3 + j]) for j in range(3)])
+    return dict(r=r, u=u, f1=v1, e=k * f0(xp, r, eh), g1=g1, h1=h1, w1=w1, tu=[v1 * (u[0] * T[j] + u[1] * T[3 + j]) for j in range(3)])
 
 
 def slot_eval(xp, X, rec, sc=SC, spd=0, dec=None):
@@ -645,9 +658,19 @@ def _back(a, R):
     return out
 
 
-def f64_copies(X, rec, spd, z=None, n_jit=8):
+class _VertexTriangle:
+    """the slot functions of this module, looked up when called (a test may patch them); tests/ee_elements_numpy.py has the edge-edge ones"""
+    slot_eval = staticmethod(lambda *a, **k: slot_eval(*a, **k))
+    slot_reverse = staticmethod(lambda *a, **k: slot_reverse(*a, **k))
+
+
+VT = _VertexTriangle()
+
+
+def f64_copies(X, rec, spd, z=None, n_jit=8, model=VT, jitter=jitters):
     """the float64 restatement of one slot at the state, its six coordinate rotations (records turned with it) and n_jit copies with every coordinate
-    moved by one ulp; arrays turned back"""
+    moved by one ulp (jitter: the one-ulp moves of a state whose construction fixes an exact outcome, which they must keep); arrays turned back"""
+    slot_eval, slot_reverse = model.slot_eval, model.slot_reverse
     out = []
     with np.errstate(all="ignore"):
         for R in rotations():
@@ -655,7 +678,7 @@ def f64_copies(X, rec, spd, z=None, n_jit=8):
             if z is not None:
                 ev.update(slot_reverse(F64, X @ R.T, _rot_rec(rec, R), (np.asarray(z).reshape(4, 3) @ R.T).ravel()))
             out.append(_back(_arr(ev), R))
-        for Xj in jitters(X, n=n_jit, seed=int(abs(X).sum() * 1e9) % 1000):
+        for Xj in jitter(X, n=n_jit, seed=int(abs(X).sum() * 1e9) % 1000):
             ev = slot_eval(F64, Xj, rec, SC, spd)
             if z is not None:
                 ev.update(slot_reverse(F64, Xj, rec, z))
@@ -675,8 +698,9 @@ def _bnd(e64, norm, extra=0.0):
 class SlotRef:
     """mp values (as (hi, lo)), bounds of one slot at one state under one spd: E, Eb; g, gb (4); H, Hb (4, 4); with z: acc, accb (4), fg, fgb (4, 3 per dof);
     gn1, gf1 with their bounds per vertex (for the key sums); f64: the copies (for the harness)"""
-    def __init__(self, X, rec, spd, z=None):
+    def __init__(self, X, rec, spd, z=None, model=VT, jitter=jitters):
         X = np.asarray(X, float)
+        slot_eval, slot_reverse = model.slot_eval, model.slot_reverse
         with mp.workdps(50):
             ev = slot_eval(MP, X, rec, SC, spd)
             if z is not None:
@@ -687,7 +711,7 @@ class SlotRef:
             if spd:
                 un = _arr(slot_eval(MP, X, rec, SC, 0))
                 hl_un = split(un["H"])
-        self.f64 = f64_copies(X, rec, spd, z)
+        self.f64 = f64_copies(X, rec, spd, z, 8, model, jitter)
         e = lambda q, axes: np.max([_fn(diff(c[q], self.hl[q]), axes) for c in self.f64], axis=0)
         self.Eb = float(_bnd(e("E", None), abs(self.hl["E"][0])))
         for q in ("g", "gn1", "gf1") + (("acc",) if z is not None else ()):
@@ -696,7 +720,7 @@ class SlotRef:
             self.fgb = _bnd(np.max([np.abs(diff(c["fg"], self.hl["fg"])) for c in self.f64], axis=0), np.abs(self.hl["fg"][0]))
         nH = _fn(self.hl["H"][0], (1, 3))
         if spd:   # projected: every sub-block takes the whole block's float64 error (projected, and unprojected: the projection is non-expansive) + 64 u |block|
-            f_un = f64_copies(X, rec, 0, None, n_jit=2)
+            f_un = f64_copies(X, rec, 0, None, n_jit=2, model=model, jitter=jitter)
             whole = max(float(e("H", None)), max(float(_fn(diff(c["H"], hl_un))) for c in f_un))
             self.Hb = _bnd(np.full((4, 4), whole), nH, 64 * U * float(_fn(hl_un[0])))
         else:
@@ -709,11 +733,13 @@ def dofs(vs):
 
 class Expected:
     """what an assembly of `cons` (float records as ctx.constraints() returns them) at `pos` must give under `spd` and the frozen dofs"""
-    def __init__(self, cons, pos, spd, frozen=None, z=None):
+    def __init__(self, cons, pos, spd, frozen=None, z=None, model=VT, jitter=jitters):
+        """model: the slot functions, or one per slot (vertex-triangle slots in front of edge-edge ones)"""
         pos = np.asarray(pos, float).reshape(-1, 3)
+        models = model if isinstance(model, (list, tuple)) else [model] * len(cons["k"])
         self.cons, self.nv, self.spd = cons, len(pos), spd
         self.frozen = np.zeros(3 * self.nv, bool) if frozen is None else np.asarray(frozen, bool)
-        self.slots = [SlotRef(pos[cons["idx"][s]], slot_rec(cons, s), spd, None if z is None else np.asarray(z).reshape(-1, 3)[cons["idx"][s]].ravel())
+        self.slots = [SlotRef(pos[cons["idx"][s]], slot_rec(cons, s), spd, None if z is None else np.asarray(z).reshape(-1, 3)[cons["idx"][s]].ravel(), models[s], jitter)
                       for s in range(len(cons["k"]))]
 
 
@@ -726,10 +752,12 @@ def worst_ratio(err, bnd, tag=""):
     return float((err[on] / bnd[on]).max()) if on.any() else 0.0
 
 
-def check_assembly(exp, got, R, tag, frozen=None):
+def check_assembly(exp, got, R, tag, frozen=None, static_diag=0.0):
     """got: dict(blocks (S, 12, 12) unmasked, masked (S, 12, 12), g (nv, 3) gradient or None, op (3 nv, 3 nv) dense contact part of the operator, E or None).
     Per slot and 3 x 3 sub-block, per vertex and per vertex pair against mp; masked blocks exactly zero on frozen rows and columns; nothing
-    outside the slots' pairs; spd: every block PSD to 64 u |block|"""
+    outside the slots' pairs; spd: every block PSD to 64 u |block|.  static_diag: got["op"] came out of a float64 sum with a static diagonal of that value and
+    its exact subtraction (operator_csr() - matrix_csr()): a pair (v, v) then takes the sum of the two terms' bounds, the static one with e64 = 0 (as the
+    inertia term of pos_grad[1]); it shows only where a slot's weight on v is tiny (an edge-edge slot with its closest point 1e-6 from an end)"""
     cons, nv = exp.cons, exp.nv
     fz = np.zeros(3 * nv, bool) if frozen is None else np.asarray(frozen, bool)
     S = len(exp.slots)
@@ -769,6 +797,7 @@ def check_assembly(exp, got, R, tag, frozen=None):
         O = np.asarray(got["op"]).reshape(nv, 3, nv, 3)
         assert not O.transpose(0, 2, 1, 3)[~pat].any(), (tag, "operator has entries outside the slots' vertex pairs")
         eo = _fn(diff(O, osum), (1, 3))
+        ob = ob + np.eye(nv) * float(_bnd(0.0, np.sqrt(3.0) * static_diag))
         R.add("operator", worst_ratio(eo[pat], ob[pat], tag), 1.0)
     if got.get("E") is not None:
         with mp.workdps(50):

@@ -1,7 +1,11 @@
 """Edge-edge contact, the context key "contact_ee" (include/tsl_hip.h, csrc/k_contact.hpp).  The reference has vertex-triangle contact only,
 so the new term is checked against a NumPy restatement (tests/ee_numpy.py), brute-force detection and finite differences, not against the
 oracle.  The scene is two diamond-section bars crossing ridge over ridge (no vertex over the other ridge): vertex-triangle contact sees
-nothing there while the ridges pass through each other."""
+nothing there while the ridges pass through each other.
+
+These tests hold the mode as a whole: the key, detection against a brute-force search, pass-through, rollout differences, solvers, groups.  The kernels
+alone -- records, blocks per 3 x 3 sub-block, the 9 -> 12 row map, launch edges, slot offsets, the frozen mask, the reverse step -- are held against an
+mpmath restatement at the bound of the other element kernels by tests/test_gpu_ee_elements.py (tests/ee_elements_numpy.py)."""
 import ctypes as C
 import os
 import sys
