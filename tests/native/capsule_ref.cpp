@@ -16,7 +16,7 @@ static void show(const char* name, const std::vector<T>& a) {
 }
 static std::vector<double> table(const CapsuleTable& S) {
   std::vector<double> t;
-  for (int j = 0; j < S.n; j++) t.insert(t.end(), S.cp[j], S.cp[j] + 14);
+  for (int j = 0; j < S.n; j++) t.insert(t.end(), S.row[j], S.row[j] + 14);
   return t;
 }
 
@@ -99,17 +99,17 @@ int main() {
   }
   // masks: the default, a given one, a bit at or above n
   std::vector<uint8_t> mask, mask0;
-  if (capsule_mask_validate(NV, 3, nullptr, mask, err)) { printf("unexpected: %s\n", err.c_str()); return 1; }
+  if (shape_mask_validate("capsule", NV, 3, nullptr, mask, err)) { printf("unexpected: %s\n", err.c_str()); return 1; }
   show("mask_all", mask);
   mask0 = mask;
   std::vector<uint8_t> given(NV, 5); given[7] = 0; given[9] = 8;
   err.clear();
-  printf("refused: %s\n", capsule_mask_validate(NV, 3, given.data(), mask, err) ? err.c_str() : "NOT REFUSED");
+  printf("refused: %s\n", shape_mask_validate("capsule", NV, 3, given.data(), mask, err) ? err.c_str() : "NOT REFUSED");
   kept &= (mask == mask0);
   given[9] = 2;
-  if (capsule_mask_validate(NV, 3, given.data(), mask, err)) { printf("unexpected: %s\n", err.c_str()); return 1; }
+  if (shape_mask_validate("capsule", NV, 3, given.data(), mask, err)) { printf("unexpected: %s\n", err.c_str()); return 1; }
   show("mask_given", mask);
-  if (capsule_mask_validate(NV, 8, nullptr, mask, err)) { printf("unexpected: %s\n", err.c_str()); return 1; }
+  if (shape_mask_validate("capsule", NV, 8, nullptr, mask, err)) { printf("unexpected: %s\n", err.c_str()); return 1; }
   show("mask_eight", mask);
   // no capsules: valid, an empty table
   CapsuleTable E{};

@@ -16,7 +16,7 @@ static void show(const char* name, const std::vector<T>& a) {
 }
 static std::vector<double> table(const ColliderPlanes& P) {
   std::vector<double> t;
-  for (int j = 0; j < P.n; j++) t.insert(t.end(), P.pl[j], P.pl[j] + 11);
+  for (int j = 0; j < P.n; j++) t.insert(t.end(), P.row[j], P.row[j] + 11);
   return t;
 }
 
@@ -72,25 +72,25 @@ int main() {
   }
   // masks: the default, a given one, a bit at or above n; vertex lists, an id out of range
   std::vector<uint8_t> mask, mask0;
-  if (collider_mask_validate(NV, 3, nullptr, mask, err)) { printf("unexpected: %s\n", err.c_str()); return 1; }
+  if (shape_mask_validate("collider", NV, 3, nullptr, mask, err)) { printf("unexpected: %s\n", err.c_str()); return 1; }
   show("mask_all", mask);
   mask0 = mask;
   std::vector<uint8_t> given(NV, 5); given[7] = 0; given[9] = 8;
   err.clear();
-  printf("refused: %s\n", collider_mask_validate(NV, 3, given.data(), mask, err) ? err.c_str() : "NOT REFUSED");
+  printf("refused: %s\n", shape_mask_validate("collider", NV, 3, given.data(), mask, err) ? err.c_str() : "NOT REFUSED");
   kept &= (mask == mask0);
   given[9] = 2;
-  if (collider_mask_validate(NV, 3, given.data(), mask, err)) { printf("unexpected: %s\n", err.c_str()); return 1; }
+  if (shape_mask_validate("collider", NV, 3, given.data(), mask, err)) { printf("unexpected: %s\n", err.c_str()); return 1; }
   show("mask_given", mask);
   const std::vector<int32_t> ptr = {0, 3, 3, 5};
   std::vector<int32_t> ids = {0, 19, 4, 4, 5};
-  if (collider_mask_from_ids(NV, 3, ptr.data(), ids.data(), mask, err)) { printf("unexpected: %s\n", err.c_str()); return 1; }
+  if (shape_mask_from_ids("collider", NV, 3, ptr.data(), ids.data(), mask, err)) { printf("unexpected: %s\n", err.c_str()); return 1; }
   show("mask_ids", mask);
   mask0 = mask;
   for (int32_t wrong : {NV, -1}) {
     ids[4] = wrong;
     err.clear();
-    printf("refused: %s\n", collider_mask_from_ids(NV, 3, ptr.data(), ids.data(), mask, err) ? err.c_str() : "NOT REFUSED");
+    printf("refused: %s\n", shape_mask_from_ids("collider", NV, 3, ptr.data(), ids.data(), mask, err) ? err.c_str() : "NOT REFUSED");
     kept &= (mask == mask0);
   }
   // no colliders: valid, an empty table

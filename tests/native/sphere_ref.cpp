@@ -16,7 +16,7 @@ static void show(const char* name, const std::vector<T>& a) {
 }
 static std::vector<double> table(const SphereTable& S) {
   std::vector<double> t;
-  for (int j = 0; j < S.n; j++) t.insert(t.end(), S.sp[j], S.sp[j] + 8);
+  for (int j = 0; j < S.n; j++) t.insert(t.end(), S.row[j], S.row[j] + 8);
   return t;
 }
 
@@ -81,27 +81,27 @@ int main() {
   }
   // masks: the default, a given one, a bit at or above n; vertex lists, an id out of range
   std::vector<uint8_t> mask, mask0;
-  if (sphere_mask_validate(NV, 3, nullptr, mask, err)) { printf("unexpected: %s\n", err.c_str()); return 1; }
+  if (shape_mask_validate("sphere", NV, 3, nullptr, mask, err)) { printf("unexpected: %s\n", err.c_str()); return 1; }
   show("mask_all", mask);
   mask0 = mask;
   std::vector<uint8_t> given(NV, 5); given[7] = 0; given[9] = 8;
   err.clear();
-  printf("refused: %s\n", sphere_mask_validate(NV, 3, given.data(), mask, err) ? err.c_str() : "NOT REFUSED");
+  printf("refused: %s\n", shape_mask_validate("sphere", NV, 3, given.data(), mask, err) ? err.c_str() : "NOT REFUSED");
   kept &= (mask == mask0);
   given[9] = 2;
-  if (sphere_mask_validate(NV, 3, given.data(), mask, err)) { printf("unexpected: %s\n", err.c_str()); return 1; }
+  if (shape_mask_validate("sphere", NV, 3, given.data(), mask, err)) { printf("unexpected: %s\n", err.c_str()); return 1; }
   show("mask_given", mask);
-  if (sphere_mask_validate(NV, 8, nullptr, mask, err)) { printf("unexpected: %s\n", err.c_str()); return 1; }
+  if (shape_mask_validate("sphere", NV, 8, nullptr, mask, err)) { printf("unexpected: %s\n", err.c_str()); return 1; }
   show("mask_eight", mask);
   const std::vector<int32_t> ptr = {0, 3, 3, 5};
   std::vector<int32_t> ids = {0, 19, 4, 4, 5};
-  if (sphere_mask_from_ids(NV, 3, ptr.data(), ids.data(), mask, err)) { printf("unexpected: %s\n", err.c_str()); return 1; }
+  if (shape_mask_from_ids("sphere", NV, 3, ptr.data(), ids.data(), mask, err)) { printf("unexpected: %s\n", err.c_str()); return 1; }
   show("mask_ids", mask);
   mask0 = mask;
   for (int32_t wrong : {NV, -1}) {
     ids[4] = wrong;
     err.clear();
-    printf("refused: %s\n", sphere_mask_from_ids(NV, 3, ptr.data(), ids.data(), mask, err) ? err.c_str() : "NOT REFUSED");
+    printf("refused: %s\n", shape_mask_from_ids("sphere", NV, 3, ptr.data(), ids.data(), mask, err) ? err.c_str() : "NOT REFUSED");
     kept &= (mask == mask0);
   }
   // no spheres: valid, an empty table

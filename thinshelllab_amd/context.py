@@ -253,6 +253,24 @@ class TslContext:
         check(self.L.tsl_tie_grad(self.h, _ptr(pos), _ptr(p), out.ctypes.data), "tsl_tie_grad")
         return out
 
+    # ---- what the three collider kinds share: kind is "collider", "sphere" or "capsule"
+    def _shape_count(self, kind):
+        out = C.c_int32(0)
+        check(getattr(self.L, f"tsl_{kind}_count")(self.h, C.byref(out)), f"tsl_{kind}_count")
+        return int(out.value)
+
+    def _shape_force(self, kind, per, pos, prev_pos):
+        self.refresh_stream()
+        out = np.zeros((self._shape_count(kind), per))
+        check(getattr(self.L, f"tsl_{kind}_force")(self.h, _ptr(pos), _ptr(prev_pos), out.ctypes.data), f"tsl_{kind}_force")
+        return out
+
+    def _shape_grad(self, kind, per, pos, prev_pos, p):
+        self.refresh_stream()
+        out = np.zeros((self._shape_count(kind), per))
+        check(getattr(self.L, f"tsl_{kind}_grad")(self.h, _ptr(pos), _ptr(prev_pos), _ptr(p), out.ctypes.data), f"tsl_{kind}_grad")
+        return out
+
     # ---- half-space colliders (tsl_set_colliders; stiffness: set_param("k_collider", k))
     def set_colliders(self, normals, offsets, mu, vertex_mask=None):
         """n half-spaces n_j . x < o_j with friction mu_j; vertex_mask (tot_NV,) uint8, bit j: collider j acts on the vertex, None: all on all; an empty
@@ -274,24 +292,16 @@ class TslContext:
             check(self.L.tsl_set_collider_offsets(self.h, o.ctypes.data), "tsl_set_collider_offsets")
 
     def collider_count(self):
-        out = C.c_int32(0)
-        check(self.L.tsl_collider_count(self.h, C.byref(out)), "tsl_collider_count")
-        return int(out.value)
+        return self._shape_count("collider")
 
     def collider_force(self, pos, prev_pos):
         """(n, 3) -sum_v g_v: the net force every plane applies to the cloth at the state (pos, prev_pos) (frozen dofs not masked)"""
-        self.refresh_stream()
-        out = np.zeros((self.collider_count(), 3))
-        check(self.L.tsl_collider_force(self.h, _ptr(pos), _ptr(prev_pos), out.ctypes.data), "tsl_collider_force")
-        return out
+        return self._shape_force("collider", 3, pos, prev_pos)
 
     def collider_grad(self, pos, prev_pos, p=None):
         """(n, 2) contribution of one reverse step to d(loss)/d(offset) and d(loss)/d(mu) of every collider at the tape state (x_s, x_{s-1}) with the
         offsets of step s in place; p None: the solution of the last adjoint_step, else a 3 * tot_NV device vector"""
-        self.refresh_stream()
-        out = np.zeros((self.collider_count(), 2))
-        check(self.L.tsl_collider_grad(self.h, _ptr(pos), _ptr(prev_pos), _ptr(p), out.ctypes.data), "tsl_collider_grad")
-        return out
+        return self._shape_grad("collider", 2, pos, prev_pos, p)
 
     # ---- sphere colliders (tsl_set_spheres; stiffness: set_param("k_sphere", k))
     def set_spheres(self, centres, radii, mu, vertex_mask=None):
@@ -317,24 +327,16 @@ class TslContext:
             check(self.L.tsl_set_sphere_centres(self.h, ce.ctypes.data, None if cp is None else cp.ctypes.data), "tsl_set_sphere_centres")
 
     def sphere_count(self):
-        out = C.c_int32(0)
-        check(self.L.tsl_sphere_count(self.h, C.byref(out)), "tsl_sphere_count")
-        return int(out.value)
+        return self._shape_count("sphere")
 
     def sphere_force(self, pos, prev_pos):
         """(n, 3) -sum_v g_v: the net force every ball applies to the cloth at the state (pos, prev_pos) (frozen dofs not masked)"""
-        self.refresh_stream()
-        out = np.zeros((self.sphere_count(), 3))
-        check(self.L.tsl_sphere_force(self.h, _ptr(pos), _ptr(prev_pos), out.ctypes.data), "tsl_sphere_force")
-        return out
+        return self._shape_force("sphere", 3, pos, prev_pos)
 
     def sphere_grad(self, pos, prev_pos, p=None):
         """(n, 8) contribution of one reverse step to d(loss)/d(centre (3), previous centre (3), mu, R) of every sphere at the tape state (x_s, x_{s-1}) with
         the centres of step s in place; p None: the solution of the last adjoint_step, else a 3 * tot_NV device vector"""
-        self.refresh_stream()
-        out = np.zeros((self.sphere_count(), 8))
-        check(self.L.tsl_sphere_grad(self.h, _ptr(pos), _ptr(prev_pos), _ptr(p), out.ctypes.data), "tsl_sphere_grad")
-        return out
+        return self._shape_grad("sphere", 8, pos, prev_pos, p)
 
     # ---- capsule colliders (tsl_set_capsules; stiffness: set_param("k_capsule", k))
     def set_capsules(self, ends_a, ends_b, radii, mu, vertex_mask=None):
@@ -364,25 +366,17 @@ class TslContext:
                   "tsl_set_capsule_ends")
 
     def capsule_count(self):
-        out = C.c_int32(0)
-        check(self.L.tsl_capsule_count(self.h, C.byref(out)), "tsl_capsule_count")
-        return int(out.value)
+        return self._shape_count("capsule")
 
     def capsule_force(self, pos, prev_pos):
         """(n, 6): [0:3] -sum_v g_v, the net force every rod applies to the cloth at the state (pos, prev_pos), [3:6] -sum_v (x_v - m) x g_v, its torque
         about the rod's midpoint (frozen dofs not masked)"""
-        self.refresh_stream()
-        out = np.zeros((self.capsule_count(), 6))
-        check(self.L.tsl_capsule_force(self.h, _ptr(pos), _ptr(prev_pos), out.ctypes.data), "tsl_capsule_force")
-        return out
+        return self._shape_force("capsule", 6, pos, prev_pos)
 
     def capsule_grad(self, pos, prev_pos, p=None):
         """(n, 14) contribution of one reverse step to d(loss)/d(a (3), b (3), previous a (3), previous b (3), mu, R) of every capsule at the tape state
         (x_s, x_{s-1}) with the endpoints of step s in place; p None: the solution of the last adjoint_step, else a 3 * tot_NV device vector"""
-        self.refresh_stream()
-        out = np.zeros((self.capsule_count(), 14))
-        check(self.L.tsl_capsule_grad(self.h, _ptr(pos), _ptr(prev_pos), _ptr(p), out.ctypes.data), "tsl_capsule_grad")
-        return out
+        return self._shape_grad("capsule", 14, pos, prev_pos, p)
 
     # ---- engine calls
     def energy(self, pos, prev_pos, vel, ref_angle):

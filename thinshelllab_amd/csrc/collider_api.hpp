@@ -1,95 +1,211 @@
-// Host side of the half-space colliders inside libtsl_hip.so: the entry points tsl_set_colliders .. tsl_collider_grad of include/tsl_hip.h and, for
-// the launch sites of tsl_hip.hip and adjoint_api.hpp, the kernel arguments and the launches of an assembly, an energy and a reverse step
-// (k_collider.hpp).  Included by tsl_hip.hip behind its helpers (tsl_fail, TSL_TRY, HIP_OK, Scope, nblk), the way handle_api.hpp is;
-// the list checks and the plane table are in collider_host.hpp, which has no device code.
+// Host side of the three collider kinds inside libtsl_hip.so -- planes (k_collider.hpp), balls (k_sphere.hpp; 2.9), rods (k_capsule.hpp;
+// 2.10): the entry points tsl_set_colliders .. tsl_capsule_grad of include/tsl_hip.h and, for the launch sites of tsl_hip.hip and adjoint_api.hpp,
+// the launches of an assembly, an energy and a reverse step.  One set of helpers, templates on the kind's Shape (k_shape.hpp);
+// an entry point checks what is particular to its kind (collider_host.hpp, sphere_host.hpp, capsule_host.hpp) and hands on.  Included by
+// tsl_hip.hip behind its helpers (tsl_fail, TSL_TRY, HIP_OK, Scope, nblk), the way handle_api.hpp is.
 #pragma once
-#include "collider_host.hpp"
+#include <type_traits>
+#include "k_capsule.hpp"
 #include "k_collider.hpp"
+#include "k_sphere.hpp"
 #include "tsl_ctx.hpp"
 
-// the collider kernels of an energy / assembly / reverse step run only while this holds: without it the launches are the ones they were
-static bool colliders_on(const tsl_ctx* c) { return c->col.n > 0 && c->k_collider != 0.0; }
-// the plane table as the scalars stand now
-static ColliderPlanes collider_planes(const tsl_ctx* c) {
-  ColliderPlanes P = c->col;
-  P.k = c->k_collider; P.eps = c->eps_contact; P.eh = c->eps_v * c->dt;
-  return P;
+template <class Shape>
+static auto& shape_set(tsl_ctx* c) {
+  if constexpr (std::is_same_v<Shape, PlaneShape>) return c->col;
+  else if constexpr (std::is_same_v<Shape, SphereShape>) return c->sph;
+  else return c->cap;
 }
-static ColliderArgs collider_args(const tsl_ctx* c) { return ColliderArgs{c->NV, c->col_mask.p}; }
-static int collider_nblk(const tsl_ctx* c) { return nblk(c->NV, 256); }
+// the kernels of a kind in an energy / assembly / reverse step run only while this holds: without it the launches are the ones they were
+template <class Shape>
+static bool shape_on(tsl_ctx* c) { return shape_set<Shape>(c).tab.n > 0 && shape_set<Shape>(c).k != 0.0; }
+// the table as the scalars stand now
+template <class Shape>
+static typename Shape::Table shape_table(tsl_ctx* c) {
+  typename Shape::Table T = shape_set<Shape>(c).tab;
+  T.k = shape_set<Shape>(c).k; T.eps = c->eps_contact; T.eh = c->eps_v * c->dt;
+  return T;
+}
+template <class Shape>
+static ShapeArgs shape_args(tsl_ctx* c) { return ShapeArgs{c->NV, shape_set<Shape>(c).mask.p}; }
+static int shape_nblk(const tsl_ctx* c) { return nblk(c->NV, 256); }
+// how many kinds hold shapes, on or not (they size the energy partials)
+static int shapes_present(tsl_ctx* c) { return (c->col.tab.n > 0) + (c->sph.tab.n > 0) + (c->cap.tab.n > 0); }
 
-// Colliders in an assembly: gradient rows and diagonal blocks behind the vertex terms on the same stream (nothing while no collider is on)
-static void collider_assemble_launch(tsl_ctx* c, hipStream_t s, const double* pos, const double* prev, double* grad) {
-  if (!colliders_on(c)) return;
-  hipLaunchKernelGGL(k_collider_assemble, dim3(collider_nblk(c)), dim3(256), 0, s, collider_planes(c), collider_args(c), pos, prev, (const int*)c->diag_blk.p, grad, c->vals_full.p);
+template <class Shape>
+static void shape_assemble_launch(tsl_ctx* c, hipStream_t s, int spd, const double* pos, const double* prev, double* grad) {
+  if (!shape_on<Shape>(c)) return;
+  hipLaunchKernelGGL(k_shape_assemble<Shape>, dim3(shape_nblk(c)), dim3(256), 0, s, shape_table<Shape>(c), shape_args<Shape>(c), spd == 0 ? 1 : 0, pos, prev,
+                     (const int*)c->diag_blk.p, grad, c->vals_full.p);
 }
-static void collider_energy_launch(tsl_ctx* c, hipStream_t s, const double* pos, const double* prev, double* e_part) {
-  hipLaunchKernelGGL(k_collider_energy, dim3(collider_nblk(c)), dim3(256), 0, s, collider_planes(c), collider_args(c), pos, prev, e_part);
+template <class Shape>
+static void shape_energy_launch(tsl_ctx* c, hipStream_t s, const double* pos, const double* prev, double* e_part, int& nb) {
+  if (!shape_on<Shape>(c)) return;
+  hipLaunchKernelGGL(k_shape_energy<Shape>, dim3(shape_nblk(c)), dim3(256), 0, s, shape_table<Shape>(c), shape_args<Shape>(c), pos, prev, e_part + nb);
+  nb += shape_nblk(c);
 }
-// the share of a reverse step that goes into pos_grad[s-1] (x_s, x_{s-1}, the adjoint solution p)
-static void collider_backprop_launch(tsl_ctx* c, hipStream_t s, const double* x_s, const double* x_prev, const double* p, double* pg_prev) {
-  if (!colliders_on(c)) return;
-  hipLaunchKernelGGL(k_collider_backprop, dim3(collider_nblk(c)), dim3(256), 0, s, collider_planes(c), collider_args(c), (const int*)c->frozen.p, x_s, x_prev, p, pg_prev);
+template <class Shape>
+static void shape_backprop_launch(tsl_ctx* c, hipStream_t s, const double* x_s, const double* x_prev, const double* p, double* pg_prev) {
+  if (!shape_on<Shape>(c)) return;
+  hipLaunchKernelGGL(k_shape_backprop<Shape>, dim3(shape_nblk(c)), dim3(256), 0, s, shape_table<Shape>(c), shape_args<Shape>(c), (const int*)c->frozen.p, x_s, x_prev, p, pg_prev);
 }
 
-// The list is checked on the host (collider_host.hpp) and kept in the context; the mask is a device buffer of NV bytes.  A refusal leaves the
-// previous list in place.  n = 0 removes the colliders.
+// The colliders in an assembly: gradient rows and diagonal blocks behind the vertex terms on the same stream -- planes, then balls, then rods; a
+// kind that is not on launches nothing.  spd 0: the exact block of the reverse step's operator; every other mode: the projected one
+static void shapes_assemble_launch(tsl_ctx* c, hipStream_t s, int spd, const double* pos, const double* prev, double* grad) {
+  shape_assemble_launch<PlaneShape>(c, s, spd, pos, prev, grad);
+  shape_assemble_launch<SphereShape>(c, s, spd, pos, prev, grad);
+  shape_assemble_launch<CapsuleShape>(c, s, spd, pos, prev, grad);
+}
+// Their energy partials from e_part on, one per workgroup of 256 vertices and kind that is on, in the same order; returns how many
+static int shapes_energy_launch(tsl_ctx* c, hipStream_t s, const double* pos, const double* prev, double* e_part) {
+  int nb = 0;
+  shape_energy_launch<PlaneShape>(c, s, pos, prev, e_part, nb);
+  shape_energy_launch<SphereShape>(c, s, pos, prev, e_part, nb);
+  shape_energy_launch<CapsuleShape>(c, s, pos, prev, e_part, nb);
+  return nb;
+}
+// Their share of a reverse step that goes into pos_grad[s-1] (x_s, x_{s-1}, the adjoint solution p), in the same order: the planes' lagged
+// friction; the balls' lagged friction and lagged contact frame; the rods' lagged friction, lagged contact frame and lagged rod parameter
+static void shapes_backprop_launch(tsl_ctx* c, hipStream_t s, const double* x_s, const double* x_prev, const double* p, double* pg_prev) {
+  shape_backprop_launch<PlaneShape>(c, s, x_s, x_prev, p, pg_prev);
+  shape_backprop_launch<SphereShape>(c, s, x_s, x_prev, p, pg_prev);
+  shape_backprop_launch<CapsuleShape>(c, s, x_s, x_prev, p, pg_prev);
+}
+
+// The tail of tsl_set_*: T is the checked list of n shapes (the kind's host header); the mask is checked here and becomes a device buffer of NV
+// bytes.  A refusal leaves the previous list in place.  n = 0 removes the kind.
+template <class Shape>
+static int shape_commit(tsl_ctx* c, const char* who, const char* noun, const typename Shape::Table& T, int32_t n, const uint8_t* vertex_mask) {
+  auto& S = shape_set<Shape>(c);
+  std::string err;
+  std::vector<uint8_t> mask;
+  if (shape_mask_validate(noun, c->NV, n, vertex_mask, mask, err)) return tsl_fail("%s: %s", who, err.c_str());
+  c->mg_omega_valid = false;
+  c->ds.anorm_valid = false;   // (the scale of the operator may change)
+  S.tab.n = 0;
+  if (n == 0) { S.mask.release(); S.part.release(); S.out.release(); return 0; }
+  TSL_TRY(S.mask.upload(mask));
+  TSL_TRY(S.part.alloc((size_t)(SHAPE_MAX * Shape::stride) * shape_nblk(c)));
+  TSL_TRY(S.out.alloc(SHAPE_MAX * Shape::stride));
+  S.tab = T;
+  return 0;
+}
+template <class Shape>
+static int shape_count(tsl_ctx* c, const char* who, int32_t* out) {
+  if (!c || !out) return tsl_fail("%s: null argument", who);
+  *out = shape_set<Shape>(c).tab.n;
+  return 0;
+}
+// read-outs, `per` values per shape: the partials joined in workgroup order, one copy to the host, one synchronisation
+template <class Shape>
+static int shape_readout(tsl_ctx* c, int per, double* out_host) {
+  auto& S = shape_set<Shape>(c);
+  hipLaunchKernelGGL(k_shape_join, dim3(1), dim3(SHAPE_MAX * Shape::stride), 0, c->stream, shape_nblk(c), S.tab.n, per, Shape::stride, (const double*)S.part.p, S.out.p);
+  HIP_OK(hipGetLastError());
+  HIP_OK(hipMemcpyAsync(out_host, S.out.p, (size_t)per * S.tab.n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIP_OK(hipStreamSynchronize(c->stream));
+  return 0;
+}
+// out_host (n x Shape::n_force) at the state (pos, prev); no shape: nothing; stiffness 0: zeros, no launch
+template <class Shape>
+static int shape_force(tsl_ctx* c, const char* who, const double* pos, const double* prev, double* out_host) {
+  Scope scope(c);
+  auto& S = shape_set<Shape>(c);
+  if (S.tab.n == 0) return 0;
+  if (!pos || !prev || !out_host) return tsl_fail("%s: null argument", who);
+  if (S.k == 0.0) { std::fill(out_host, out_host + Shape::n_force * (size_t)S.tab.n, 0.0); return 0; }
+  hipLaunchKernelGGL(k_shape_force<Shape>, dim3(shape_nblk(c)), dim3(256), 0, c->stream, shape_table<Shape>(c), shape_args<Shape>(c), pos, prev, S.part.p);
+  return shape_readout<Shape>(c, Shape::n_force, out_host);
+}
+// out_host (n x Shape::n_grad): the share of one reverse step at the tape state (pos = x_s, prev = x_{s-1}) with the table of step s in place;
+// p_dev null: the last adjoint solution
+template <class Shape>
+static int shape_grad(tsl_ctx* c, const char* who, const double* pos, const double* prev, const double* p_dev, double* out_host) {
+  Scope scope(c);
+  auto& S = shape_set<Shape>(c);
+  if (S.tab.n == 0) return 0;
+  if (!pos || !prev || !out_host) return tsl_fail("%s: null argument", who);
+  if (S.k == 0.0) { std::fill(out_host, out_host + Shape::n_grad * (size_t)S.tab.n, 0.0); return 0; }
+  const double* p = p_dev ? p_dev : (const double*)c->pdir.p;
+  hipLaunchKernelGGL(k_shape_grad<Shape>, dim3(shape_nblk(c)), dim3(256), 0, c->stream, shape_table<Shape>(c), shape_args<Shape>(c), (const int*)c->frozen.p, pos, prev, p, S.part.p);
+  return shape_readout<Shape>(c, Shape::n_grad, out_host);
+}
+
+// ---- planes.  Force: n x 3, the net force -sum_v g_v of every plane.  Grad: n x 2, d(loss)/d(o_j) and d(loss)/d(mu_j), the offsets of step s in place
 extern "C" int tsl_set_colliders(tsl_ctx* c, const double* normals, const double* offsets, const double* mu, int32_t n, const uint8_t* vertex_mask) {
   Scope scope(c);
   (void)hipStreamSynchronize(c->stream);
   std::string err;
-  ColliderPlanes P = c->col;
+  ColliderPlanes P = c->col.tab;
   if (collider_validate(normals, offsets, mu, n, P, err)) return tsl_fail("tsl_set_colliders: %s", err.c_str());
-  std::vector<uint8_t> mask;
-  if (collider_mask_validate(c->NV, n, vertex_mask, mask, err)) return tsl_fail("tsl_set_colliders: %s", err.c_str());
-  c->mg_omega_valid = false;
-  c->ds.anorm_valid = false;   // (the scale of the operator may change)
-  c->col.n = 0;
-  if (n == 0) { c->col_mask.release(); c->col_part.release(); c->col_out.release(); return 0; }
-  TSL_TRY(c->col_mask.upload(mask));
-  TSL_TRY(c->col_part.alloc((size_t)COLLIDER_SLOTS * collider_nblk(c)));
-  TSL_TRY(c->col_out.alloc(COLLIDER_SLOTS));
-  c->col = P;
-  return 0;
+  return shape_commit<PlaneShape>(c, "tsl_set_colliders", "collider", P, n, vertex_mask);
 }
 extern "C" int tsl_set_collider_offsets(tsl_ctx* c, const double* offsets) {
   Scope scope(c);
   (void)hipStreamSynchronize(c->stream);
-  if (c->col.n == 0) return 0;
+  if (c->col.tab.n == 0) return 0;
   std::string err;
-  if (collider_offsets_validate(offsets, c->col, err)) return tsl_fail("tsl_set_collider_offsets: %s", err.c_str());
+  if (collider_offsets_validate(offsets, c->col.tab, err)) return tsl_fail("tsl_set_collider_offsets: %s", err.c_str());
   return 0;
 }
-extern "C" int tsl_collider_count(tsl_ctx* c, int32_t* out) {
-  if (!c || !out) return tsl_fail("tsl_collider_count: null argument");
-  *out = c->col.n;
-  return 0;
-}
-// read-outs, `per` values per collider: the partials joined in workgroup order, one copy to the host, one synchronisation
-static int collider_readout(tsl_ctx* c, int per, double* out_host) {
-  hipLaunchKernelGGL(k_collider_join, dim3(1), dim3(64), 0, c->stream, collider_nblk(c), (const double*)c->col_part.p, c->col_out.p);
-  HIP_OK(hipGetLastError());
-  HIP_OK(hipMemcpyAsync(out_host, c->col_out.p, (size_t)per * c->col.n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  HIP_OK(hipStreamSynchronize(c->stream));
-  return 0;
-}
-// out_host (n x 3): the net force -sum_v g_v of every plane at the state (pos, prev_pos); k_collider = 0: zeros, no launch
+extern "C" int tsl_collider_count(tsl_ctx* c, int32_t* out) { return shape_count<PlaneShape>(c, "tsl_collider_count", out); }
 extern "C" int tsl_collider_force(tsl_ctx* c, const double* pos, const double* prev, double* out_host) {
-  Scope scope(c);
-  if (c->col.n == 0) return 0;
-  if (!pos || !prev || !out_host) return tsl_fail("tsl_collider_force: null argument");
-  if (c->k_collider == 0.0) { std::fill(out_host, out_host + 3 * (size_t)c->col.n, 0.0); return 0; }
-  hipLaunchKernelGGL(k_collider_force, dim3(collider_nblk(c)), dim3(256), 0, c->stream, collider_planes(c), collider_args(c), pos, prev, c->col_part.p);
-  return collider_readout(c, 3, out_host);
+  return shape_force<PlaneShape>(c, "tsl_collider_force", pos, prev, out_host);
 }
-// out_host (n x 2): the share of one reverse step in d(loss)/d(o_j) and d(loss)/d(mu_j) at the tape state (pos = x_s, prev_pos = x_{s-1}) with the
-// offsets of step s in place; p_dev null: the last adjoint solution
 extern "C" int tsl_collider_grad(tsl_ctx* c, const double* pos, const double* prev, const double* p_dev, double* out_host) {
+  return shape_grad<PlaneShape>(c, "tsl_collider_grad", pos, prev, p_dev, out_host);
+}
+
+// ---- balls.  The previous centres of a new list are its centres.  Force: n x 3, the net force -sum_v g_v of every ball.  Grad: n x 8,
+// d(loss)/d(c_j, cp_j, mu_j, R_j), the centres and previous centres of step s in place
+extern "C" int tsl_set_spheres(tsl_ctx* c, const double* centres, const double* radii, const double* mu, int32_t n, const uint8_t* vertex_mask) {
   Scope scope(c);
-  if (c->col.n == 0) return 0;
-  if (!pos || !prev || !out_host) return tsl_fail("tsl_collider_grad: null argument");
-  if (c->k_collider == 0.0) { std::fill(out_host, out_host + 2 * (size_t)c->col.n, 0.0); return 0; }
-  const double* p = p_dev ? p_dev : (const double*)c->pdir.p;
-  hipLaunchKernelGGL(k_collider_grad, dim3(collider_nblk(c)), dim3(256), 0, c->stream, collider_planes(c), collider_args(c), (const int*)c->frozen.p, pos, prev, p, c->col_part.p);
-  return collider_readout(c, 2, out_host);
+  (void)hipStreamSynchronize(c->stream);
+  std::string err;
+  SphereTable S = c->sph.tab;
+  if (sphere_validate(centres, radii, mu, n, S, err)) return tsl_fail("tsl_set_spheres: %s", err.c_str());
+  return shape_commit<SphereShape>(c, "tsl_set_spheres", "sphere", S, n, vertex_mask);
+}
+extern "C" int tsl_set_sphere_centres(tsl_ctx* c, const double* centres, const double* prev_centres) {
+  Scope scope(c);
+  (void)hipStreamSynchronize(c->stream);
+  if (c->sph.tab.n == 0) return 0;
+  std::string err;
+  if (sphere_centres_validate(centres, prev_centres, c->sph.tab, err)) return tsl_fail("tsl_set_sphere_centres: %s", err.c_str());
+  return 0;
+}
+extern "C" int tsl_sphere_count(tsl_ctx* c, int32_t* out) { return shape_count<SphereShape>(c, "tsl_sphere_count", out); }
+extern "C" int tsl_sphere_force(tsl_ctx* c, const double* pos, const double* prev, double* out_host) {
+  return shape_force<SphereShape>(c, "tsl_sphere_force", pos, prev, out_host);
+}
+extern "C" int tsl_sphere_grad(tsl_ctx* c, const double* pos, const double* prev, const double* p_dev, double* out_host) {
+  return shape_grad<SphereShape>(c, "tsl_sphere_grad", pos, prev, p_dev, out_host);
+}
+
+// ---- rods.  The previous endpoints of a new list are its endpoints.  Force: n x 6, the net force -sum_v g_v of every rod and its torque
+// -sum_v (x_v - m) x g_v about the rod's midpoint.  Grad: n x 14, d(loss)/d(a_j, b_j, ap_j, bp_j, mu_j, R_j), the endpoints and previous endpoints of
+// step s in place
+extern "C" int tsl_set_capsules(tsl_ctx* c, const double* a, const double* b, const double* radii, const double* mu, int32_t n, const uint8_t* vertex_mask) {
+  Scope scope(c);
+  (void)hipStreamSynchronize(c->stream);
+  std::string err;
+  CapsuleTable S = c->cap.tab;
+  if (capsule_validate(a, b, radii, mu, n, S, err)) return tsl_fail("tsl_set_capsules: %s", err.c_str());
+  return shape_commit<CapsuleShape>(c, "tsl_set_capsules", "capsule", S, n, vertex_mask);
+}
+extern "C" int tsl_set_capsule_ends(tsl_ctx* c, const double* a, const double* b, const double* prev_a, const double* prev_b) {
+  Scope scope(c);
+  (void)hipStreamSynchronize(c->stream);
+  if (c->cap.tab.n == 0) return 0;
+  std::string err;
+  if (capsule_ends_validate(a, b, prev_a, prev_b, c->cap.tab, err)) return tsl_fail("tsl_set_capsule_ends: %s", err.c_str());
+  return 0;
+}
+extern "C" int tsl_capsule_count(tsl_ctx* c, int32_t* out) { return shape_count<CapsuleShape>(c, "tsl_capsule_count", out); }
+extern "C" int tsl_capsule_force(tsl_ctx* c, const double* pos, const double* prev, double* out_host) {
+  return shape_force<CapsuleShape>(c, "tsl_capsule_force", pos, prev, out_host);
+}
+extern "C" int tsl_capsule_grad(tsl_ctx* c, const double* pos, const double* prev, const double* p_dev, double* out_host) {
+  return shape_grad<CapsuleShape>(c, "tsl_capsule_grad", pos, prev, p_dev, out_host);
 }

@@ -20,17 +20,13 @@
 // The gap is sph_gap of k_sphere.hpp about the rounded closest point, corrected by the rounding error of that point (cap_gap); sph_fric and sph_M
 // are the spheres', with SphHead::dc the motion of the rod's point.  Degenerate pairs: rho < 1e-12 contributes nothing; rho0 < 1e-12 has no
 // friction.  Segments shorter than 1e-9 m never get here (capsule_host.hpp refuses them).
-// One lane per VERTEX, the capsules in ascending j, the table by value in the kernel arguments.  A vertex with mask 0 leaves at once; a pair with
-// d >= eps and lam = 0 leaves behind the two heads (two square roots, four divisions).  No atomics, every sum in a fixed order: the same bits run
-// to run.  Launched only while capsules exist and k_capsule != 0.  Frozen dofs follow the rule of every other term.
+// The kernels are k_shape.hpp's with CapsuleShape below: one lane per VERTEX, the capsules in ascending j, the table by value in the kernel
+// arguments; a pair with d >= eps and lam = 0 leaves behind the two heads (two square roots, four divisions).  The normal block, the friction
+// block, the energy and the gradient of a pair are the spheres' (k_sphere.hpp), with the barrel term under CapHead::barrel.  Launched only while
+// capsules exist and k_capsule != 0.
 #pragma once
 #include "capsule_host.hpp"
 #include "k_sphere.hpp"
-
-struct CapsuleArgs {
-  int NV;
-  const unsigned char* mask;   // NV: bit j set: capsule j acts on the vertex
-};
 
 // the cheap part of the pair (vertex, capsule j): the sphere's head about the closest points, and where on the rod they lie
 struct CapHead {
@@ -39,6 +35,8 @@ struct CapHead {
   double ee, ee0;    // e . e, e0 . e0
   double t, t0, s0;
   bool in, in0;
+  static constexpr bool barrel = true;
+  TSL_DEV const SphHead& sph() const { return h; }
 };
 // The closest point c = a + t e as an unevaluated sum ch + cl: the product's rounding error by fma, the sum's by a two-sum.  A rounded c alone is
 // off by half a last bit of |c| (1e-16 m for a rod of radius 1 m), which is 1e-12 of a penetration of 1e-4 m and shows in lam and in every entry
@@ -59,7 +57,7 @@ TSL_DEV double cap_gap(const d3& x, const d3& a, const d3& e, double t, double R
 }
 TSL_DEV CapHead cap_head(const CapsuleTable& S, int j, const d3& x, const d3& xp) {
   CapHead c;
-  const double* r = S.cp[j];
+  const double* r = S.row[j];
   const d3 a(r[0], r[1], r[2]), b(r[3], r[4], r[5]), ap(r[6], r[7], r[8]), bp(r[9], r[10], r[11]);
   const double R = r[12];
   c.e = b - a; c.e0 = bp - ap;
@@ -113,183 +111,71 @@ TSL_DEV CapPrev cap_prev(const CapHead& c, const SphFric& f, double k, double ep
   return o;
 }
 
-// F[v] += g (where a gradient is asked for), diagonal block of v += H through diag_blk, as k_sphere_assemble.  The upper triangle of H is formed
-// and mirrored: the block is symmetric bit for bit.  exact (uniform): spd == 0, the curvature part of H_n is added; else it is left out.
-__global__ void __launch_bounds__(256) k_capsule_assemble(CapsuleTable S, CapsuleArgs A, int exact, const double* __restrict__ pos, const double* __restrict__ prev,
-                                                          const int* __restrict__ diag_blk, double* __restrict__ F, double* __restrict__ vals) {
-  const int v = blockIdx.x * blockDim.x + threadIdx.x;
-  if (v >= A.NV) return;
-  const unsigned m = A.mask[v];
-  if (!m) return;
-  const d3 x = ld3(pos, v), xp = ld3(prev, v);
-  d3 g(0.0, 0.0, 0.0);
-  double hxx = 0.0, hxy = 0.0, hxz = 0.0, hyy = 0.0, hyz = 0.0, hzz = 0.0;
-  for (int j = 0; j < S.n; j++) {
-    if (!((m >> j) & 1u)) continue;
+struct CapsuleShape {
+  using Table = CapsuleTable;
+  static constexpr int stride = 16, n_force = 6, n_grad = 14;
+  static TSL_DEV void assemble(const Table& S, int j, const d3& x, const d3& xp, int exact, d3& g, Sym3& H) {
+    sph_assemble_pair(cap_head(S, j, x, xp), S, x, xp, exact, g, H);
+  }
+  static TSL_DEV void energy(const Table& S, int j, const d3& x, const d3& xp, double& e) { sph_energy_pair(cap_head(S, j, x, xp).h, S, x, xp, e); }
+  // -(dg / dx_prev)^T p_v, the endpoints and previous endpoints of step s in the table
+  static TSL_DEV void backprop(const Table& S, int j, const d3& x, const d3& xp, const d3& pv, d3& acc) {
     const CapHead c = cap_head(S, j, x, xp);
     const SphHead& h = c.h;
-    if (!h.ok || (!h.act && !(h.lam > 0.0))) continue;
-    if (h.act) {
-      const d3 n = h.q / h.rho;
-      const double kd = S.k * (h.d - S.eps);
-      g = g + n * kd;
-      hxx += S.k * (n.x * n.x); hxy += S.k * (n.x * n.y); hxz += S.k * (n.x * n.z);
-      hyy += S.k * (n.y * n.y); hyz += S.k * (n.y * n.z); hzz += S.k * (n.z * n.z);
-      if (exact) {
-        const double cr = kd / h.rho, uu = c.in ? 1.0 / c.ee : 0.0;
-        const d3& e = c.e;
-        hxx += cr * (1.0 - n.x * n.x - uu * (e.x * e.x)); hxy -= cr * (n.x * n.y + uu * (e.x * e.y)); hxz -= cr * (n.x * n.z + uu * (e.x * e.z));
-        hyy += cr * (1.0 - n.y * n.y - uu * (e.y * e.y)); hyz -= cr * (n.y * n.z + uu * (e.y * e.z)); hzz += cr * (1.0 - n.z * n.z - uu * (e.z * e.z));
-      }
-    }
-    if (h.lam > 0.0) {
-      const SphFric f = sph_fric(h, x, xp, S.eh);
-      g = g + f.w * (h.lam * f.a);
-      const d3& n0 = f.n0; const d3& w = f.w;
-      hxx += h.lam * (f.a * (1.0 - n0.x * n0.x) + f.f2r * (w.x * w.x)); hxy += h.lam * (f.f2r * (w.x * w.y) - f.a * (n0.x * n0.y));
-      hxz += h.lam * (f.f2r * (w.x * w.z) - f.a * (n0.x * n0.z)); hyy += h.lam * (f.a * (1.0 - n0.y * n0.y) + f.f2r * (w.y * w.y));
-      hyz += h.lam * (f.f2r * (w.y * w.z) - f.a * (n0.y * n0.z)); hzz += h.lam * (f.a * (1.0 - n0.z * n0.z) + f.f2r * (w.z * w.z));
-    }
-  }
-  if (F) st3(F, v, ld3(F, v) + g);
-  const size_t base = (size_t)diag_blk[v];
-  vals[base + 64 * 0] += hxx; vals[base + 64 * 1] += hxy; vals[base + 64 * 2] += hxz;
-  vals[base + 64 * 3] += hxy; vals[base + 64 * 4] += hyy; vals[base + 64 * 5] += hyz;
-  vals[base + 64 * 6] += hxz; vals[base + 64 * 7] += hyz; vals[base + 64 * 8] += hzz;
-}
-
-// one partial per workgroup (wg_join), behind the sphere partials; k_energy_final adds them in its fixed order
-__global__ void __launch_bounds__(256) k_capsule_energy(CapsuleTable S, CapsuleArgs A, const double* __restrict__ pos, const double* __restrict__ prev,
-                                                        double* __restrict__ e_part) {
-  const int v = blockIdx.x * blockDim.x + threadIdx.x;
-  double e[1] = {0.0};
-  const unsigned m = v < A.NV ? A.mask[v] : 0u;
-  if (m) {
-    const d3 x = ld3(pos, v), xp = ld3(prev, v);
-    for (int j = 0; j < S.n; j++) {
-      if (!((m >> j) & 1u)) continue;
-      const CapHead c = cap_head(S, j, x, xp);
-      const SphHead& h = c.h;
-      if (!h.ok || (!h.act && !(h.lam > 0.0))) continue;
-      if (h.act) e[0] += 0.5 * S.k * (h.d - S.eps) * (h.d - S.eps);
-      if (h.lam > 0.0) e[0] += h.lam * fr_f0(sph_fric(h, x, xp, S.eh).r, S.eh);
-    }
-  }
-  wg_join<1>(e, e_part + blockIdx.x);
-}
-
-// The reverse step: pos = x_s, prev = x_{s-1}, p the adjoint solution (its frozen dofs do not count), the endpoints and previous endpoints of step s
-// in the table.  Into the vertex's own row of pos_grad[s-1], on free dofs:  += sum_j -(dg / dx_prev)^T p_v.  In front of k_adj_prev.
-__global__ void __launch_bounds__(256) k_capsule_backprop(CapsuleTable S, CapsuleArgs A, const int* __restrict__ frozen, const double* __restrict__ pos,
-                                                          const double* __restrict__ prev, const double* __restrict__ p, double* __restrict__ pg_prev) {
-  const int v = blockIdx.x * blockDim.x + threadIdx.x;
-  if (v >= A.NV) return;
-  const unsigned m = A.mask[v];
-  if (!m) return;
-  const int* __restrict__ fz = frozen + 3 * (size_t)v;
-  const d3 pv = sph_free_p(frozen, p, v);
-  const d3 x = ld3(pos, v), xp = ld3(prev, v);
-  d3 acc(0.0, 0.0, 0.0);
-  for (int j = 0; j < S.n; j++) {
-    if (!((m >> j) & 1u)) continue;
-    const CapHead c = cap_head(S, j, x, xp);
-    const SphHead& h = c.h;
-    if (!h.ok || !(h.lam > 0.0)) continue;   // (lam > 0 implies d0 < eps and mu > 0)
+    if (!h.ok || !(h.lam > 0.0)) return;   // (lam > 0 implies d0 < eps and mu > 0)
     const CapPrev o = cap_prev(c, sph_fric(h, x, xp, S.eh), S.k, S.eps, pv);
     acc = acc + o.X;
     if (c.in0) acc = acc + c.e0 * (h.lam * o.DMy / c.ee0);
   }
-  const d3 o = ld3(pg_prev, v);
-  st3(pg_prev, v, d3(fz[0] ? o.x : o.x + acc.x, fz[1] ? o.y : o.y + acc.y, fz[2] ? o.z : o.z + acc.z));
-}
-
-// Read-outs.  A workgroup writes CAPSULE_SLOTS partials, 16 per capsule (14 used); the capsules are joined one after the other (wg_join<14> /
-// wg_join<6>), so that a lane holds the sums of one capsule at a time; k_capsule_join adds the partials in workgroup order.
-#define CAPSULE_SLOTS (16 * TSL_MAX_CAPSULES)
-// tsl_capsule_grad, slots 16 j ..: this reverse step's share of d(loss)/d(a_j) (3), d(loss)/d(b_j) (3), d(loss)/d(ap_j) (3), d(loss)/d(bp_j) (3),
-// d(loss)/d(mu_j), d(loss)/d(R_j), each -sum_v (dg/d.)^T p_v, H_n exact.  Free dofs of p only.
-__global__ void __launch_bounds__(256) k_capsule_grad(CapsuleTable S, CapsuleArgs A, const int* __restrict__ frozen, const double* __restrict__ pos,
-                                                      const double* __restrict__ prev, const double* __restrict__ p, double* __restrict__ part) {
-  const int v = blockIdx.x * blockDim.x + threadIdx.x;
-  const unsigned m = v < A.NV ? A.mask[v] : 0u;
-  d3 pv, x, xp;
-  if (m) { pv = sph_free_p(frozen, p, v); x = ld3(pos, v); xp = ld3(prev, v); }
-  for (int j = 0; j < S.n; j++) {   // (uniform)
-    double s[14];
-#pragma unroll
-    for (int q = 0; q < 14; q++) s[q] = 0.0;
-    if ((m >> j) & 1u) {
-      const CapHead c = cap_head(S, j, x, xp);
-      const SphHead& h = c.h;
-      if (h.ok && (h.act || h.pen > 0.0)) {
-        d3 ga(0.0, 0.0, 0.0), gb(0.0, 0.0, 0.0);
-        if (h.act) {
-          // -(dg/da)^T p = (1 - t) H_n p - phi' n (tau . p),  -(dg/db)^T p = t H_n p + phi' n (tau . p),  tau = in e / (e . e)
-          const d3 Hp = cap_Hn(c, S.k, S.eps, pv);
-          const d3 n = h.q / h.rho;
-          const d3 tn = n * (c.in ? (S.k * (h.d - S.eps)) * (dot(c.e, pv) / c.ee) : 0.0);
-          ga = Hp * (1.0 - c.t) - tn; gb = Hp * c.t + tn;
-          s[13] = S.k * dot(n, pv);
-        }
-        if (h.pen > 0.0) {
-          const SphFric f = sph_fric(h, x, xp, S.eh);
-          const double paw = f.a * dot(f.w, pv);
-          if (h.lam > 0.0) {
-            const d3 Mp = sph_M(f, pv) * h.lam;
-            ga = ga + Mp * (1.0 - c.t0); gb = gb + Mp * c.t0;
-            const CapPrev o = cap_prev(c, f, S.k, S.eps, pv);
-            d3 gap = -(o.X * (1.0 - c.t0)) + f.n0 * (h.lam * o.t0z), gbp = -(o.X * c.t0) - f.n0 * (h.lam * o.t0z);
-            if (c.in0) {
-              const double sc = h.lam * o.DMy / c.ee0;
-              gap = gap - (h.q0 + c.e0 * (1.0 - c.s0)) * sc; gbp = gbp + (h.q0 - c.e0 * c.s0) * sc;
-            }
-            s[6] = gap.x; s[7] = gap.y; s[8] = gap.z; s[9] = gbp.x; s[10] = gbp.y; s[11] = gbp.z;
-          }
-          s[12] = -((S.k * h.pen) * paw);
-          if (h.d0 < S.eps) s[13] -= (h.mu * S.k) * paw;
-        }
-        s[0] = ga.x; s[1] = ga.y; s[2] = ga.z; s[3] = gb.x; s[4] = gb.y; s[5] = gb.z;
-      }
+  // tsl_capsule_force: -g_v of capsule j, the force the rod applies to the cloth, and -(x_v - m) x g_v, its torque about the rod's midpoint
+  // m = (a + b) / 2, in the sign of the force
+  static TSL_DEV void force(const Table& S, int j, const d3& x, const d3& xp, double (&s)[6]) {
+    const CapHead c = cap_head(S, j, x, xp);
+    const SphHead& h = c.h;
+    if (h.ok && (h.act || h.lam > 0.0)) {
+      const d3 g = sph_pair_g(h, S, x, xp);
+      const double* r = S.row[j];
+      const d3 arm = x - d3(0.5 * (r[0] + r[3]), 0.5 * (r[1] + r[4]), 0.5 * (r[2] + r[5]));
+      const d3 tq = cross(arm, g);
+      s[0] = -g.x; s[1] = -g.y; s[2] = -g.z; s[3] = -tq.x; s[4] = -tq.y; s[5] = -tq.z;
     }
-    wg_join<14>(s, part + (size_t)CAPSULE_SLOTS * blockIdx.x + 16 * j);
-    __syncthreads();   // (the LDS of wg_join is used again for the next capsule)
   }
-}
-// tsl_capsule_force, slots 16 j .. 16 j + 5: -sum_v g_v of capsule j, the net force the rod applies to the cloth, and -sum_v (x_v - m) x g_v, its
-// torque about the rod's midpoint m = (a + b) / 2, in the sign of the force; frozen dofs are not masked
-__global__ void __launch_bounds__(256) k_capsule_force(CapsuleTable S, CapsuleArgs A, const double* __restrict__ pos, const double* __restrict__ prev,
-                                                       double* __restrict__ part) {
-  const int v = blockIdx.x * blockDim.x + threadIdx.x;
-  const unsigned m = v < A.NV ? A.mask[v] : 0u;
-  d3 x, xp;
-  if (m) { x = ld3(pos, v); xp = ld3(prev, v); }
-  for (int j = 0; j < S.n; j++) {   // (uniform)
-    double s[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-    if ((m >> j) & 1u) {
-      const CapHead c = cap_head(S, j, x, xp);
-      const SphHead& h = c.h;
-      if (h.ok && (h.act || h.lam > 0.0)) {
-        d3 g(0.0, 0.0, 0.0);
-        if (h.act) g = g + (h.q / h.rho) * (S.k * (h.d - S.eps));
+  // tsl_capsule_grad: this reverse step's share of d(loss)/d(a_j) (3), d(loss)/d(b_j) (3), d(loss)/d(ap_j) (3), d(loss)/d(bp_j) (3),
+  // d(loss)/d(mu_j), d(loss)/d(R_j), each -(dg/d.)^T p_v, H_n exact
+  static TSL_DEV void grad(const Table& S, int j, const d3& x, const d3& xp, const d3& pv, double (&s)[14]) {
+    const CapHead c = cap_head(S, j, x, xp);
+    const SphHead& h = c.h;
+    if (h.ok && (h.act || h.pen > 0.0)) {
+      d3 ga(0.0, 0.0, 0.0), gb(0.0, 0.0, 0.0);
+      if (h.act) {
+        // -(dg/da)^T p = (1 - t) H_n p - phi' n (tau . p),  -(dg/db)^T p = t H_n p + phi' n (tau . p),  tau = in e / (e . e)
+        const d3 Hp = cap_Hn(c, S.k, S.eps, pv);
+        const d3 n = h.q / h.rho;
+        const d3 tn = n * (c.in ? (S.k * (h.d - S.eps)) * (dot(c.e, pv) / c.ee) : 0.0);
+        ga = Hp * (1.0 - c.t) - tn; gb = Hp * c.t + tn;
+        s[13] = S.k * dot(n, pv);
+      }
+      if (h.pen > 0.0) {
+        const SphFric f = sph_fric(h, x, xp, S.eh);
+        const double paw = f.a * dot(f.w, pv);
         if (h.lam > 0.0) {
-          const SphFric f = sph_fric(h, x, xp, S.eh);
-          g = g + f.w * (h.lam * f.a);
+          const d3 Mp = sph_M(f, pv) * h.lam;
+          ga = ga + Mp * (1.0 - c.t0); gb = gb + Mp * c.t0;
+          const CapPrev o = cap_prev(c, f, S.k, S.eps, pv);
+          d3 gap = -(o.X * (1.0 - c.t0)) + f.n0 * (h.lam * o.t0z), gbp = -(o.X * c.t0) - f.n0 * (h.lam * o.t0z);
+          if (c.in0) {
+            const double sc = h.lam * o.DMy / c.ee0;
+            gap = gap - (h.q0 + c.e0 * (1.0 - c.s0)) * sc; gbp = gbp + (h.q0 - c.e0 * c.s0) * sc;
+          }
+          s[6] = gap.x; s[7] = gap.y; s[8] = gap.z; s[9] = gbp.x; s[10] = gbp.y; s[11] = gbp.z;
         }
-        const double* r = S.cp[j];
-        const d3 arm = x - d3(0.5 * (r[0] + r[3]), 0.5 * (r[1] + r[4]), 0.5 * (r[2] + r[5]));
-        const d3 tq = cross(arm, g);
-        s[0] = -g.x; s[1] = -g.y; s[2] = -g.z; s[3] = -tq.x; s[4] = -tq.y; s[5] = -tq.z;
+        s[12] = -((S.k * h.pen) * paw);
+        if (h.d0 < S.eps) {
+#pragma clang fp contract(off)   // (the product rounded on its own: it is the one cap_prev forms, not a part of an fma here)
+          s[13] -= (h.mu * S.k) * paw;
+        }
       }
+      s[0] = ga.x; s[1] = ga.y; s[2] = ga.z; s[3] = gb.x; s[4] = gb.y; s[5] = gb.z;
     }
-    wg_join<6>(s, part + (size_t)CAPSULE_SLOTS * blockIdx.x + 16 * j);
-    __syncthreads();
   }
-}
-// out[per j + i] = part[0][16 j + i] + part[1][16 j + i] + ..., in workgroup order, for j < n, i < per: one lane per slot (CAPSULE_SLOTS lanes)
-__global__ void k_capsule_join(int n_wg, int n, int per, const double* __restrict__ part, double* __restrict__ out) {
-  const int q = threadIdx.x, j = q >> 4, i = q & 15;
-  if (j >= n || i >= per) return;
-  double t = 0.0;
-  for (int w = 0; w < n_wg; w++) t += part[(size_t)CAPSULE_SLOTS * w + q];
-  out[per * j + i] = t;
-}
+};

@@ -14,26 +14,22 @@
 // [d < eps] k n n^T, the eigen-clamp of H_n in closed form (its eigenvectors are n and the tangent plane), and adds the same numbers.  H is 3 x 3
 // on the vertex's own diagonal block: no constraint slot, no row list, no change of a factorisation plan.  Nothing is stored per step.
 // Degenerate pairs: rho < 1e-12 (the vertex in the centre: no normal) contributes nothing; rho0 < 1e-12 has no friction.
-// One lane per VERTEX, the spheres in ascending j, the table by value in the kernel arguments.  A vertex with mask 0 leaves at once; a pair with
-// d >= eps and lam = 0 leaves behind the two square roots rho, rho0.  No atomics, every sum in a fixed order: the same bits run to run.  Launched
-// only while spheres exist and k_sphere != 0.  Frozen dofs follow the rule of every other term: the assembly adds to the unmasked gradient and
-// matrix, k_mask_vec / k_mask_matrix behind it take the frozen entries out again.
+// The kernels are k_shape.hpp's with SphereShape below: one lane per VERTEX, the spheres in ascending j, the table by value in the kernel
+// arguments; a pair with d >= eps and lam = 0 leaves behind the two square roots rho, rho0.  Launched only while spheres exist and k_sphere != 0.
+// The blocks that a rod shares (sph_normal_block, sph_friction_block, sph_pair_g and the pair functions built on them) take the pair's head as a
+// template argument: Head::barrel tells the capsule's (k_capsule.hpp), whose additions are compiled into its own instances only.
 #pragma once
 #include "k_contact.hpp"
-#include "k_handle.hpp"
+#include "k_shape.hpp"
 #include "sphere_host.hpp"
-#include "tsl_device.hpp"
-
-struct SphereArgs {
-  int NV;
-  const unsigned char* mask;   // NV: bit j set: sphere j acts on the vertex
-};
 
 // the cheap part of the pair (vertex, sphere j): two square roots
 struct SphHead {
   d3 q, q0, dc;   // x - c, x_prev - cp, c - cp
   double rho, rho0, d, d0, mu, pen, lam;
   bool ok, act;   // ok: rho >= 1e-12;  act: d < eps
+  static constexpr bool barrel = false;
+  TSL_DEV const SphHead& sph() const { return *this; }
 };
 // The gap |x - c| - R without its cancellations: a ball of radius 1e4 m (a floor in all but name) leaves |x - c| - R with the last bit of 1e4,
 // 2e-12 m, where the gap itself is 1e-6 m, and the line search of a step then compares energies that carry this noise.  x - c = s + e exactly
@@ -63,7 +59,7 @@ TSL_DEV double sph_gap(const d3& x, const d3& c, double R, d3& q, double& rho) {
 }
 TSL_DEV SphHead sph_head(const SphereTable& S, int j, const d3& x, const d3& xp) {
   SphHead h;
-  const double* t = S.sp[j];
+  const double* t = S.row[j];
   const d3 c(t[0], t[1], t[2]), cp(t[3], t[4], t[5]);
   h.mu = t[7];
   h.dc = c - cp;
@@ -108,169 +104,108 @@ TSL_DEV d3 sph_prev_term(const SphHead& h, const SphFric& f, double k, double ep
   return sph_M(f, y) * h.lam - Lty;
 }
 
-// F[v] += g (where a gradient is asked for), diagonal block of v += H through diag_blk, as k_collider_assemble.  The upper triangle of H is formed
-// and mirrored: the block is symmetric bit for bit.  exact (uniform): spd == 0, the curvature part of H_n is added; else it is left out.
-__global__ void __launch_bounds__(256) k_sphere_assemble(SphereTable S, SphereArgs A, int exact, const double* __restrict__ pos, const double* __restrict__ prev,
-                                                         const int* __restrict__ diag_blk, double* __restrict__ F, double* __restrict__ vals) {
-  const int v = blockIdx.x * blockDim.x + threadIdx.x;
-  if (v >= A.NV) return;
-  const unsigned m = A.mask[v];
-  if (!m) return;
-  const d3 x = ld3(pos, v), xp = ld3(prev, v);
+// [d < eps]: g += k (d - eps) n, H += k n n^T and, where exact, the curvature part of H_n (on a barrel without its part along the rod)
+template <class Head>
+TSL_DEV void sph_normal_block(const Head& c, double k, double eps, int exact, d3& g, Sym3& H) {
+  const SphHead& h = c.sph();
+  const d3 n = h.q / h.rho;
+  const double kd = k * (h.d - eps);
+  g = g + n * kd;
+  H.xx += k * (n.x * n.x); H.xy += k * (n.x * n.y); H.xz += k * (n.x * n.z);
+  H.yy += k * (n.y * n.y); H.yz += k * (n.y * n.z); H.zz += k * (n.z * n.z);
+  if (exact) {
+    const double cr = kd / h.rho;
+    if constexpr (Head::barrel) {
+      const double uu = c.in ? 1.0 / c.ee : 0.0;
+      const d3& e = c.e;
+      H.xx += cr * (1.0 - n.x * n.x - uu * (e.x * e.x)); H.xy -= cr * (n.x * n.y + uu * (e.x * e.y)); H.xz -= cr * (n.x * n.z + uu * (e.x * e.z));
+      H.yy += cr * (1.0 - n.y * n.y - uu * (e.y * e.y)); H.yz -= cr * (n.y * n.z + uu * (e.y * e.z)); H.zz += cr * (1.0 - n.z * n.z - uu * (e.z * e.z));
+    } else {
+      H.xx += cr * (1.0 - n.x * n.x); H.xy -= cr * (n.x * n.y); H.xz -= cr * (n.x * n.z);
+      H.yy += cr * (1.0 - n.y * n.y); H.yz -= cr * (n.y * n.z); H.zz += cr * (1.0 - n.z * n.z);
+    }
+  }
+}
+// [lam > 0]: g += lam a w, H += lam M
+TSL_DEV void sph_friction_block(const SphHead& h, const SphFric& f, d3& g, Sym3& H) {
+  g = g + f.w * (h.lam * f.a);
+  const d3& n0 = f.n0; const d3& w = f.w;
+  H.xx += h.lam * (f.a * (1.0 - n0.x * n0.x) + f.f2r * (w.x * w.x)); H.xy += h.lam * (f.f2r * (w.x * w.y) - f.a * (n0.x * n0.y));
+  H.xz += h.lam * (f.f2r * (w.x * w.z) - f.a * (n0.x * n0.z)); H.yy += h.lam * (f.a * (1.0 - n0.y * n0.y) + f.f2r * (w.y * w.y));
+  H.yz += h.lam * (f.f2r * (w.y * w.z) - f.a * (n0.y * n0.z)); H.zz += h.lam * (f.a * (1.0 - n0.z * n0.z) + f.f2r * (w.z * w.z));
+}
+// the pair functions of a Shape (k_shape.hpp) that a ball and a rod share, on the pair's head; S: the kind's table, for k, eps, eh
+template <class Head, class Tab>
+TSL_DEV void sph_assemble_pair(const Head& c, const Tab& S, const d3& x, const d3& xp, int exact, d3& g, Sym3& H) {
+  const SphHead& h = c.sph();
+  if (!h.ok || (!h.act && !(h.lam > 0.0))) return;
+  if (h.act) sph_normal_block(c, S.k, S.eps, exact, g, H);
+  if (h.lam > 0.0) sph_friction_block(h, sph_fric(h, x, xp, S.eh), g, H);
+}
+template <class Tab>
+TSL_DEV void sph_energy_pair(const SphHead& h, const Tab& S, const d3& x, const d3& xp, double& e) {
+  if (!h.ok || (!h.act && !(h.lam > 0.0))) return;
+  if (h.act) e += 0.5 * S.k * (h.d - S.eps) * (h.d - S.eps);
+  if (h.lam > 0.0) e += h.lam * fr_f0(sph_fric(h, x, xp, S.eh).r, S.eh);
+}
+// the pair's gradient g, asked for where h.ok && (h.act || h.lam > 0)
+template <class Tab>
+TSL_DEV d3 sph_pair_g(const SphHead& h, const Tab& S, const d3& x, const d3& xp) {
   d3 g(0.0, 0.0, 0.0);
-  double hxx = 0.0, hxy = 0.0, hxz = 0.0, hyy = 0.0, hyz = 0.0, hzz = 0.0;
-  for (int j = 0; j < S.n; j++) {
-    if (!((m >> j) & 1u)) continue;
-    const SphHead h = sph_head(S, j, x, xp);
-    if (!h.ok || (!h.act && !(h.lam > 0.0))) continue;
-    if (h.act) {
-      const d3 n = h.q / h.rho;
-      const double kd = S.k * (h.d - S.eps);
-      g = g + n * kd;
-      hxx += S.k * (n.x * n.x); hxy += S.k * (n.x * n.y); hxz += S.k * (n.x * n.z);
-      hyy += S.k * (n.y * n.y); hyz += S.k * (n.y * n.z); hzz += S.k * (n.z * n.z);
-      if (exact) {
-        const double cr = kd / h.rho;
-        hxx += cr * (1.0 - n.x * n.x); hxy -= cr * (n.x * n.y); hxz -= cr * (n.x * n.z);
-        hyy += cr * (1.0 - n.y * n.y); hyz -= cr * (n.y * n.z); hzz += cr * (1.0 - n.z * n.z);
-      }
-    }
-    if (h.lam > 0.0) {
-      const SphFric f = sph_fric(h, x, xp, S.eh);
-      g = g + f.w * (h.lam * f.a);
-      const d3& n0 = f.n0; const d3& w = f.w;
-      hxx += h.lam * (f.a * (1.0 - n0.x * n0.x) + f.f2r * (w.x * w.x)); hxy += h.lam * (f.f2r * (w.x * w.y) - f.a * (n0.x * n0.y));
-      hxz += h.lam * (f.f2r * (w.x * w.z) - f.a * (n0.x * n0.z)); hyy += h.lam * (f.a * (1.0 - n0.y * n0.y) + f.f2r * (w.y * w.y));
-      hyz += h.lam * (f.f2r * (w.y * w.z) - f.a * (n0.y * n0.z)); hzz += h.lam * (f.a * (1.0 - n0.z * n0.z) + f.f2r * (w.z * w.z));
-    }
+  if (h.act) g = g + (h.q / h.rho) * (S.k * (h.d - S.eps));
+  if (h.lam > 0.0) {
+    const SphFric f = sph_fric(h, x, xp, S.eh);
+    g = g + f.w * (h.lam * f.a);
   }
-  if (F) st3(F, v, ld3(F, v) + g);
-  const size_t base = (size_t)diag_blk[v];
-  vals[base + 64 * 0] += hxx; vals[base + 64 * 1] += hxy; vals[base + 64 * 2] += hxz;
-  vals[base + 64 * 3] += hxy; vals[base + 64 * 4] += hyy; vals[base + 64 * 5] += hyz;
-  vals[base + 64 * 6] += hxz; vals[base + 64 * 7] += hyz; vals[base + 64 * 8] += hzz;
+  return g;
 }
 
-// one partial per workgroup (wg_join), behind the collider partials; k_energy_final adds them in its fixed order
-__global__ void __launch_bounds__(256) k_sphere_energy(SphereTable S, SphereArgs A, const double* __restrict__ pos, const double* __restrict__ prev,
-                                                       double* __restrict__ e_part) {
-  const int v = blockIdx.x * blockDim.x + threadIdx.x;
-  double e[1] = {0.0};
-  const unsigned m = v < A.NV ? A.mask[v] : 0u;
-  if (m) {
-    const d3 x = ld3(pos, v), xp = ld3(prev, v);
-    for (int j = 0; j < S.n; j++) {
-      if (!((m >> j) & 1u)) continue;
-      const SphHead h = sph_head(S, j, x, xp);
-      if (!h.ok || (!h.act && !(h.lam > 0.0))) continue;
-      if (h.act) e[0] += 0.5 * S.k * (h.d - S.eps) * (h.d - S.eps);
-      if (h.lam > 0.0) e[0] += h.lam * fr_f0(sph_fric(h, x, xp, S.eh).r, S.eh);
-    }
+struct SphereShape {
+  using Table = SphereTable;
+  static constexpr int stride = 8, n_force = 3, n_grad = 8;
+  static TSL_DEV void assemble(const Table& S, int j, const d3& x, const d3& xp, int exact, d3& g, Sym3& H) {
+    sph_assemble_pair(sph_head(S, j, x, xp), S, x, xp, exact, g, H);
   }
-  wg_join<1>(e, e_part + blockIdx.x);
-}
-
-// p with its frozen dofs zeroed
-TSL_DEV d3 sph_free_p(const int* __restrict__ frozen, const double* __restrict__ p, int v) {
-  const int* __restrict__ fz = frozen + 3 * (size_t)v;
-  const d3 pr = ld3(p, v);
-  return d3(fz[0] ? 0.0 : pr.x, fz[1] ? 0.0 : pr.y, fz[2] ? 0.0 : pr.z);
-}
-
-// The reverse step: pos = x_s, prev = x_{s-1}, p the adjoint solution (its frozen dofs do not count), the centres and previous centres of step s in
-// the table.  Into the vertex's own row of pos_grad[s-1], on free dofs:  += sum_j lam M p_v - L^T p_v = -(dg / dx_prev)^T p_v.  In front of k_adj_prev.
-__global__ void __launch_bounds__(256) k_sphere_backprop(SphereTable S, SphereArgs A, const int* __restrict__ frozen, const double* __restrict__ pos,
-                                                         const double* __restrict__ prev, const double* __restrict__ p, double* __restrict__ pg_prev) {
-  const int v = blockIdx.x * blockDim.x + threadIdx.x;
-  if (v >= A.NV) return;
-  const unsigned m = A.mask[v];
-  if (!m) return;
-  const int* __restrict__ fz = frozen + 3 * (size_t)v;
-  const d3 pv = sph_free_p(frozen, p, v);
-  const d3 x = ld3(pos, v), xp = ld3(prev, v);
-  d3 acc(0.0, 0.0, 0.0);
-  for (int j = 0; j < S.n; j++) {
-    if (!((m >> j) & 1u)) continue;
+  static TSL_DEV void energy(const Table& S, int j, const d3& x, const d3& xp, double& e) { sph_energy_pair(sph_head(S, j, x, xp), S, x, xp, e); }
+  // lam M p_v - L^T p_v = -(dg / dx_prev)^T p_v, the centres and previous centres of step s in the table
+  static TSL_DEV void backprop(const Table& S, int j, const d3& x, const d3& xp, const d3& pv, d3& acc) {
     const SphHead h = sph_head(S, j, x, xp);
-    if (!h.ok || !(h.lam > 0.0)) continue;   // (lam > 0 implies d0 < eps and mu > 0)
+    if (!h.ok || !(h.lam > 0.0)) return;   // (lam > 0 implies d0 < eps and mu > 0)
     acc = acc + sph_prev_term(h, sph_fric(h, x, xp, S.eh), S.k, S.eps, pv);
   }
-  const d3 o = ld3(pg_prev, v);
-  st3(pg_prev, v, d3(fz[0] ? o.x : o.x + acc.x, fz[1] ? o.y : o.y + acc.y, fz[2] ? o.z : o.z + acc.z));
-}
-
-// Read-outs.  A workgroup writes SPHERE_SLOTS partials, 8 per sphere; the spheres are joined one after the other (wg_join<8> / wg_join<3>), so that a
-// lane holds the sums of one sphere at a time; k_sphere_join adds the partials in workgroup order.
-#define SPHERE_SLOTS (8 * TSL_MAX_SPHERES)
-// tsl_sphere_grad, slots 8 j ..: this reverse step's share of d(loss)/d(c_j) (3: (H_n + lam M) p_v, H_n exact), d(loss)/d(cp_j) (3: -(lam M p_v - L^T p_v)),
-// d(loss)/d(mu_j) (-p_v . k max(0, eps - d0) a w), d(loss)/d(R_j) (-p_v . (-[d < eps] k n + [d0 < eps] mu k a w)), summed over the vertices.  Free dofs of p only.
-__global__ void __launch_bounds__(256) k_sphere_grad(SphereTable S, SphereArgs A, const int* __restrict__ frozen, const double* __restrict__ pos,
-                                                     const double* __restrict__ prev, const double* __restrict__ p, double* __restrict__ part) {
-  const int v = blockIdx.x * blockDim.x + threadIdx.x;
-  const unsigned m = v < A.NV ? A.mask[v] : 0u;
-  d3 pv, x, xp;
-  if (m) { pv = sph_free_p(frozen, p, v); x = ld3(pos, v); xp = ld3(prev, v); }
-  for (int j = 0; j < S.n; j++) {   // (uniform)
-    double s[8];
-#pragma unroll
-    for (int q = 0; q < 8; q++) s[q] = 0.0;
-    if ((m >> j) & 1u) {
-      const SphHead h = sph_head(S, j, x, xp);
-      if (h.ok && (h.act || h.pen > 0.0)) {
-        d3 gc(0.0, 0.0, 0.0);
-        if (h.act) {
-          gc = sph_Hn(h, S.k, S.eps, pv);
-          s[7] = S.k * dot(h.q, pv) / h.rho;
-        }
-        if (h.pen > 0.0) {
-          const SphFric f = sph_fric(h, x, xp, S.eh);
-          const double paw = f.a * dot(f.w, pv);
-          if (h.lam > 0.0) {
-            gc = gc + sph_M(f, pv) * h.lam;
-            const d3 gp = sph_prev_term(h, f, S.k, S.eps, pv);
-            s[3] = -gp.x; s[4] = -gp.y; s[5] = -gp.z;
-          }
-          s[6] = -((S.k * h.pen) * paw);
-          if (h.d0 < S.eps) s[7] -= (h.mu * S.k) * paw;
-        }
-        s[0] = gc.x; s[1] = gc.y; s[2] = gc.z;
-      }
+  // tsl_sphere_force: -g_v of sphere j, the force the ball applies to the cloth
+  static TSL_DEV void force(const Table& S, int j, const d3& x, const d3& xp, double (&s)[3]) {
+    const SphHead h = sph_head(S, j, x, xp);
+    if (h.ok && (h.act || h.lam > 0.0)) {
+      const d3 g = sph_pair_g(h, S, x, xp);
+      s[0] = -g.x; s[1] = -g.y; s[2] = -g.z;
     }
-    wg_join<8>(s, part + (size_t)SPHERE_SLOTS * blockIdx.x + 8 * j);
-    __syncthreads();   // (the LDS of wg_join is used again for the next sphere)
   }
-}
-// tsl_sphere_force, slots 8 j .. 8 j + 2: -sum_v g_v of sphere j, the net force the ball applies to the cloth (the sign of k_collider_force); frozen dofs are not
-// masked
-__global__ void __launch_bounds__(256) k_sphere_force(SphereTable S, SphereArgs A, const double* __restrict__ pos, const double* __restrict__ prev,
-                                                      double* __restrict__ part) {
-  const int v = blockIdx.x * blockDim.x + threadIdx.x;
-  const unsigned m = v < A.NV ? A.mask[v] : 0u;
-  d3 x, xp;
-  if (m) { x = ld3(pos, v); xp = ld3(prev, v); }
-  for (int j = 0; j < S.n; j++) {   // (uniform)
-    double s[3] = {0.0, 0.0, 0.0};
-    if ((m >> j) & 1u) {
-      const SphHead h = sph_head(S, j, x, xp);
-      if (h.ok && (h.act || h.lam > 0.0)) {
-        d3 g(0.0, 0.0, 0.0);
-        if (h.act) g = g + (h.q / h.rho) * (S.k * (h.d - S.eps));
+  // tsl_sphere_grad: this reverse step's share of d(loss)/d(c_j) (3: (H_n + lam M) p_v, H_n exact), d(loss)/d(cp_j) (3: -(lam M p_v - L^T p_v)),
+  // d(loss)/d(mu_j) (-p_v . k max(0, eps - d0) a w), d(loss)/d(R_j) (-p_v . (-[d < eps] k n + [d0 < eps] mu k a w))
+  static TSL_DEV void grad(const Table& S, int j, const d3& x, const d3& xp, const d3& pv, double (&s)[8]) {
+    const SphHead h = sph_head(S, j, x, xp);
+    if (h.ok && (h.act || h.pen > 0.0)) {
+      d3 gc(0.0, 0.0, 0.0);
+      if (h.act) {
+        gc = sph_Hn(h, S.k, S.eps, pv);
+        s[7] = S.k * dot(h.q, pv) / h.rho;
+      }
+      if (h.pen > 0.0) {
+        const SphFric f = sph_fric(h, x, xp, S.eh);
+        const double paw = f.a * dot(f.w, pv);
         if (h.lam > 0.0) {
-          const SphFric f = sph_fric(h, x, xp, S.eh);
-          g = g + f.w * (h.lam * f.a);
+          gc = gc + sph_M(f, pv) * h.lam;
+          const d3 gp = sph_prev_term(h, f, S.k, S.eps, pv);
+          s[3] = -gp.x; s[4] = -gp.y; s[5] = -gp.z;
         }
-        s[0] = -g.x; s[1] = -g.y; s[2] = -g.z;
+        s[6] = -((S.k * h.pen) * paw);
+        if (h.d0 < S.eps) {
+#pragma clang fp contract(off)   // (the product rounded on its own: it is the one sph_prev_term forms, not a part of an fma here)
+          s[7] -= (h.mu * S.k) * paw;
+        }
       }
+      s[0] = gc.x; s[1] = gc.y; s[2] = gc.z;
     }
-    wg_join<3>(s, part + (size_t)SPHERE_SLOTS * blockIdx.x + 8 * j);
-    __syncthreads();
   }
-}
-// out[per j + i] = part[0][8 j + i] + part[1][8 j + i] + ..., in workgroup order, for j < n, i < per: one lane per slot
-__global__ void k_sphere_join(int n_wg, int n, int per, const double* __restrict__ part, double* __restrict__ out) {
-  const int q = threadIdx.x, j = q >> 3, i = q & 7;
-  if (j >= n || i >= per) return;
-  double t = 0.0;
-  for (int w = 0; w < n_wg; w++) t += part[(size_t)SPHERE_SLOTS * w + q];
-  out[per * j + i] = t;
-}
+};

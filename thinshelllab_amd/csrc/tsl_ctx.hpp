@@ -206,6 +206,16 @@ struct DirectSolver {
   }
 };
 
+// One kind of collider as the context keeps it: the table (tab.n shapes; its k, eps, eh are filled in per launch), the kind's stiffness, the
+// per-vertex mask (NV), and the partials (SHAPE_MAX * stride per workgroup of 256 vertices) and the result (SHAPE_MAX * stride) of the read-outs
+template <class Table>
+struct ShapeSet {
+  Table tab{};
+  double k = 0.0;
+  DevBuf<unsigned char> mask;
+  DevBuf<double> part, out;
+};
+
 struct tsl_group;
 struct tsl_ctx {
   tsl_group* group = nullptr;   // set while the context is a member of a scene group (its matrix, right-hand side / solution vectors and fronts are views into the group's memory)
@@ -401,24 +411,12 @@ struct tsl_ctx {
   double k_tie = 0.0;
   DevBuf<int> ti_idx;                  // n x 4 (t0, t1, t2, v)
   DevBuf<double> ti_b, ti_w, ti_out;   // n x 3, n, n x 3 (read-outs of tsl_tie_force / tsl_tie_residuals / tsl_tie_grad)
-  // ---- half-space colliders (tsl_set_colliders, k_collider.hpp): the plane table (col.n planes; its k, eps, eh are filled in per launch), the
-  // per-vertex mask, and the partials and the result of the read-outs.  The collider kernels run while col.n > 0 and k_collider != 0
-  ColliderPlanes col{};
-  double k_collider = 0.0;
-  DevBuf<unsigned char> col_mask;      // NV
-  DevBuf<double> col_part, col_out;    // COLLIDER_SLOTS per workgroup of 256 vertices; COLLIDER_SLOTS
-  // ---- sphere colliders (tsl_set_spheres, k_sphere.hpp): the table (sph.n balls, centres and previous centres; its k, eps, eh are filled in per
-  // launch), the per-vertex mask, and the partials and the result of the read-outs.  The sphere kernels run while sph.n > 0 and k_sphere != 0
-  SphereTable sph{};
-  double k_sphere = 0.0;
-  DevBuf<unsigned char> sph_mask;      // NV
-  DevBuf<double> sph_part, sph_out;    // SPHERE_SLOTS per workgroup of 256 vertices; SPHERE_SLOTS
-  // ---- capsule colliders (tsl_set_capsules, k_capsule.hpp): the table (cap.n rods, endpoints and previous endpoints; its k, eps, eh are filled in per
-  // launch), the per-vertex mask, and the partials and the result of the read-outs.  The capsule kernels run while cap.n > 0 and k_capsule != 0
-  CapsuleTable cap{};
-  double k_capsule = 0.0;
-  DevBuf<unsigned char> cap_mask;      // NV
-  DevBuf<double> cap_part, cap_out;    // CAPSULE_SLOTS per workgroup of 256 vertices; CAPSULE_SLOTS
+  // ---- colliders (collider_api.hpp; k_shape.hpp): one set per kind -- planes (tsl_set_colliders, k_collider.hpp), balls (tsl_set_spheres,
+  // k_sphere.hpp: centres and previous centres), rods (tsl_set_capsules, k_capsule.hpp: endpoints and previous endpoints).  A kind's kernels run
+  // while tab.n > 0 and k != 0
+  ShapeSet<ColliderPlanes> col;
+  ShapeSet<SphereTable> sph;
+  ShapeSet<CapsuleTable> cap;
 
   // ---- multigrid preconditioner
   std::vector<MgCloth*> mg;

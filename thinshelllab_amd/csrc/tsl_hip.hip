@@ -54,8 +54,6 @@ static inline int gsz(size_t n) { size_t b = (n + 255) / 256; return (int)std::m
 #include "handle_api.hpp"
 #include "tie_api.hpp"
 #include "collider_api.hpp"
-#include "sphere_api.hpp"
-#include "capsule_api.hpp"
 #include "k_scene.hpp"
 
 // ------------------------------------------------------------------------------------------------
@@ -284,17 +282,9 @@ extern "C" int tsl_set_param(tsl_ctx* c, const char* key, double v) {
     c->k_tie = v;
     TSL_TRY(tie_slots_refresh(c));   // (the tie slots exist while k_tie != 0)
   }
-  else if (k == "k_collider") {
-    if (!(v >= 0.0) || !std::isfinite(v)) return tsl_fail("tsl_set_param: k_collider must be finite and >= 0 (got %g)", v);
-    c->k_collider = v;
-  }
-  else if (k == "k_sphere") {
-    if (!(v >= 0.0) || !std::isfinite(v)) return tsl_fail("tsl_set_param: k_sphere must be finite and >= 0 (got %g)", v);
-    c->k_sphere = v;
-  }
-  else if (k == "k_capsule") {
-    if (!(v >= 0.0) || !std::isfinite(v)) return tsl_fail("tsl_set_param: k_capsule must be finite and >= 0 (got %g)", v);
-    c->k_capsule = v;
+  else if (k == "k_collider" || k == "k_sphere" || k == "k_capsule") {
+    if (!(v >= 0.0) || !std::isfinite(v)) return tsl_fail("tsl_set_param: %s must be finite and >= 0 (got %g)", key, v);
+    (k == "k_collider" ? c->col.k : k == "k_sphere" ? c->sph.k : c->cap.k) = v;
   }
   else if (k == "cg_tol") c->cg_tol = v;
   else if (k == "cg_maxit") c->cg_maxit = (int)v;
@@ -374,11 +364,7 @@ static int energy_async(tsl_ctx* c, const double* pos, const double* prev, const
   const int nb1 = nblk(nmax, 256), nb2 = nvf > 0 ? nblk(nvf, 64) : 0, nb3 = c->nc_ee > 0 ? nblk(c->nc_ee, 64) : 0;
   const int nb4 = handles_on(c) ? nblk(c->n_handle, 256) : 0;   // soft handles: their partials behind the contact ones
   const int nb5 = ties_on(c) ? nblk(c->n_tie, 64) : 0;          // ties: one partial per wave, behind the handle ones
-  const int nb6 = colliders_on(c) ? collider_nblk(c) : 0;       // colliders: one partial per workgroup of 256 vertices, behind the tie ones
-  const int nb7 = spheres_on(c) ? sphere_nblk(c) : 0;           // spheres: one partial per workgroup of 256 vertices, behind the collider ones
-  const int nb8 = capsules_on(c) ? capsule_nblk(c) : 0;         // capsules: likewise, behind the sphere ones
-  const size_t n_part = (size_t)nb1 + (size_t)nblk(c->max_n_constraints, 64) + 1 + (size_t)nblk(c->n_handle, 256) + (size_t)nblk(c->n_tie, 64) + (size_t)(c->col.n > 0 ? collider_nblk(c) : 0) +
-                        (size_t)(c->sph.n > 0 ? sphere_nblk(c) : 0) + (size_t)(c->cap.n > 0 ? capsule_nblk(c) : 0);
+  const size_t n_part = (size_t)nb1 + (size_t)nblk(c->max_n_constraints, 64) + 1 + (size_t)nblk(c->n_handle, 256) + (size_t)nblk(c->n_tie, 64) + (size_t)shapes_present(c) * shape_nblk(c);
   if (c->e_part.n < n_part) { if (c->e_part.alloc(n_part)) return -1; }
   if (c->n_stvk > 0) hipLaunchKernelGGL(k_energy_stvk, dim3(nb1), dim3(256), 0, s, vert_args(c), cloth_args(c), tet_args(c), pos, prev, vel, ref, c->e_part.p, stvk_args(c));
   else hipLaunchKernelGGL(k_energy, dim3(nb1), dim3(256), 0, s, vert_args(c), cloth_args(c), tet_args(c), pos, prev, vel, ref, c->e_part.p);
@@ -386,10 +372,9 @@ static int energy_async(tsl_ctx* c, const double* pos, const double* prev, const
   if (nb3 > 0) hipLaunchKernelGGL(k_ee_energy, dim3(nb3), dim3(64), 0, s, c->nc_ee, ee_args(contact_args(c), nvf), pos, c->e_part.p + nb1 + nb2);
   if (nb4 > 0) handle_dispatch(c, [&](auto NC) { hipLaunchKernelGGL(k_handle_energy<NC>, dim3(nb4), dim3(256), 0, s, handle_args(c), pos, c->e_part.p + nb1 + nb2 + nb3); });
   if (nb5 > 0) hipLaunchKernelGGL(k_tie_energy, dim3(nblk(c->n_tie, 256)), dim3(256), 0, s, tie_args(c), pos, c->e_part.p + nb1 + nb2 + nb3 + nb4);
-  if (nb6 > 0) collider_energy_launch(c, s, pos, prev, c->e_part.p + nb1 + nb2 + nb3 + nb4 + nb5);
-  if (nb7 > 0) sphere_energy_launch(c, s, pos, prev, c->e_part.p + nb1 + nb2 + nb3 + nb4 + nb5 + nb6);
-  if (nb8 > 0) capsule_energy_launch(c, s, pos, prev, c->e_part.p + nb1 + nb2 + nb3 + nb4 + nb5 + nb6 + nb7);
-  hipLaunchKernelGGL(k_energy_final, dim3(1), dim3(256), 0, s, nb1 + nb2 + nb3 + nb4 + nb5 + nb6 + nb7 + nb8, (const double*)c->e_part.p, &SC(c)->energy);
+  // colliders: one partial per workgroup of 256 vertices and kind (planes, balls, rods), behind the tie ones
+  const int nb6 = shapes_energy_launch(c, s, pos, prev, c->e_part.p + nb1 + nb2 + nb3 + nb4 + nb5);
+  hipLaunchKernelGGL(k_energy_final, dim3(1), dim3(256), 0, s, nb1 + nb2 + nb3 + nb4 + nb5 + nb6, (const double*)c->e_part.p, &SC(c)->energy);
   return 0;
 }
 static int energy_sync(tsl_ctx* c, const double* pos, const double* prev, const double* vel, const double* ref, double* E) {
@@ -465,9 +450,7 @@ static int assemble_enqueue(tsl_ctx* c, const double* pos, const double* prev, c
   }
   hipLaunchKernelGGL(k_vert_hess, dim3(nblk(NV, 256)), dim3(256), 0, s, VA, c->diag_blk.p, c->vals_full.p);      // (the mass diagonal: the first contribution to its blocks)
   handle_assemble_launch(c, s, pos, grad);
-  collider_assemble_launch(c, s, pos, prev, grad);
-  sphere_assemble_launch(c, s, spd, pos, prev, grad);
-  capsule_assemble_launch(c, s, spd, pos, prev, grad);
+  shapes_assemble_launch(c, s, spd, pos, prev, grad);
   if (grad) {
     if (c->n_cface) cloth_grad_face_launch(c, s, CA, pos);
     if (c->n_hinge) hipLaunchKernelGGL(k_cloth_grad_hinge, dim3(nblk(c->n_hinge, 256)), dim3(256), 0, s, CA, pos, ref);
@@ -540,9 +523,7 @@ static int assemble_enqueue_early(tsl_ctx* c, const double* pos, const double* p
   }
   hipLaunchKernelGGL(k_vert_hess, dim3(nblk(NV, 256)), dim3(256), 0, s, VA, c->diag_blk.p, c->vals_full.p);   // (the mass diagonal: the first contribution to its blocks)
   handle_assemble_launch(c, s, pos, grad);   // (on the stream of the vertex terms, in front of ev_fork: the gathers and masks of the other streams wait for it as they do for those)
-  collider_assemble_launch(c, s, pos, prev, grad);
-  sphere_assemble_launch(c, s, spd, pos, prev, grad);
-  capsule_assemble_launch(c, s, spd, pos, prev, grad);
+  shapes_assemble_launch(c, s, spd, pos, prev, grad);
   HIP_OK(hipEventRecord(c->ev_fork, s));   // normals, vertex gradient and mass diagonal are in place
   if (c->n_cface) {
     const int nq = (int)c->h_cloth.size() * 9;

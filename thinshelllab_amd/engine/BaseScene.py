@@ -127,12 +127,54 @@ def validate_ties(tot_NV, faces_tab, vertex_ids, face_ids, bary, weights=None):
     return v.astype(np.int32), f.astype(np.int32), np.ascontiguousarray(b), w
 
 
-TSL_MAX_COLLIDERS = 8
+SHAPE_MAX = 8   # colliders of one kind: one bit each in a vertex's mask byte (csrc/shape_host.hpp)
+TSL_MAX_COLLIDERS = TSL_MAX_SPHERES = TSL_MAX_CAPSULES = SHAPE_MAX
+
+
+def _check_shape(who, noun, j, mu, radius=None):
+    """the radius (where the kind has one) and the friction coefficient of shape j, with the messages of csrc/shape_host.hpp"""
+    if radius is not None and not (np.isfinite(radius) and radius > 0.0):
+        raise ValueError(f"{who}: radius {radius:g} of {noun} {j} is not finite and positive")
+    if not (mu >= 0.0 and np.isfinite(mu)):
+        raise ValueError(f"{who}: friction coefficient {mu:g} of {noun} {j} is negative or not finite")
+
+
+def _check_count(who, noun, n):
+    if n > SHAPE_MAX:
+        raise ValueError(f"{who}: {n} {noun}s: at most {SHAPE_MAX}")
+
+
+def _check_k(who, name, k):
+    """the stiffness of a collider kind as a float, with the message of tsl_set_param"""
+    k = float(k)
+    if not (k >= 0.0 and np.isfinite(k)):
+        raise ValueError(f"{who}: {name} must be finite and >= 0 (got {k:g})")
+    return k
+
+
+def _shape_mask(who, noun, tot_NV, n, vertex_ids):
+    """The uint8 mask (tot_NV), bit j: shape j acts on the vertex.  vertex_ids None: every shape on every vertex; else one entry per shape, None (all
+    vertices) or a list of global vertex ids; ValueError for a wrong number of lists or an id out of range"""
+    mask = np.full(tot_NV, (1 << n) - 1, np.uint8)
+    if vertex_ids is not None:
+        if len(vertex_ids) != n:
+            raise ValueError(f"{who}: {len(vertex_ids)} vertex lists for {n} {noun}s")
+        mask[:] = 0
+        for j, ids in enumerate(vertex_ids):
+            if ids is None:
+                mask |= np.uint8(1 << j)
+                continue
+            v = np.asarray(ids, dtype=np.int64).reshape(-1)
+            for vi in v.tolist():
+                if vi < 0 or vi >= tot_NV:
+                    raise ValueError(f"{who}: vertex {vi} of {noun} {j} out of range [0, {tot_NV})")
+            mask[v] |= np.uint8(1 << j)
+    return mask
 
 
 def validate_colliders(tot_NV, normals, offsets, mu, vertex_ids=None):
     """The checks of tsl_set_colliders on the host, with the messages of csrc/collider_host.hpp: returns (unit normals (n, 3), offsets (n), mu (n),
-    uint8 mask (tot_NV)) or raises ValueError naming the offender -- more than TSL_MAX_COLLIDERS colliders, a zero or non-finite normal, a non-finite
+    uint8 mask (tot_NV)) or raises ValueError naming the offender -- more than SHAPE_MAX colliders, a zero or non-finite normal, a non-finite
     offset, a negative or non-finite friction coefficient, a vertex id out of range.  vertex_ids None: every collider acts on every vertex; else one
     entry per collider, None (all vertices) or a list of global vertex ids."""
     o = np.asarray(offsets, dtype=np.float64).reshape(-1)
@@ -141,8 +183,7 @@ def validate_colliders(tot_NV, normals, offsets, mu, vertex_ids=None):
     m = np.asarray(mu, dtype=np.float64).reshape(-1)
     if nr.shape != (n, 3) or m.shape != (n,):
         raise ValueError(f"set_colliders: {len(nr)} normals and {m.size} friction coefficients for {n} offsets")
-    if n > TSL_MAX_COLLIDERS:
-        raise ValueError(f"set_colliders: {n} colliders: at most {TSL_MAX_COLLIDERS}")
+    _check_count("set_colliders", "collider", n)
     unit = np.zeros((n, 3))
     for j in range(n):
         length = float(np.sqrt((nr[j, 0] * nr[j, 0] + nr[j, 1] * nr[j, 1]) + nr[j, 2] * nr[j, 2]))
@@ -150,32 +191,14 @@ def validate_colliders(tot_NV, normals, offsets, mu, vertex_ids=None):
             raise ValueError(f"set_colliders: normal ({nr[j, 0]:g}, {nr[j, 1]:g}, {nr[j, 2]:g}) of collider {j} is zero or not finite")
         if not np.isfinite(o[j]):
             raise ValueError(f"set_colliders: offset {o[j]:g} of collider {j} is not finite")
-        if not (m[j] >= 0.0 and np.isfinite(m[j])):
-            raise ValueError(f"set_colliders: friction coefficient {m[j]:g} of collider {j} is negative or not finite")
+        _check_shape("set_colliders", "collider", j, m[j])
         unit[j] = nr[j] / length
-    mask = np.full(tot_NV, (1 << n) - 1, np.uint8)
-    if vertex_ids is not None:
-        if len(vertex_ids) != n:
-            raise ValueError(f"set_colliders: {len(vertex_ids)} vertex lists for {n} colliders")
-        mask[:] = 0
-        for j, ids in enumerate(vertex_ids):
-            if ids is None:
-                mask |= np.uint8(1 << j)
-                continue
-            v = np.asarray(ids, dtype=np.int64).reshape(-1)
-            for vi in v.tolist():
-                if vi < 0 or vi >= tot_NV:
-                    raise ValueError(f"set_colliders: vertex {vi} of collider {j} out of range [0, {tot_NV})")
-            mask[v] |= np.uint8(1 << j)
-    return unit, o.copy(), m.copy(), mask
-
-
-TSL_MAX_SPHERES = 8
+    return unit, o.copy(), m.copy(), _shape_mask("set_colliders", "collider", tot_NV, n, vertex_ids)
 
 
 def validate_spheres(tot_NV, centres, radii, mu, vertex_ids=None):
     """The checks of tsl_set_spheres on the host, with the messages of csrc/sphere_host.hpp: returns (centres (n, 3), radii (n), mu (n), uint8 mask
-    (tot_NV)) or raises ValueError naming the offender -- more than TSL_MAX_SPHERES spheres, a non-finite centre, a radius that is not finite and
+    (tot_NV)) or raises ValueError naming the offender -- more than SHAPE_MAX spheres, a non-finite centre, a radius that is not finite and
     positive, a negative or non-finite friction coefficient, a vertex id out of range.  vertex_ids None: every sphere acts on every vertex; else one
     entry per sphere, None (all vertices) or a list of global vertex ids."""
     r = np.asarray(radii, dtype=np.float64).reshape(-1)
@@ -184,33 +207,14 @@ def validate_spheres(tot_NV, centres, radii, mu, vertex_ids=None):
     m = np.asarray(mu, dtype=np.float64).reshape(-1)
     if c.shape != (n, 3) or m.shape != (n,):
         raise ValueError(f"set_spheres: {len(c)} centres and {m.size} friction coefficients for {n} radii")
-    if n > TSL_MAX_SPHERES:
-        raise ValueError(f"set_spheres: {n} spheres: at most {TSL_MAX_SPHERES}")
+    _check_count("set_spheres", "sphere", n)
     for j in range(n):
         if not np.isfinite(c[j]).all():
             raise ValueError(f"set_spheres: centre ({c[j, 0]:g}, {c[j, 1]:g}, {c[j, 2]:g}) of sphere {j} is not finite")
-        if not (np.isfinite(r[j]) and r[j] > 0.0):
-            raise ValueError(f"set_spheres: radius {r[j]:g} of sphere {j} is not finite and positive")
-        if not (m[j] >= 0.0 and np.isfinite(m[j])):
-            raise ValueError(f"set_spheres: friction coefficient {m[j]:g} of sphere {j} is negative or not finite")
-    mask = np.full(tot_NV, (1 << n) - 1, np.uint8)
-    if vertex_ids is not None:
-        if len(vertex_ids) != n:
-            raise ValueError(f"set_spheres: {len(vertex_ids)} vertex lists for {n} spheres")
-        mask[:] = 0
-        for j, ids in enumerate(vertex_ids):
-            if ids is None:
-                mask |= np.uint8(1 << j)
-                continue
-            v = np.asarray(ids, dtype=np.int64).reshape(-1)
-            for vi in v.tolist():
-                if vi < 0 or vi >= tot_NV:
-                    raise ValueError(f"set_spheres: vertex {vi} of sphere {j} out of range [0, {tot_NV})")
-            mask[v] |= np.uint8(1 << j)
-    return c.copy(), r.copy(), m.copy(), mask
+        _check_shape("set_spheres", "sphere", j, m[j], r[j])
+    return c.copy(), r.copy(), m.copy(), _shape_mask("set_spheres", "sphere", tot_NV, n, vertex_ids)
 
 
-TSL_MAX_CAPSULES = 8
 CAPSULE_MIN_LEN = 1e-9
 
 
@@ -227,7 +231,7 @@ def _capsule_ends_check(who, what, a, b, j):
 
 def validate_capsules(tot_NV, ends_a, ends_b, radii, mu, vertex_ids=None):
     """The checks of tsl_set_capsules on the host, with the messages of csrc/capsule_host.hpp: returns (a (n, 3), b (n, 3), radii (n), mu (n), uint8
-    mask (tot_NV)) or raises ValueError naming the offender -- more than TSL_MAX_CAPSULES capsules, a non-finite endpoint, a segment shorter than
+    mask (tot_NV)) or raises ValueError naming the offender -- more than SHAPE_MAX capsules, a non-finite endpoint, a segment shorter than
     1e-9 m, a radius that is not finite and positive, a negative or non-finite friction coefficient, a vertex id out of range.  vertex_ids None:
     every capsule acts on every vertex; else one entry per capsule, None (all vertices) or a list of global vertex ids."""
     r = np.asarray(radii, dtype=np.float64).reshape(-1)
@@ -237,31 +241,13 @@ def validate_capsules(tot_NV, ends_a, ends_b, radii, mu, vertex_ids=None):
     m = np.asarray(mu, dtype=np.float64).reshape(-1)
     if a.shape != (n, 3) or b.shape != (n, 3) or m.shape != (n,):
         raise ValueError(f"set_capsules: {len(a)} endpoints a, {len(b)} endpoints b and {m.size} friction coefficients for {n} radii")
-    if n > TSL_MAX_CAPSULES:
-        raise ValueError(f"set_capsules: {n} capsules: at most {TSL_MAX_CAPSULES}")
+    _check_count("set_capsules", "capsule", n)
     for j in range(n):
         bad = _capsule_ends_check("set_capsules", "", a[j], b[j], j)
         if bad:
             raise ValueError(bad)
-        if not (np.isfinite(r[j]) and r[j] > 0.0):
-            raise ValueError(f"set_capsules: radius {r[j]:g} of capsule {j} is not finite and positive")
-        if not (m[j] >= 0.0 and np.isfinite(m[j])):
-            raise ValueError(f"set_capsules: friction coefficient {m[j]:g} of capsule {j} is negative or not finite")
-    mask = np.full(tot_NV, (1 << n) - 1, np.uint8)
-    if vertex_ids is not None:
-        if len(vertex_ids) != n:
-            raise ValueError(f"set_capsules: {len(vertex_ids)} vertex lists for {n} capsules")
-        mask[:] = 0
-        for j, ids in enumerate(vertex_ids):
-            if ids is None:
-                mask |= np.uint8(1 << j)
-                continue
-            v = np.asarray(ids, dtype=np.int64).reshape(-1)
-            for vi in v.tolist():
-                if vi < 0 or vi >= tot_NV:
-                    raise ValueError(f"set_capsules: vertex {vi} of capsule {j} out of range [0, {tot_NV})")
-            mask[v] |= np.uint8(1 << j)
-    return a.copy(), b.copy(), r.copy(), m.copy(), mask
+        _check_shape("set_capsules", "capsule", j, m[j], r[j])
+    return a.copy(), b.copy(), r.copy(), m.copy(), _shape_mask("set_capsules", "capsule", tot_NV, n, vertex_ids)
 
 
 class _SystemMatrix:
@@ -819,9 +805,7 @@ class BaseScene:
         vertex ids.  The normals are normalised and stay fixed; an empty list removes the colliders.  The lists are checked here, before any
         library call."""
         n, o, m, mask = validate_colliders(self.tot_NV, normals, offsets, mu, vertex_ids)
-        k = float(k)
-        if not (k >= 0.0 and np.isfinite(k)):
-            raise ValueError(f"set_colliders: k_collider must be finite and >= 0 (got {k:g})")
+        k = _check_k("set_colliders", "k_collider", k)
         self._col_n, self._col_o, self._col_mu, self._col_mask, self.k_collider = n, o, m, mask, k
         self._dirty.add("colliders")
 
@@ -857,9 +841,7 @@ class BaseScene:
         one entry per sphere, None or a list of global vertex ids.  The balls start at rest (previous centres = centres); the radii stay fixed; an
         empty list removes the spheres.  The lists are checked here, before any library call."""
         c, r, m, mask = validate_spheres(self.tot_NV, centres, radii, mu, vertex_ids)
-        k = float(k)
-        if not (k >= 0.0 and np.isfinite(k)):
-            raise ValueError(f"set_spheres: k_sphere must be finite and >= 0 (got {k:g})")
+        k = _check_k("set_spheres", "k_sphere", k)
         self._sph_c, self._sph_cp, self._sph_cp_step = c, c.copy(), c.copy()
         self._sph_R, self._sph_mu, self._sph_mask, self.k_sphere = r, m, mask, k
         self._dirty.add("spheres")
@@ -912,9 +894,7 @@ class BaseScene:
         vertex; else one entry per capsule, None or a list of global vertex ids.  The rods start at rest (previous endpoints = endpoints); the radii
         stay fixed; an empty list removes the capsules.  The lists are checked here, before any library call."""
         a, b, r, m, mask = validate_capsules(self.tot_NV, ends_a, ends_b, radii, mu, vertex_ids)
-        k = float(k)
-        if not (k >= 0.0 and np.isfinite(k)):
-            raise ValueError(f"set_capsules: k_capsule must be finite and >= 0 (got {k:g})")
+        k = _check_k("set_capsules", "k_capsule", k)
         e = np.stack([a, b], axis=1)
         self._cap_e, self._cap_ep, self._cap_ep_step = e, e.copy(), e.copy()
         self._cap_R, self._cap_mu, self._cap_mask, self.k_capsule = r, m, mask, k
