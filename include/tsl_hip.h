@@ -507,6 +507,37 @@ int tsl_bench_direct(tsl_ctx* ctx, int cls, int reps, double* out4_host);
 int tsl_direct_info(tsl_ctx* ctx, double* out10_host);
 int tsl_direct_counters(tsl_ctx* ctx, double* out_host, int32_t n);
 
+/* ---- the iterative hierarchy taken apart (tests/ only): read-only views of the last preconditioner set-up, and entry points that run one
+ * part of the hierarchy alone.  All four run the set-up a solve would run first if it is stale (block-Jacobi inverse, dense body inverses,
+ * mg_setup_operators), launch no kernel a solve does not launch, and alter no state a solve does not alter.
+ *   tsl_mg_info:   out = {cloth hierarchies H (0 with the multigrid off), dense bodies B (0 while they are not in use);
+ *                  per hierarchy: v_offset, N0, M0, levels L the cycle walks, then per level: N, M, kind;  per dense body: n3}.
+ *                  kind: 0 a level with a coarser one below, else how the last level is solved: 1 dense inverse (k_st_coarse_apply),
+ *                  2 all sweeps in one workgroup (k_st_coarse), 3 one launch per sweep (k_st_spmv5).  Returns the number of values, < 0 if
+ *                  cap is too small.  Level index l in tsl_mg_export = position in this list (l = 0 is the first stencil level).
+ *   tsl_mg_export: array `what` of level `level` of hierarchy `hierarchy` to the host, exactly as the cycle reads it; cap = room in elements;
+ *                  returns the number of elements, < 0 where the level has no such array.
+ *                    TSL_MG_A      double[225 n]  slot-major: A[(s * 9 + e) * n + row], s = (dI + 2) * 5 + (dJ + 2)
+ *                    TSL_MG_DINV   double[9 n]    row-major 3 x 3 per node;  level -1: the level-0 blocks, 9 * tot_NV, ORIGINAL vertex order
+ *                    TSL_MG_OMEGA  double[2]      {omega, lambda};  level -1: level 0;  none on a dense last level
+ *                    TSL_MG_ROWPOS int32[tot_NV]  level -1 only: the solver's row of every vertex (level 0 runs in that order: its power iteration starts
+ *                                                 from a vector that is a function of the row)
+ *                    TSL_MG_A32    float[225 n]   (levels with a coarser one below)
+ *                    TSL_MG_S32    float[441 nc]  S[(s * 9 + e) * nc + crow], s = (dI + 3) * 7 + (dJ + 3)   (same levels)
+ *                    TSL_MG_CINV   float[n3 * n3], TSL_MG_BAD int32[1]: dense last level and its bad-pivot flag
+ *                    TSL_MG_BINV   float[n3 * ld], ld = n3 rounded up to 4, TSL_MG_BAD_BODY int32[1]: dense body `hierarchy` (level ignored)
+ *   tsl_mg_apply:  z = M^-1 r, both 3 * tot_NV device vectors in the caller's vertex order: gather, then what one PCG iteration launches for
+ *                  its preconditioner (mg_vcycle with the body sweep, or block Jacobi / body blocks with the multigrid off), scatter.
+ *   tsl_solve_with: ONE solver of the hierarchy, no successor: method 0 pcg_restarts with the active preconditioner, 1 minres, 2 gmres,
+ *                  3 bicgstab; cap <= 0: "cg_maxit".  stats->flag: 0 (method 0) / 1 (methods 1-3) when the solver met its own stopping rule,
+ *                  3 otherwise; stats->method echoes the argument.  (hierarchy_fallback's rebuild of the preconditioner from the fully projected
+ *                  assembly needs the state of a running time step: like tsl_solve, a call from outside a step runs behind the one in place.) */
+enum { TSL_MG_A = 0, TSL_MG_DINV = 1, TSL_MG_OMEGA = 2, TSL_MG_A32 = 3, TSL_MG_S32 = 4, TSL_MG_CINV = 5, TSL_MG_BAD = 6, TSL_MG_BINV = 7, TSL_MG_BAD_BODY = 8, TSL_MG_ROWPOS = 9 };
+int tsl_mg_info(tsl_ctx* ctx, int32_t* out_host, int32_t cap);
+int tsl_mg_export(tsl_ctx* ctx, int32_t hierarchy, int32_t level, int32_t what, void* host, int64_t cap);
+int tsl_mg_apply(tsl_ctx* ctx, const double* r_dev, double* z_dev);
+int tsl_solve_with(tsl_ctx* ctx, int32_t method, int32_t cap, const double* rhs_dev, double* x_dev, tsl_solve_stats* stats_host);
+
 /* ---- scene groups: several scenes of ONE device whose sparse direct solves share their launches --------------------------------------------
  * The reference's trajectory-optimisation drivers roll out independent copies of one scene (training/trajopt_*.py, one rollout per candidate
  * trajectory); a single 100k-triangle scene leaves most of the chip idle during the latency-bound parts of its factorisation.  A group takes the

@@ -478,6 +478,53 @@ class TslContext:
         n = 3 * (len(rp) - 1)
         return sp.bsr_matrix((vals, col, rp), shape=(n, n)).tocsr()
 
+    # ---- the iterative hierarchy taken apart (tests): tsl_mg_info / tsl_mg_export / tsl_mg_apply / tsl_solve_with
+    MG_ARRAYS = dict(A=(0, np.float64), Dinv=(1, np.float64), omega=(2, np.float64), A32=(3, np.float32), S32=(4, np.float32), Cinv=(5, np.float32),
+                     bad=(6, np.int32), Binv=(7, np.float32), bad_body=(8, np.int32), rowpos=(9, np.int32))
+    MG_KINDS = ("inner", "dense", "one_workgroup", "per_sweep")
+
+    def mg_info(self):
+        """{"hierarchies": [{v_offset, N0, M0, levels: [{N, M, kind}]}], "bodies": [n3, ...]} of the preconditioner as the next solve runs it"""
+        self.refresh_stream()
+        out = np.zeros(256, np.int32)
+        n = check(self.L.tsl_mg_info(self.h, out.ctypes.data, len(out)), "tsl_mg_info")
+        v = [int(t) for t in out[:n]]
+        H, B, k = v[0], v[1], 2
+        hs = []
+        for _ in range(H):
+            h = dict(v_offset=v[k], N0=v[k + 1], M0=v[k + 2], levels=[])
+            nl = v[k + 3]; k += 4
+            for _ in range(nl):
+                h["levels"].append(dict(N=v[k], M=v[k + 1], kind=self.MG_KINDS[v[k + 2]])); k += 3
+            hs.append(h)
+        return dict(hierarchies=hs, bodies=v[k:k + B])
+
+    def mg_export(self, what, hierarchy=0, level=0, size=None):
+        """array `what` (a key of MG_ARRAYS) of one level (-1: level 0) of one hierarchy, or of dense body `hierarchy`, flat, as the cycle reads it"""
+        self.refresh_stream()
+        code, dt = self.MG_ARRAYS[what]
+        cap = int(size) if size is not None else 9 * self.tot_NV * 225
+        out = np.zeros(cap, dt)
+        n = check(self.L.tsl_mg_export(self.h, int(hierarchy), int(level), code, out.ctypes.data, cap), f"tsl_mg_export({what})")
+        return out[:n].copy()
+
+    def mg_apply(self, r, z=None):
+        """z = M^-1 r with the preconditioner a PCG iteration would apply (device vectors, 3 * tot_NV, the caller's vertex order)"""
+        self.refresh_stream()
+        if z is None:
+            z = torch.empty_like(r)
+        check(self.L.tsl_mg_apply(self.h, _ptr(r), _ptr(z)), "tsl_mg_apply")
+        return z
+
+    def solve_with(self, method, rhs, cap=0, x=None):
+        """one solver of the hierarchy alone: 0 PCG (active preconditioner), 1 MINRES, 2 GMRES, 3 BiCGStab; cap 0: "cg_maxit" """
+        self.refresh_stream()
+        if x is None:
+            x = torch.empty_like(rhs)
+        st = SolveStats()
+        check(self.L.tsl_solve_with(self.h, int(method), int(cap), _ptr(rhs), _ptr(x), C.byref(st)), "tsl_solve_with")
+        return x, st.as_dict()
+
     def constraints(self):
         m = self.max_n_constraints + self.tie_count()   # (the tie slots lie behind the detected ones)
         idx = np.zeros((m, 4), np.int32); w = np.zeros((m, 3)); k = np.zeros(m); dx0 = np.zeros((m, 3)); T = np.zeros((m, 6)); n = np.zeros((m, 3)); mu = np.zeros(m)

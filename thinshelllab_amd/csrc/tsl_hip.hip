@@ -4,7 +4,8 @@
 //   and SparseMatrix.solve (sparse_solver.py:85-105).  No kernel is defined here: device code lives in the k_*.hpp headers (k_scene.hpp: energy and
 //   gradient gathers, k_adjoint.hpp: the reverse step), and the entry points of a subject in its own header, included below where what they call is
 //   defined: handle_api.hpp (soft handles), param_api.hpp (read-outs of system identification; its key table and partial layout are host logic in
-//   param_keys.hpp), adjoint_api.hpp (Grad.transfer_grad, analytic_grad_single.py:217-257), direct_host.hpp / direct_group.hpp (sparse direct solve).
+//   param_keys.hpp), adjoint_api.hpp (Grad.transfer_grad, analytic_grad_single.py:217-257), direct_host.hpp / direct_group.hpp (sparse direct solve),
+//   mg_test_api.hpp (views of the iterative hierarchy and its parts run alone, for the tests).
 // There is no CPU fallback in this library: without a HIP device every entry point fails.
 #include <stdarg.h>
 #include <cctype>
@@ -1859,6 +1860,7 @@ extern "C" int tsl_solve(tsl_ctx* c, const double* rhs, double* x, tsl_solve_sta
 }
 
 #include "param_api.hpp"
+#include "mg_test_api.hpp"
 
 // ------------------------------------------------------------------------------------------------
 extern "C" int tsl_update_ref_angle(tsl_ctx* c, const double* pos, double* ref) {
