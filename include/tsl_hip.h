@@ -103,7 +103,7 @@ int tsl_ctx_create(const tsl_scene_desc* desc, tsl_ctx** out);
 void tsl_ctx_destroy(tsl_ctx* ctx);
 int tsl_set_stream(tsl_ctx* ctx, void* hip_stream);
 
-/* 0-d field writes of the reference and the engine's own switches (45 keys + three patterns; an unknown key is an error).
+/* 0-d field writes of the reference and the engine's own switches (46 keys + three patterns; an unknown key is an error).
  *  Scene (trajopt_folding.py:50,66; Scene_folding.py:30-31; geometry.py:8-19; geometry_self.py:166-230):
  *   "cloth<i>.Kb|Kl|Ka|k_angle", "elastic<i>.mu|lam|alpha", "mu_cloth_elastic", "mu_cloth_cloth", "k_contact", "eps_contact", "eps_v", "damping",
  *   "k_handle" (0 default: stiffness in N/m of the soft handles of tsl_set_handles; negative fails; with 0, or with no handles, no handle kernel is launched),
@@ -114,6 +114,8 @@ int tsl_set_stream(tsl_ctx* ctx, void* hip_stream);
  *   spheres, no sphere kernel is launched),
  *   "k_capsule" (0 default: stiffness in N/m shared by the capsule colliders of tsl_set_capsules; negative or non-finite fails; with 0, or with no
  *   capsules, no capsule kernel is launched),
+ *   "k_box" (0 default: stiffness in N/m shared by the rounded-box colliders of tsl_set_boxes; negative or non-finite fails; with 0, or with no
+ *   boxes, no box kernel is launched),
  *   "cloth<i>.membrane" (0 default: edge springs Kl + area term Ka, as the reference; 1: a St. Venant-Kirchhoff membrane per face, A0 Psi(F) with
  *   F = [x1 - x0, x2 - x0] Dm^-1, Dm the rest triangle rebuilt from the face's rest lengths (fails naming a face whose lengths violate the triangle
  *   inequality), Psi = mu |E|^2 + lam/2 tr(E)^2, E = (F^T F - I) / 2, A0 the rest area; it replaces the springs and the area term of the cloth's
@@ -378,6 +380,62 @@ int tsl_set_capsule_ends(tsl_ctx* ctx, const double* a_host, const double* b_hos
 int tsl_capsule_count(tsl_ctx* ctx, int32_t* out_host);
 int tsl_capsule_force(tsl_ctx* ctx, const double* pos_dev, const double* prev_pos_dev, double* out_host);
 int tsl_capsule_grad(tsl_ctx* ctx, const double* pos_dev, const double* prev_pos_dev, const double* p_dev, double* out_host);
+
+/* Rounded-box colliders (no reference counterpart: its table tops are meshed bodies): up to TSL_MAX_BOXES solid boxes with rounded edges and corners
+ * and the cloth outside -- a table top whose edge the cloth hangs over, a shelf, a step, a gripper jaw, a plate that tilts.  Box j has a centre c_j
+ * and an orientation that may be set before every step, a previous pose (where the box was at the start of the step), half extents h_j >= 0 of the
+ * core box and a rounding radius r_j > 0 (the solid is the core box grown by r_j; no sharp box), both fixed once the list is set, and a friction
+ * coefficient mu_j >= 0; the stiffness "k_box" of tsl_set_param is shared (0 by default: off), the thickness of the shell is eps_contact, the
+ * friction regularisation eh = eps_v dt.  A per-vertex 8-bit mask of its own says which boxes act on a vertex.  Poses are a centre and a quaternion
+ * (s, x, y, z), normalised by the library and turned into R (columns u_i: the box axes in the world) once on the host.  For vertex v and box j,
+ * with x_prev the start-of-step positions (the prev_pos argument of tsl_energy / tsl_assemble; x_{s-1} in a reverse step):
+ *   y  = R^T (x - c),        b  = clamp(y, -h, h),    free_i  = [-h_i < y_i < h_i]   (an axis with h_i = 0 is never free)
+ *   q  = R (y - b),  rho = |q|,  n = q / rho,  d = rho - r
+ *   y0 = R0^T (x_prev - cp), b0 = clamp(y0, -h, h),   free0_i = [-h_i < y0_i < h_i]
+ *   q0 = R0 (y0 - b0), rho0, n0, d0 = rho0 - r
+ *   lam = mu k max(0, eps - d0),  dc = (c + R b0) - (cp + R0 b0),  D = (x - x_prev) - dc,  P0 = I - n0 n0^T,  w = P0 D,  r_w = |w|,  a1 = f1(r_w)
+ *   E = [d < eps] 1/2 k (d - eps)^2 + lam f0(r_w),  g = [d < eps] k (d - eps) n + lam a1 w,
+ *   H = H_n + lam M on the vertex's own diagonal block,  H_n = [d < eps] (k n n^T + k (d - eps) / rho (I - n n^T - sum_i free_i u_i u_i^T)),
+ *   M = a1 P0 + [r_w > 1e-9] (f2 / r_w) w w^T.
+ * The slip is relative to the material point of the box under the vertex at the start of the step: a plate that tilts drags the cloth with it.
+ * b0, n0 and lam are constants of the step.  The curvature term vanishes on a face, is the rod's on an edge and the ball's at a corner: half
+ * extents (L/2, 0, 0) give the capsule of length L, (0, 0, 0) the sphere.  tsl_assemble with spd = 0 (the reverse step's operator) adds H_n exact,
+ * every other mode, with and without "spd_literal", adds [d < eps] k n n^T (the eigen-clamp in closed form); lam M is positive semi-definite as it
+ * stands.  No constraint slot, no row list: the plans of the factorisation and tsl_contact_counts do not depend on boxes.  Nothing is stored per
+ * step.  A pair with rho < 1e-12 (a vertex inside the core box, deeper than r) contributes nothing, one with rho0 < 1e-12 has no friction: the
+ * limit of the model.  Frozen dofs follow the mask rule.  One lane per vertex, no atomics: the same bits run to run.  With no boxes or k_box = 0
+ * every launch is the one it was.
+ *   tsl_set_boxes: centres_host (n x 3), quats_host (n x 4), half_extents_host (n x 3), radii_host (n), mu_host (n), vertex_mask_host (tot_NV bytes,
+ *     bit j: box j acts on the vertex; NULL: every box on every vertex); host pointers, copied; the previous poses := the poses; the stream is
+ *     synchronised; n = 0 removes the boxes.  Fails, naming the offender, and leaves the previous list in place for more than TSL_MAX_BOXES boxes or
+ *     n < 0, a non-finite centre, a zero or non-finite quaternion, a negative or non-finite half extent, a radius that is not finite and positive,
+ *     a negative or non-finite mu, a mask byte that names a box at or above n.
+ *   tsl_set_box_poses: centres_host, quats_host and prev_centres_host, prev_quats_host (both NULL: the previous poses := the poses; exactly one
+ *     NULL fails) for the next energy, assemble, step or adjoint step; set those of step s before the reverse step s and before tsl_box_grad.  A
+ *     non-finite centre or a zero or non-finite quaternion fails, naming the box, and leaves all four in place.
+ *   tsl_box_count: n.
+ *   tsl_box_force: out_host (n x 6) at the state (pos, prev_pos): [0:3] -sum_v g_v of box j, the net force the box applies to the cloth, in the
+ *     sign of tsl_sphere_force; [3:6] -sum_v (x_v - c) x g_v, its torque about the box's centre in the same sign; frozen dofs are NOT masked;
+ *     k_box = 0: zeros.
+ *   tsl_box_grad: out_host (n x 14) at the tape state (pos = x_s, prev_pos = x_{s-1}), sign of tsl_sphere_grad, p the adjoint solution on its
+ *     free dofs (p_dev == NULL: the solution of the last tsl_adjoint_step): the share of one reverse step in
+ *       [0:3]  d(loss)/d(c_j)       = sum_v H_n p_v + lam M p_v   (H_n exact),
+ *       [3:6]  d(loss)/d(theta_j)   = sum_v (x - c) x (H_n p_v) + p_v x g_n + (R b0) x (lam M p_v),   g_n = [d < eps] k (d - eps) n,
+ *       [6:9]  d(loss)/d(cp_j)      = -sum_v X,
+ *       [9:12] d(loss)/d(theta_p_j) = sum_v -(x_prev - cp) x X - lam n0 x z + lam q0 x (M p_v),
+ *       [12]   d(loss)/d(mu_j)      = -sum_v p_v . k max(0, eps - d0) a1 w,
+ *       [13]   d(loss)/d(r_j)       = -sum_v p_v . (-[d < eps] k n + [d0 < eps] mu k a1 w),
+ *     with theta, theta_p world-frame rotation vectors applied on the left (R <- exp([theta]x) R, as tsl_frame_grad), B = a1 I + [r_w > 1e-9]
+ *     (f2 / r_w) w w^T, z = -((n0 . D) B p_v + D (n0 . B p_v)), G0 = P0 - sum_i free0_i u0_i u0_i^T, Delta = sum_i free0_i (u_i - u0_i) u0_i^T and
+ *       X = lam (M p_v - G0 z / rho0) + [d0 < eps] mu k n0 (a1 w . p_v) + lam Delta^T M p_v = -(dg/dx_prev)^T p_v,
+ *     which the reverse step itself adds to the free dofs of the vertex's row of pos_grad[s-1].  There is no gradient for the half extents. */
+#define TSL_MAX_BOXES 8
+int tsl_set_boxes(tsl_ctx* ctx, const double* centres_host, const double* quats_host, const double* half_extents_host, const double* radii_host, const double* mu_host, int32_t n,
+                  const uint8_t* vertex_mask_host);
+int tsl_set_box_poses(tsl_ctx* ctx, const double* centres_host, const double* quats_host, const double* prev_centres_host, const double* prev_quats_host);
+int tsl_box_count(tsl_ctx* ctx, int32_t* out_host);
+int tsl_box_force(tsl_ctx* ctx, const double* pos_dev, const double* prev_pos_dev, double* out_host);
+int tsl_box_grad(tsl_ctx* ctx, const double* pos_dev, const double* prev_pos_dev, const double* p_dev, double* out_host);
 
 /* BaseScene.compute_energy (BaseScene.py:427-451) at the given state, constraints as last detected. */
 int tsl_energy(tsl_ctx* ctx, const double* pos_dev, const double* prev_pos_dev, const double* vel_dev,

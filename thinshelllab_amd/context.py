@@ -253,7 +253,7 @@ class TslContext:
         check(self.L.tsl_tie_grad(self.h, _ptr(pos), _ptr(p), out.ctypes.data), "tsl_tie_grad")
         return out
 
-    # ---- what the three collider kinds share: kind is "collider", "sphere" or "capsule"
+    # ---- what the four collider kinds share: kind is "collider", "sphere", "capsule" or "box"
     def _shape_count(self, kind):
         out = C.c_int32(0)
         check(getattr(self.L, f"tsl_{kind}_count")(self.h, C.byref(out)), f"tsl_{kind}_count")
@@ -377,6 +377,49 @@ class TslContext:
         """(n, 14) contribution of one reverse step to d(loss)/d(a (3), b (3), previous a (3), previous b (3), mu, R) of every capsule at the tape state
         (x_s, x_{s-1}) with the endpoints of step s in place; p None: the solution of the last adjoint_step, else a 3 * tot_NV device vector"""
         return self._shape_grad("capsule", 14, pos, prev_pos, p)
+
+    # ---- rounded-box colliders (tsl_set_boxes; stiffness: set_param("k_box", k))
+    def set_boxes(self, centres, quats, half_extents, radii, mu, vertex_mask=None):
+        """n solid boxes with rounded edges and corners (centre c_j, quaternion (s, x, y, z), half extents h_j >= 0 of the core box, rounding radius r_j > 0,
+        friction mu_j) with the cloth outside; vertex_mask (tot_NV,) uint8, bit j: box j acts on the vertex, None: all on all; an empty list removes
+        them.  The quaternions are normalised by the library; the previous poses are set to the poses; half extents and radii stay fixed."""
+        r = _np(radii, np.float64).reshape(-1)
+        n = len(r)
+        ce = _np(centres, np.float64).reshape(-1, 3)
+        qu = _np(quats, np.float64).reshape(-1, 4)
+        he = _np(half_extents, np.float64).reshape(-1, 3)
+        m = _np(mu, np.float64).reshape(-1)
+        assert ce.shape == (n, 3) and qu.shape == (n, 4) and he.shape == (n, 3) and m.shape == (n,), (ce.shape, qu.shape, he.shape, r.shape, m.shape)
+        vm = None if vertex_mask is None else _np(vertex_mask, np.uint8).reshape(-1)
+        assert vm is None or vm.shape == (self.tot_NV,), vm.shape
+        check(self.L.tsl_set_boxes(self.h, ce.ctypes.data if n else None, qu.ctypes.data if n else None, he.ctypes.data if n else None,
+                                   r.ctypes.data if n else None, m.ctypes.data if n else None, n, None if vm is None else vm.ctypes.data), "tsl_set_boxes")
+
+    def set_box_poses(self, centres, quats, prev_centres=None, prev_quats=None):
+        """the poses of the next energy / assembly / step / reverse step and where the boxes were at the start of that step (both None: the poses)"""
+        n = self.box_count()
+        ce = _np(centres, np.float64).reshape(-1, 3)
+        qu = _np(quats, np.float64).reshape(-1, 4)
+        pc = None if prev_centres is None else _np(prev_centres, np.float64).reshape(-1, 3)
+        pq = None if prev_quats is None else _np(prev_quats, np.float64).reshape(-1, 4)
+        assert ce.shape == (n, 3) and qu.shape == (n, 4) and (pc is None or pc.shape == (n, 3)) and (pq is None or pq.shape == (n, 4)), (ce.shape, qu.shape, n)
+        if n:
+            check(self.L.tsl_set_box_poses(self.h, ce.ctypes.data, qu.ctypes.data, None if pc is None else pc.ctypes.data, None if pq is None else pq.ctypes.data),
+                  "tsl_set_box_poses")
+
+    def box_count(self):
+        return self._shape_count("box")
+
+    def box_force(self, pos, prev_pos):
+        """(n, 6): [0:3] -sum_v g_v, the net force every box applies to the cloth at the state (pos, prev_pos), [3:6] -sum_v (x_v - c) x g_v, its torque
+        about the box's centre (frozen dofs not masked)"""
+        return self._shape_force("box", 6, pos, prev_pos)
+
+    def box_grad(self, pos, prev_pos, p=None):
+        """(n, 14) contribution of one reverse step to d(loss)/d(c (3), theta (3), previous c (3), previous theta (3), mu, r) of every box at the tape state
+        (x_s, x_{s-1}) with the poses of step s in place (theta: world-frame rotation vectors applied on the left); p None: the solution of the last
+        adjoint_step, else a 3 * tot_NV device vector"""
+        return self._shape_grad("box", 14, pos, prev_pos, p)
 
     # ---- engine calls
     def energy(self, pos, prev_pos, vel, ref_angle):

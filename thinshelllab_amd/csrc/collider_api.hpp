@@ -1,10 +1,11 @@
-// Host side of the three collider kinds inside libtsl_hip.so -- planes (k_collider.hpp), balls (k_sphere.hpp; 2.9), rods (k_capsule.hpp;
-// 2.10): the entry points tsl_set_colliders .. tsl_capsule_grad of include/tsl_hip.h and, for the launch sites of tsl_hip.hip and adjoint_api.hpp,
+// Host side of the four collider kinds inside libtsl_hip.so -- planes (k_collider.hpp), balls (k_sphere.hpp; 2.9), rods (k_capsule.hpp;
+// 2.10), rounded boxes (k_box.hpp; 2.12): the entry points tsl_set_colliders .. tsl_box_grad of include/tsl_hip.h and, for the launch sites of tsl_hip.hip and adjoint_api.hpp,
 // the launches of an assembly, an energy and a reverse step.  One set of helpers, templates on the kind's Shape (k_shape.hpp);
-// an entry point checks what is particular to its kind (collider_host.hpp, sphere_host.hpp, capsule_host.hpp) and hands on.  Included by
+// an entry point checks what is particular to its kind (collider_host.hpp, sphere_host.hpp, capsule_host.hpp, box_host.hpp) and hands on.  Included by
 // tsl_hip.hip behind its helpers (tsl_fail, TSL_TRY, HIP_OK, Scope, nblk), the way handle_api.hpp is.
 #pragma once
 #include <type_traits>
+#include "k_box.hpp"
 #include "k_capsule.hpp"
 #include "k_collider.hpp"
 #include "k_sphere.hpp"
@@ -14,7 +15,8 @@ template <class Shape>
 static auto& shape_set(tsl_ctx* c) {
   if constexpr (std::is_same_v<Shape, PlaneShape>) return c->col;
   else if constexpr (std::is_same_v<Shape, SphereShape>) return c->sph;
-  else return c->cap;
+  else if constexpr (std::is_same_v<Shape, CapsuleShape>) return c->cap;
+  else return c->box;
 }
 // the kernels of a kind in an energy / assembly / reverse step run only while this holds: without it the launches are the ones they were
 template <class Shape>
@@ -30,7 +32,7 @@ template <class Shape>
 static ShapeArgs shape_args(tsl_ctx* c) { return ShapeArgs{c->NV, shape_set<Shape>(c).mask.p}; }
 static int shape_nblk(const tsl_ctx* c) { return nblk(c->NV, 256); }
 // how many kinds hold shapes, on or not (they size the energy partials)
-static int shapes_present(tsl_ctx* c) { return (c->col.tab.n > 0) + (c->sph.tab.n > 0) + (c->cap.tab.n > 0); }
+static int shapes_present(tsl_ctx* c) { return (c->col.tab.n > 0) + (c->sph.tab.n > 0) + (c->cap.tab.n > 0) + (c->box.tab.n > 0); }
 
 template <class Shape>
 static void shape_assemble_launch(tsl_ctx* c, hipStream_t s, int spd, const double* pos, const double* prev, double* grad) {
@@ -50,12 +52,13 @@ static void shape_backprop_launch(tsl_ctx* c, hipStream_t s, const double* x_s, 
   hipLaunchKernelGGL(k_shape_backprop<Shape>, dim3(shape_nblk(c)), dim3(256), 0, s, shape_table<Shape>(c), shape_args<Shape>(c), (const int*)c->frozen.p, x_s, x_prev, p, pg_prev);
 }
 
-// The colliders in an assembly: gradient rows and diagonal blocks behind the vertex terms on the same stream -- planes, then balls, then rods; a
+// The colliders in an assembly: gradient rows and diagonal blocks behind the vertex terms on the same stream -- planes, then balls, then rods, then boxes; a
 // kind that is not on launches nothing.  spd 0: the exact block of the reverse step's operator; every other mode: the projected one
 static void shapes_assemble_launch(tsl_ctx* c, hipStream_t s, int spd, const double* pos, const double* prev, double* grad) {
   shape_assemble_launch<PlaneShape>(c, s, spd, pos, prev, grad);
   shape_assemble_launch<SphereShape>(c, s, spd, pos, prev, grad);
   shape_assemble_launch<CapsuleShape>(c, s, spd, pos, prev, grad);
+  shape_assemble_launch<BoxShape>(c, s, spd, pos, prev, grad);
 }
 // Their energy partials from e_part on, one per workgroup of 256 vertices and kind that is on, in the same order; returns how many
 static int shapes_energy_launch(tsl_ctx* c, hipStream_t s, const double* pos, const double* prev, double* e_part) {
@@ -63,14 +66,16 @@ static int shapes_energy_launch(tsl_ctx* c, hipStream_t s, const double* pos, co
   shape_energy_launch<PlaneShape>(c, s, pos, prev, e_part, nb);
   shape_energy_launch<SphereShape>(c, s, pos, prev, e_part, nb);
   shape_energy_launch<CapsuleShape>(c, s, pos, prev, e_part, nb);
+  shape_energy_launch<BoxShape>(c, s, pos, prev, e_part, nb);
   return nb;
 }
 // Their share of a reverse step that goes into pos_grad[s-1] (x_s, x_{s-1}, the adjoint solution p), in the same order: the planes' lagged
-// friction; the balls' lagged friction and lagged contact frame; the rods' lagged friction, lagged contact frame and lagged rod parameter
+// friction; the balls' lagged friction and lagged contact frame; the rods' lagged friction, lagged contact frame and lagged rod parameter; the boxes' lagged friction, lagged contact frame and lagged material point
 static void shapes_backprop_launch(tsl_ctx* c, hipStream_t s, const double* x_s, const double* x_prev, const double* p, double* pg_prev) {
   shape_backprop_launch<PlaneShape>(c, s, x_s, x_prev, p, pg_prev);
   shape_backprop_launch<SphereShape>(c, s, x_s, x_prev, p, pg_prev);
   shape_backprop_launch<CapsuleShape>(c, s, x_s, x_prev, p, pg_prev);
+  shape_backprop_launch<BoxShape>(c, s, x_s, x_prev, p, pg_prev);
 }
 
 // The tail of tsl_set_*: T is the checked list of n shapes (the kind's host header); the mask is checked here and becomes a device buffer of NV
@@ -208,4 +213,32 @@ extern "C" int tsl_capsule_force(tsl_ctx* c, const double* pos, const double* pr
 }
 extern "C" int tsl_capsule_grad(tsl_ctx* c, const double* pos, const double* prev, const double* p_dev, double* out_host) {
   return shape_grad<CapsuleShape>(c, "tsl_capsule_grad", pos, prev, p_dev, out_host);
+}
+
+// ---- rounded boxes.  The previous poses of a new list are its poses.  Force: n x 6, the net force -sum_v g_v of every box and its torque
+// -sum_v (x_v - c) x g_v about the box's centre.  Grad: n x 14, d(loss)/d(c_j, theta_j, cp_j, theta_p_j, mu_j, r_j), the poses and previous poses of
+// step s in place
+extern "C" int tsl_set_boxes(tsl_ctx* c, const double* centres, const double* quats, const double* half_extents, const double* radii, const double* mu, int32_t n,
+                             const uint8_t* vertex_mask) {
+  Scope scope(c);
+  (void)hipStreamSynchronize(c->stream);
+  std::string err;
+  BoxTable S = c->box.tab;
+  if (box_validate(centres, quats, half_extents, radii, mu, n, S, err)) return tsl_fail("tsl_set_boxes: %s", err.c_str());
+  return shape_commit<BoxShape>(c, "tsl_set_boxes", "box", S, n, vertex_mask);
+}
+extern "C" int tsl_set_box_poses(tsl_ctx* c, const double* centres, const double* quats, const double* prev_centres, const double* prev_quats) {
+  Scope scope(c);
+  (void)hipStreamSynchronize(c->stream);
+  if (c->box.tab.n == 0) return 0;
+  std::string err;
+  if (box_poses_validate(centres, quats, prev_centres, prev_quats, c->box.tab, err)) return tsl_fail("tsl_set_box_poses: %s", err.c_str());
+  return 0;
+}
+extern "C" int tsl_box_count(tsl_ctx* c, int32_t* out) { return shape_count<BoxShape>(c, "tsl_box_count", out); }
+extern "C" int tsl_box_force(tsl_ctx* c, const double* pos, const double* prev, double* out_host) {
+  return shape_force<BoxShape>(c, "tsl_box_force", pos, prev, out_host);
+}
+extern "C" int tsl_box_grad(tsl_ctx* c, const double* pos, const double* prev, const double* p_dev, double* out_host) {
+  return shape_grad<BoxShape>(c, "tsl_box_grad", pos, prev, p_dev, out_host);
 }

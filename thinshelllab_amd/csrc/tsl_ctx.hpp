@@ -15,6 +15,7 @@
 #include "../../include/tsl_hip.h"
 #include "collider_host.hpp"
 #include "sphere_host.hpp"
+#include "box_host.hpp"
 #include "capsule_host.hpp"
 #include "k_body.hpp"
 #include "direct_plan.hpp"
@@ -412,11 +413,12 @@ struct tsl_ctx {
   DevBuf<int> ti_idx;                  // n x 4 (t0, t1, t2, v)
   DevBuf<double> ti_b, ti_w, ti_out;   // n x 3, n, n x 3 (read-outs of tsl_tie_force / tsl_tie_residuals / tsl_tie_grad)
   // ---- colliders (collider_api.hpp; k_shape.hpp): one set per kind -- planes (tsl_set_colliders, k_collider.hpp), balls (tsl_set_spheres,
-  // k_sphere.hpp: centres and previous centres), rods (tsl_set_capsules, k_capsule.hpp: endpoints and previous endpoints).  A kind's kernels run
-  // while tab.n > 0 and k != 0
+  // k_sphere.hpp: centres and previous centres), rods (tsl_set_capsules, k_capsule.hpp: endpoints and previous endpoints), rounded boxes
+  // (tsl_set_boxes, k_box.hpp: poses and previous poses).  A kind's kernels run while tab.n > 0 and k != 0
   ShapeSet<ColliderPlanes> col;
   ShapeSet<SphereTable> sph;
   ShapeSet<CapsuleTable> cap;
+  ShapeSet<BoxTable> box;
 
   // ---- multigrid preconditioner
   std::vector<MgCloth*> mg;

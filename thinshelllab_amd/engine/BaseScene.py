@@ -9,6 +9,7 @@ hands the hot path to ``libtsl_hip.so`` through ``TslContext``:
   H.solve              -> tsl_solve           (sparse_solver.py:85-105)
 State lives once, in global HBM tensors; per-body fields are views (no pushup/pushdown copies).
 """
+import math
 from dataclasses import dataclass
 
 import numpy as np
@@ -16,7 +17,7 @@ import torch
 
 from . import gripper_single
 from .field import Field, ScalarField
-from .frames import compose, frame_targets, validate_frames, validate_poses
+from .frames import compose, frame_targets, quat_normalize, validate_frames, validate_poses
 from .gripper_single import quat_to_rotmat
 from .gripper_tactile import gripper
 from .model_elastic_offset import Elastic
@@ -128,7 +129,7 @@ def validate_ties(tot_NV, faces_tab, vertex_ids, face_ids, bary, weights=None):
 
 
 SHAPE_MAX = 8   # colliders of one kind: one bit each in a vertex's mask byte (csrc/shape_host.hpp)
-TSL_MAX_COLLIDERS = TSL_MAX_SPHERES = TSL_MAX_CAPSULES = SHAPE_MAX
+TSL_MAX_COLLIDERS = TSL_MAX_SPHERES = TSL_MAX_CAPSULES = TSL_MAX_BOXES = SHAPE_MAX
 
 
 def _check_shape(who, noun, j, mu, radius=None):
@@ -250,6 +251,45 @@ def validate_capsules(tot_NV, ends_a, ends_b, radii, mu, vertex_ids=None):
     return a.copy(), b.copy(), r.copy(), m.copy(), _shape_mask("set_capsules", "capsule", tot_NV, n, vertex_ids)
 
 
+def _box_pose_check(who, what, c, q, j):
+    """the message of csrc/box_host.hpp for the pose of box j (what: "" or "previous "), or None"""
+    if not np.isfinite(c).all():
+        return f"{who}: {what}centre ({c[0]:g}, {c[1]:g}, {c[2]:g}) of box {j} is not finite"
+    n = math.sqrt(((q[0] * q[0] + q[1] * q[1]) + q[2] * q[2]) + q[3] * q[3]) if np.isfinite(q).all() else float("nan")
+    if not (n > 0.0 and math.isfinite(n)):
+        return f"{who}: {what}quaternion ({q[0]:g}, {q[1]:g}, {q[2]:g}, {q[3]:g}) of box {j} is zero or not finite"
+    return None
+
+
+def validate_boxes(tot_NV, centres, quats, half_extents, radii, mu, vertex_ids=None):
+    """The checks of tsl_set_boxes on the host, with the messages of csrc/box_host.hpp: returns (centres (n, 3), unit quaternions (n, 4), half extents
+    (n, 3), radii (n), mu (n), uint8 mask (tot_NV)) or raises ValueError naming the offender -- more than SHAPE_MAX boxes, a non-finite centre, a
+    zero or non-finite quaternion, a negative or non-finite half extent, a radius that is not finite and positive, a negative or non-finite friction
+    coefficient, a vertex id out of range.  vertex_ids None: every box acts on every vertex; else one entry per box, None (all vertices) or a list
+    of global vertex ids."""
+    r = np.asarray(radii, dtype=np.float64).reshape(-1)
+    n = len(r)
+    c = np.asarray(centres, dtype=np.float64).reshape(-1, 3) if n else np.zeros((0, 3))
+    q = np.array(quats, dtype=np.float64).reshape(-1, 4) if n else np.zeros((0, 4))
+    h = np.asarray(half_extents, dtype=np.float64).reshape(-1, 3) if n else np.zeros((0, 3))
+    m = np.asarray(mu, dtype=np.float64).reshape(-1)
+    if c.shape != (n, 3) or q.shape != (n, 4) or h.shape != (n, 3) or m.shape != (n,):
+        raise ValueError(f"set_boxes: {len(c)} centres, {len(q)} quaternions, {len(h)} half extents and {m.size} friction coefficients for {n} radii")
+    if n > SHAPE_MAX:
+        raise ValueError(f"set_boxes: {n} boxes: at most {SHAPE_MAX}")
+    for j in range(n):
+        bad = _box_pose_check("set_boxes", "", c[j], q[j], j)
+        if bad:
+            raise ValueError(bad)
+        if not (np.isfinite(h[j]).all() and (h[j] >= 0.0).all()):
+            raise ValueError(f"set_boxes: half extents ({h[j, 0]:g}, {h[j, 1]:g}, {h[j, 2]:g}) of box {j} are negative or not finite")
+        _check_shape("set_boxes", "box", j, m[j], r[j])
+        q[j] = quat_normalize(q[j])
+    if vertex_ids is not None and len(vertex_ids) != n:
+        raise ValueError(f"set_boxes: {len(vertex_ids)} vertex lists for {n} boxes")
+    return c.copy(), q, h.copy(), r.copy(), m.copy(), _shape_mask("set_boxes", "box", tot_NV, n, vertex_ids)
+
+
 class _SystemMatrix:
     """Stand-in for ``SparseMatrix`` (sparse_solver.py): the matrix itself lives inside the context."""
 
@@ -341,6 +381,17 @@ class BaseScene:
         self._cap_mu = np.zeros(0)
         self._cap_mask = np.zeros(0, np.uint8)
         self.k_capsule = 0.0
+        # rounded-box colliders (set_boxes): _box_c, _box_q the poses (centres (n, 3), unit quaternions (n, 4)) for the next step, _box_cp, _box_qp those of
+        # the last completed step (where the boxes are at the start of the next one), _box_cp_step, _box_qp_step the previous poses that the last
+        # completed step used (the tape records them); half extents, radii, friction coefficients, the per-vertex mask and the stiffness k_box, kept
+        # here and pushed to the engine context lazily
+        self._box_c = self._box_cp = self._box_cp_step = np.zeros((0, 3))
+        self._box_q = self._box_qp = self._box_qp_step = np.zeros((0, 4))
+        self._box_h = np.zeros((0, 3))
+        self._box_r = np.zeros(0)
+        self._box_mu = np.zeros(0)
+        self._box_mask = np.zeros(0, np.uint8)
+        self.k_box = 0.0
         # rigid frames of the handles (set_handle_frames): frame and local point of every handle, position and unit quaternion of every frame
         self._frame_of = np.zeros(0, np.int32)
         self._frame_local = np.zeros((0, 3))
@@ -624,6 +675,8 @@ class BaseScene:
                 self._push_spheres()
             if self.n_capsule:
                 self._push_capsules()
+            if self.n_box:
+                self._push_boxes()
             self._dirty.clear()
         if self._dirty:
             if "ties" in self._dirty:
@@ -640,6 +693,10 @@ class BaseScene:
                 self._push_capsules()
             elif "capsule_ends" in self._dirty:
                 self._ctx.set_capsule_ends(self._cap_e[:, 0], self._cap_e[:, 1], self._cap_ep[:, 0], self._cap_ep[:, 1])
+            if "boxes" in self._dirty:
+                self._push_boxes()
+            elif "box_poses" in self._dirty:
+                self._ctx.set_box_poses(self._box_c, self._box_q, self._box_cp, self._box_qp)
             if "handles" in self._dirty:
                 self._push_handles()
             else:
@@ -940,6 +997,78 @@ class BaseScene:
             self._cap_ep = self._cap_e.copy()
             self._dirty.add("capsule_ends")
 
+    # ------------------------------------------------------------------ rounded-box colliders (no counterpart in the reference)
+    @property
+    def n_box(self):
+        return len(self._box_r)
+
+    def set_boxes(self, centres, quats, half_extents, radii, mu, k, vertex_ids=None):
+        """Up to 8 solid boxes with rounded edges and corners (centre, quaternion (s, x, y, z), half extents >= 0 of the core box, rounding radius > 0,
+        friction coefficient mu_j >= 0) with the cloth outside and one stiffness k >= 0 in N/m: a table top whose edge the cloth hangs over, a shelf,
+        a step, a gripper jaw, a plate that tilts (set_box_poses or move_boxes before every step).  The solid is the core box grown by the radius;
+        there is no sharp box.  The shell is eps_contact thick, the friction is regularised with eps_v dt and acts on the slip relative to the
+        box's material point under the vertex.  A vertex inside the core box, deeper than the radius, feels nothing: the limit of the model.
+        vertex_ids None: every box acts on every vertex; else one entry per box, None or a list of global vertex ids.  The boxes start at rest
+        (previous poses = poses); half extents and radii stay fixed; an empty list removes the boxes.  The lists are checked here, before any
+        library call."""
+        c, q, h, r, m, mask = validate_boxes(self.tot_NV, centres, quats, half_extents, radii, mu, vertex_ids)
+        k = _check_k("set_boxes", "k_box", k)
+        self._box_c, self._box_cp, self._box_cp_step = c, c.copy(), c.copy()
+        self._box_q, self._box_qp, self._box_qp_step = q, q.copy(), q.copy()
+        self._box_h, self._box_r, self._box_mu, self._box_mask, self.k_box = h, r, m, mask, k
+        self._dirty.add("boxes")
+
+    def _check_box_poses(self, what, centres, quats):
+        c = np.asarray(centres, dtype=np.float64).reshape(-1, 3)
+        q = np.array(quats, dtype=np.float64).reshape(-1, 4)
+        if c.shape != (self.n_box, 3) or q.shape != (self.n_box, 4):
+            raise ValueError(f"set_box_poses: {len(c)} {what}centres and {len(q)} {what}quaternions for {self.n_box} boxes")
+        for j in range(len(c)):
+            bad = _box_pose_check("set_box_poses", what, c[j], q[j], j)
+            if bad:
+                raise ValueError(bad)
+            q[j] = quat_normalize(q[j])
+        return c.copy(), q
+
+    def set_box_poses(self, centres, quats, prev_centres=None, prev_quats=None):
+        """the poses of the next step (or energy, assembly, reverse step).  Where the boxes were at the start of that step is kept by the scene: the
+        poses of the last completed step.  prev_centres and prev_quats together override it (a tape puts a recorded step back; a caller restarts a
+        rollout); one without the other is refused."""
+        if (prev_centres is None) != (prev_quats is None):
+            raise ValueError("set_box_poses: previous " + ("centres without previous quaternions" if prev_quats is None else "quaternions without previous centres"))
+        c, q = self._check_box_poses("", centres, quats)
+        if prev_centres is not None:
+            self._box_cp, self._box_qp = self._check_box_poses("previous ", prev_centres, prev_quats)
+        self._box_c, self._box_q = c, q
+        self._dirty.add("box_poses")
+
+    def move_boxes(self, delta_pos, delta_theta):
+        """the poses of the next step from those in place: c += delta_pos, R <- exp([delta_theta]x) R per box (frames.compose: world-frame rotation
+        vectors applied on the left, the convention of box_pose_grad)"""
+        dp = np.asarray(delta_pos, dtype=np.float64).reshape(-1, 3)
+        dth = np.asarray(delta_theta, dtype=np.float64).reshape(-1, 3)
+        if dp.shape != (self.n_box, 3) or dth.shape != (self.n_box, 3):
+            raise ValueError(f"move_boxes: {len(dp)} translations and {len(dth)} rotation vectors for {self.n_box} boxes")
+        if self.n_box:
+            self.set_box_poses(*compose(self._box_c, self._box_q, dp, dth))
+
+    def box_force(self):
+        """(n, 6): the net force every box applies to the cloth at the current positions and start-of-step positions, and its torque about the box's
+        centre (a level plate under a resting cloth reads the weight it carries and where it carries it)"""
+        return self._ensure_ctx().box_force(self.pos.t, self.prev_pos.t)
+
+    def _push_boxes(self):
+        self._ctx.set_boxes(self._box_c, self._box_q, self._box_h, self._box_r, self._box_mu, self._box_mask if self.n_box else None)
+        self._ctx.set_box_poses(self._box_c, self._box_q, self._box_cp, self._box_qp)
+        self._ctx.set_param("k_box", self.k_box)
+
+    def _boxes_step_done(self):
+        """a step is complete: its poses are where the boxes are at the start of the next one"""
+        if self.n_box:
+            self._box_cp_step, self._box_qp_step = self._box_cp, self._box_qp
+            self._box_cp, self._box_qp = self._box_c.copy(), self._box_q.copy()
+            self._dirty.add("box_poses")
+
     # ------------------------------------------------------------------ rigid frames for the handles (no counterpart in the reference)
     @property
     def n_frame(self):
@@ -1069,6 +1198,7 @@ class BaseScene:
         st = ctx.step(*self._state())
         self._spheres_step_done()
         self._capsules_step_done()
+        self._boxes_step_done()
         self.last_stats = st
         self.nc[None] = st["nc"]
         self.E[None] = st["energy"]

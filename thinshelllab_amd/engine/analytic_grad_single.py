@@ -47,6 +47,28 @@ def handle_tape_init(grad, sys, T):
         grad.capsule_ends = Field(torch.zeros((T, grad.n_capsule, 2, 3), dtype=torch.float64))
         grad.capsule_ends_prev = Field(torch.zeros((T, grad.n_capsule, 2, 3), dtype=torch.float64))
         grad.capsule_grad = Field(torch.zeros((T, grad.n_capsule, 14), dtype=torch.float64))
+    # rounded-box colliders (BaseScene.set_boxes): the poses (centre (3), unit quaternion (4)) and previous poses of every step and
+    # d(loss)/d(c, theta, cp, theta_p, mu, r) per reverse step
+    grad.n_box = getattr(sys, "n_box", 0)
+    if grad.n_box:
+        grad.box_poses = Field(torch.zeros((T, grad.n_box, 7), dtype=torch.float64))
+        grad.box_poses_prev = Field(torch.zeros((T, grad.n_box, 7), dtype=torch.float64))
+        grad.box_grad = Field(torch.zeros((T, grad.n_box, 14), dtype=torch.float64))
+
+
+def box_pose_grad(grad):
+    """(T, n, 6) d(loss)/d(pose trajectory) -- [0:3] the centre, [3:6] a world-frame rotation vector applied on the left of the step's orientation --
+    when each step's previous pose was the pose of the step before: row s is box_grad[s, :, 0:6] + box_grad[s + 1, :, 6:12].  Raises if the tape
+    shows another trajectory."""
+    if not grad.n_box:
+        raise ValueError("box_pose_grad: the scene has no boxes")
+    e, ep, g = grad.box_poses.t, grad.box_poses_prev.t, grad.box_grad.t
+    if not torch.equal(ep[1:], e[:-1]):
+        s = int((ep[1:] != e[:-1]).reshape(len(e) - 1, -1).any(dim=1).nonzero()[0, 0]) + 1
+        raise ValueError(f"box_pose_grad: the previous poses of step {s} are not the poses of step {s - 1}")
+    out = g[:, :, 0:6].clone()
+    out[:-1] += g[1:, :, 6:12]
+    return out
 
 
 def capsule_end_grad(grad):
@@ -91,6 +113,10 @@ def handle_tape_reset(grad):
         grad.capsule_ends.fill(0)
         grad.capsule_ends_prev.fill(0)
         grad.capsule_grad.fill(0)
+    if grad.n_box:
+        grad.box_poses.fill(0)
+        grad.box_poses_prev.fill(0)
+        grad.box_grad.fill(0)
     if grad.n_handle:
         grad.handle_targets.fill(0)
         grad.handle_grad.fill(0)
@@ -115,6 +141,9 @@ def handle_tape_record(grad, sys, step):
     if grad.n_capsule:   # likewise: the endpoints of the step just completed, and where the rods were when it started
         grad.capsule_ends.t[step] = torch.as_tensor(sys._cap_ep)
         grad.capsule_ends_prev.t[step] = torch.as_tensor(sys._cap_ep_step)
+    if grad.n_box:   # likewise: the poses of the step just completed, and where the boxes were when it started
+        grad.box_poses.t[step] = torch.as_tensor(np.concatenate([sys._box_cp, sys._box_qp], axis=1))
+        grad.box_poses_prev.t[step] = torch.as_tensor(np.concatenate([sys._box_cp_step, sys._box_qp_step], axis=1))
 
 
 def handle_tape_push(grad, sys, step):
@@ -131,6 +160,9 @@ def handle_tape_push(grad, sys, step):
     if grad.n_capsule:   # the endpoints and previous endpoints of step `step`: the reverse step evaluates t0, the contact frame and the slip with them
         e, ep = grad.capsule_ends.t[step].numpy(), grad.capsule_ends_prev.t[step].numpy()
         sys.set_capsule_ends(e[:, 0], e[:, 1], ep[:, 0], ep[:, 1])
+    if grad.n_box:   # the poses and previous poses of step `step`: the reverse step evaluates b0, the contact frame and the slip with them
+        e, ep = grad.box_poses.t[step].numpy(), grad.box_poses_prev.t[step].numpy()
+        sys.set_box_poses(e[:, 0:3], e[:, 3:7], ep[:, 0:3], ep[:, 3:7])
 
 
 def handle_tape_pull(grad, ctx, step):
@@ -147,6 +179,8 @@ def handle_tape_pull(grad, ctx, step):
         grad.sphere_grad.t[step] += torch.as_tensor(ctx.sphere_grad(grad.pos_buffer.t[step], grad.pos_buffer.t[step - 1]))
     if grad.n_capsule:   # capsule_grad[step] += d(loss)/d(a, b, ap, bp of step `step`, mu, R) of the reverse step just taken, at the tape state (x_step, x_{step-1})
         grad.capsule_grad.t[step] += torch.as_tensor(ctx.capsule_grad(grad.pos_buffer.t[step], grad.pos_buffer.t[step - 1]))
+    if grad.n_box:   # box_grad[step] += d(loss)/d(c, theta, cp, theta_p of step `step`, mu, r) of the reverse step just taken, at the tape state (x_step, x_{step-1})
+        grad.box_grad.t[step] += torch.as_tensor(ctx.box_grad(grad.pos_buffer.t[step], grad.pos_buffer.t[step - 1]))
 
 
 class Grad:
@@ -197,6 +231,11 @@ class Grad:
     def capsule_end_grad(self):
         """(T, n, 2, 3) d(loss)/d(endpoint trajectory of the capsules); raises if a step's previous endpoints were not the endpoints of the step before"""
         return capsule_end_grad(self)
+
+    def box_pose_grad(self):
+        """(T, n, 6) d(loss)/d(pose trajectory of the boxes: centre, world-frame rotation vector); raises if a step's previous poses were not the poses of
+        the step before"""
+        return box_pose_grad(self)
 
     # :37-51
     def copy_pos(self, sys, step):

@@ -65,6 +65,7 @@ class SceneGroup:
             d = r.as_dict()
             s._spheres_step_done()
             s._capsules_step_done()
+            s._boxes_step_done()
             s.last_stats = d
             s.nc[None] = d["nc"]
             s.E[None] = d["energy"]
