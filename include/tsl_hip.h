@@ -103,7 +103,7 @@ int tsl_ctx_create(const tsl_scene_desc* desc, tsl_ctx** out);
 void tsl_ctx_destroy(tsl_ctx* ctx);
 int tsl_set_stream(tsl_ctx* ctx, void* hip_stream);
 
-/* 0-d field writes of the reference and the engine's own switches (46 keys + three patterns; an unknown key is an error).
+/* 0-d field writes of the reference and the engine's own switches (48 keys + three patterns; an unknown key is an error).
  *  Scene (trajopt_folding.py:50,66; Scene_folding.py:30-31; geometry.py:8-19; geometry_self.py:166-230):
  *   "cloth<i>.Kb|Kl|Ka|k_angle", "elastic<i>.mu|lam|alpha", "mu_cloth_elastic", "mu_cloth_cloth", "k_contact", "eps_contact", "eps_v", "damping",
  *   "k_handle" (0 default: stiffness in N/m of the soft handles of tsl_set_handles; negative fails; with 0, or with no handles, no handle kernel is launched),
@@ -120,7 +120,8 @@ int tsl_set_stream(tsl_ctx* ctx, void* hip_stream);
  *   F = [x1 - x0, x2 - x0] Dm^-1, Dm the rest triangle rebuilt from the face's rest lengths (fails naming a face whose lengths violate the triangle
  *   inequality), Psi = mu |E|^2 + lam/2 tr(E)^2, E = (F^T F - I) / 2, A0 the rest area; it replaces the springs and the area term of the cloth's
  *   faces, bending / inertia / contact unchanged; spd 1 clamps the 6 x 6 d2Psi/dF2 by eigen-clamp, "spd_literal" does not apply to it; any value but
- *   0 / 1 fails), "cloth<i>.stvk_mu", "cloth<i>.stvk_lam" (its Lame parameters in N/m, default 0; Kl / Ka of a StVK cloth are kept unused, as are
+ *   0 / 1 fails), "wind_cn", "wind_ct" (0 default: the normal and the tangential drag coefficient in N s / m^3 of the wind of tsl_set_wind; negative or
+ *   non-finite fails; with both 0, or with no wind list, no wind kernel is launched), "cloth<i>.stvk_mu", "cloth<i>.stvk_lam" (its Lame parameters in N/m, default 0; Kl / Ka of a StVK cloth are kept unused, as are
  *   stvk_* of a spring cloth; switching at any time keeps the block pattern and the plans of the factorisation),
  *   "newton_cap", "plastic", "contact" (0: no detection in tsl_step), "grid_h", "grid_extent" (broad-phase cell and box), "self_contact<body>"
  *   (0 / 1: the body's vertices are also projected onto its own triangles), "contact_ee" (0 default: vertex-triangle contact only, as the reference;
@@ -436,6 +437,46 @@ int tsl_set_box_poses(tsl_ctx* ctx, const double* centres_host, const double* qu
 int tsl_box_count(tsl_ctx* ctx, int32_t* out_host);
 int tsl_box_force(tsl_ctx* ctx, const double* pos_dev, const double* prev_pos_dev, double* out_host);
 int tsl_box_grad(tsl_ctx* ctx, const double* pos_dev, const double* prev_pos_dev, const double* p_dev, double* out_host);
+
+/* Wind (no reference counterpart, which has no load from the medium): lagged linear aerodynamic drag on a list of cloth faces.  Wind face f of the
+ * list has the corners (v_0, v_1, v_2) of its face in the scene's face table (faces_host of tsl_scene_desc; the cloths' faces are its first
+ * sum NF faces) and a weight w_f >= 0; the coefficients "wind_cn" (normal) and "wind_ct" (tangential) of tsl_set_param, both in N s / m^3 and 0 by
+ * default, are shared, and there is one wind velocity W per step and scene.  With x_prev the start-of-step positions (the prev_pos argument of
+ * tsl_energy / tsl_assemble; x_{s-1} in a reverse step):
+ *   a   = 1/2 (xp_1 - xp_0) x (xp_2 - xp_0),  A0 = |a|,  n0 = a / A0          the lagged area vector
+ *   M   = w_f [ c_t A0 I + (c_n - c_t) a a^T / A0 ] = w_f A0 (c_n n0 n0^T + c_t (I - n0 n0^T))
+ *   r   = (xbar - xpbar) / dt - W,  xbar = (x_0 + x_1 + x_2) / 3
+ *   E_w = dt / 2 sum_f r^T M r,  gradient row of each corner: M r / 3,  block of each of the nine corner pairs: M / (9 dt).
+ * The force on the sheet is M (W - u) with u the centroid's velocity over the step.  M depends on x_prev only: the blocks are constant over the
+ * Newton iterations of a step and positive semi-definite as they stand, so every spd mode, with and without "spd_literal", adds the same numbers.
+ * The three pair blocks of a cloth face are in the matrix pattern already: no constraint slot, no row list, and the plans of the factorisation and
+ * tsl_contact_counts do not depend on the wind.  A face with A0 < 1e-12 m^2 at the start of the step contributes nothing.  Frozen dofs follow the
+ * mask rule.  One record per face, then one lane per touched vertex and per touched block over gather lists, no atomics: the same bits run to run.
+ * With no list, or wind_cn = wind_ct = 0, every launch is the one it was.  Not modelled: drag quadratic in speed; a wind that varies in space (the
+ * weights are the only spatial handle); faces of FEM bodies (refused); gradients for the weights; keys of tsl_param_grad_keys (the coefficient
+ * columns of tsl_wind_grad carry those gradients).
+ *   tsl_set_wind: faces_host (n global face ids), weights_host (n; NULL: 1 each); host pointers, copied; the stream is synchronised; n = 0 removes
+ *     the list; faces_host == NULL with n = -1: every cloth face in ascending order (weights_host then has one entry per cloth face).  Fails, naming
+ *     the offender, and leaves the previous list in place for n < 0, a face out of range, a surface face of a body, a face listed twice, a
+ *     negative or non-finite weight.
+ *   tsl_set_wind_velocity: W_host (3) for the next energy, assemble, step or adjoint step; set that of step s before the reverse step s and before
+ *     tsl_wind_grad.  A non-finite component fails, naming it, and leaves the velocity in place.
+ *   tsl_wind_count: n.
+ *   tsl_wind_force: out_host (3) = -sum_f M_f r_f at the state (pos, prev_pos): the net force the wind applies to the cloth; frozen dofs are NOT
+ *     masked; wind off: zeros.
+ *   tsl_wind_grad: out_host (5) at the tape state (pos = x_s, prev_pos = x_{s-1}), sign of tsl_sphere_grad, p the adjoint solution on its free
+ *     dofs (p_dev == NULL: the solution of the last tsl_adjoint_step), P_f its sum over the corners of face f: the share of one reverse step in
+ *       [0:3] d(loss)/d(W)   = +1/3 sum_f M_f P_f,
+ *       [3]   d(loss)/d(c_n) = -1/3 sum_f w_f A0 (n0.r)(n0.P_f),
+ *       [4]   d(loss)/d(c_t) = -1/3 sum_f w_f A0 (r.P_f - (n0.r)(n0.P_f)).
+ *     The reverse step itself adds -(dg/dx_prev)^T p to the free dofs of the corners' rows of pos_grad[s-1]: M P_f / (9 dt) to each corner (through r)
+ *     and, through a, with q = 1/3 w_f [ c_t (P.r) a / A0 + (c_n - c_t) (((a.r) P + (a.P) r) / A0 - (a.P)(a.r) a / A0^3) ], e1 = xp_1 - xp_0 and
+ *     e2 = xp_2 - xp_0:  -1/2 (e2 x q) to corner 1, -1/2 (q x e1) to corner 2, minus their sum to corner 0. */
+int tsl_set_wind(tsl_ctx* ctx, const int32_t* faces_host, const double* weights_host, int32_t n);
+int tsl_set_wind_velocity(tsl_ctx* ctx, const double* W_host);
+int tsl_wind_count(tsl_ctx* ctx, int32_t* out_host);
+int tsl_wind_force(tsl_ctx* ctx, const double* pos_dev, const double* prev_pos_dev, double* out_host);
+int tsl_wind_grad(tsl_ctx* ctx, const double* pos_dev, const double* prev_pos_dev, const double* p_dev, double* out_host);
 
 /* BaseScene.compute_energy (BaseScene.py:427-451) at the given state, constraints as last detected. */
 int tsl_energy(tsl_ctx* ctx, const double* pos_dev, const double* prev_pos_dev, const double* vel_dev,

@@ -421,6 +421,46 @@ class TslContext:
         adjoint_step, else a 3 * tot_NV device vector"""
         return self._shape_grad("box", 14, pos, prev_pos, p)
 
+    # ---- wind (tsl_set_wind; coefficients: set_param("wind_cn", c_n), set_param("wind_ct", c_t))
+    def set_wind(self, faces=None, weights=None):
+        """lagged aerodynamic drag on the cloth faces `faces` (global face ids, each once) with the weights `weights` (None: 1 each); faces None: every
+        cloth face in ascending order; an empty list removes the wind"""
+        w = None if weights is None else _np(weights, np.float64).reshape(-1)
+        if faces is None:
+            assert w is None or w.shape == (self.n_cface,), w.shape
+            check(self.L.tsl_set_wind(self.h, None, None if w is None else w.ctypes.data, -1), "tsl_set_wind")
+            return
+        f = _np(faces, np.int32).reshape(-1)
+        n = len(f)
+        assert w is None or w.shape == (n,), (w.shape, n)
+        check(self.L.tsl_set_wind(self.h, f.ctypes.data if n else None, None if (w is None or not n) else w.ctypes.data, n), "tsl_set_wind")
+
+    def set_wind_velocity(self, W):
+        """the wind velocity (3,) of the next energy / assembly / step / reverse step"""
+        W = _np(W, np.float64).reshape(-1)
+        assert W.shape == (3,), W.shape
+        check(self.L.tsl_set_wind_velocity(self.h, W.ctypes.data), "tsl_set_wind_velocity")
+
+    def wind_count(self):
+        out = C.c_int32(0)
+        check(self.L.tsl_wind_count(self.h, C.byref(out)), "tsl_wind_count")
+        return int(out.value)
+
+    def wind_force(self, pos, prev_pos):
+        """(3,) -sum_f M_f r_f: the net force the wind applies to the cloth at the state (pos, prev_pos) (frozen dofs not masked)"""
+        self.refresh_stream()
+        out = np.zeros(3)
+        check(self.L.tsl_wind_force(self.h, _ptr(pos), _ptr(prev_pos), out.ctypes.data), "tsl_wind_force")
+        return out
+
+    def wind_grad(self, pos, prev_pos, p=None):
+        """(5,) contribution of one reverse step to d(loss)/d(W (3), c_n, c_t) at the tape state (x_s, x_{s-1}) with the wind velocity of step s in
+        place; p None: the solution of the last adjoint_step, else a 3 * tot_NV device vector"""
+        self.refresh_stream()
+        out = np.zeros(5)
+        check(self.L.tsl_wind_grad(self.h, _ptr(pos), _ptr(prev_pos), _ptr(p), out.ctypes.data), "tsl_wind_grad")
+        return out
+
     # ---- engine calls
     def energy(self, pos, prev_pos, vel, ref_angle):
         self.refresh_stream()

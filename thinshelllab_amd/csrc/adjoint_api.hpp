@@ -95,6 +95,8 @@ static int adjoint_post(tsl_ctx* c, const AdjStep& t) {
   if (c->n_hinge) hipLaunchKernelGGL(k_adj_x2a, dim3(nblk(c->n_hinge, 256)), dim3(256), 0, s, CA, t.x_s, c->pdir.p, t.ag_prev);
   // the colliders' lagged terms (planes, balls, rods): -(dg / dx_prev)^T p into the vertices' own rows of pos_grad[s-1] (nothing while none is on)
   shapes_backprop_launch(c, s, t.x_s, t.x_prev, c->pdir.p, t.pg_prev);
+  // the wind's lagged terms: the lagged centroid and the lagged area vector of every listed face, into the rows of its corners (nothing while it is off)
+  wind_backprop_launch(c, s, t.x_s, t.x_prev, c->pdir.p, t.pg_prev);
   // get_prev_grad / get_prev_prev_grad
   hipLaunchKernelGGL(k_adj_prev, dim3(gsz(t.n3)), dim3(256), 0, s, NV, c->pdir.p, c->mass.p, c->frozen.p, c->dt, t.adj_damping, t.pg_prev, t.pg_prev2);
   HIP_OK(hipGetLastError());

@@ -217,6 +217,17 @@ struct ShapeSet {
   DevBuf<double> part, out;
 };
 
+// The wind as the context keeps it (wind_api.hpp; k_wind.hpp): the list of n cloth faces as copies the context owns -- corner vertices, weights, the
+// gather lists of handle_host.hpp (n_vert touched vertices, n_blk touched blocks) --, the two drag coefficients, the wind velocity of the next step,
+// the face records of an assembly (9 n, entry-major), the staging array of a reverse step (n x 3 x 3), and the partials (5 per workgroup of 256
+// faces) and the result (5) of the read-outs.  The wind kernels run while n > 0 and cn + ct != 0
+struct WindSet {
+  int n = 0, n_vert = 0, n_blk = 0;
+  double cn = 0.0, ct = 0.0, W[3] = {0.0, 0.0, 0.0};
+  DevBuf<int> cv, vl_v, vl_ptr, vl_ent, bl_addr, bl_ptr, bl_ent;
+  DevBuf<double> w, rec, stage, part, out;
+};
+
 struct tsl_group;
 struct tsl_ctx {
   tsl_group* group = nullptr;   // set while the context is a member of a scene group (its matrix, right-hand side / solution vectors and fronts are views into the group's memory)
@@ -419,6 +430,8 @@ struct tsl_ctx {
   ShapeSet<SphereTable> sph;
   ShapeSet<CapsuleTable> cap;
   ShapeSet<BoxTable> box;
+  // ---- wind (tsl_set_wind, "wind_cn" / "wind_ct"; wind_api.hpp): lagged drag on a list of cloth faces
+  WindSet wind;
 
   // ---- multigrid preconditioner
   std::vector<MgCloth*> mg;

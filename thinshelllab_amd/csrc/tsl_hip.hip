@@ -55,6 +55,7 @@ static inline int gsz(size_t n) { size_t b = (n + 255) / 256; return (int)std::m
 #include "handle_api.hpp"
 #include "tie_api.hpp"
 #include "collider_api.hpp"
+#include "wind_api.hpp"
 #include "k_scene.hpp"
 
 // ------------------------------------------------------------------------------------------------
@@ -287,6 +288,10 @@ extern "C" int tsl_set_param(tsl_ctx* c, const char* key, double v) {
     if (!(v >= 0.0) || !std::isfinite(v)) return tsl_fail("tsl_set_param: %s must be finite and >= 0 (got %g)", key, v);
     (k == "k_collider" ? c->col.k : k == "k_sphere" ? c->sph.k : k == "k_capsule" ? c->cap.k : c->box.k) = v;
   }
+  else if (k == "wind_cn" || k == "wind_ct") {
+    if (!(v >= 0.0) || !std::isfinite(v)) return tsl_fail("tsl_set_param: %s must be finite and >= 0 (got %g)", key, v);
+    (k == "wind_cn" ? c->wind.cn : c->wind.ct) = v;
+  }
   else if (k == "cg_tol") c->cg_tol = v;
   else if (k == "cg_maxit") c->cg_maxit = (int)v;
   else if (k == "newton_cap") c->newton_cap = (int)v;
@@ -365,7 +370,7 @@ static int energy_async(tsl_ctx* c, const double* pos, const double* prev, const
   const int nb1 = nblk(nmax, 256), nb2 = nvf > 0 ? nblk(nvf, 64) : 0, nb3 = c->nc_ee > 0 ? nblk(c->nc_ee, 64) : 0;
   const int nb4 = handles_on(c) ? nblk(c->n_handle, 256) : 0;   // soft handles: their partials behind the contact ones
   const int nb5 = ties_on(c) ? nblk(c->n_tie, 64) : 0;          // ties: one partial per wave, behind the handle ones
-  const size_t n_part = (size_t)nb1 + (size_t)nblk(c->max_n_constraints, 64) + 1 + (size_t)nblk(c->n_handle, 256) + (size_t)nblk(c->n_tie, 64) + (size_t)shapes_present(c) * shape_nblk(c);
+  const size_t n_part = (size_t)nb1 + (size_t)nblk(c->max_n_constraints, 64) + 1 + (size_t)nblk(c->n_handle, 256) + (size_t)nblk(c->n_tie, 64) + (size_t)shapes_present(c) * shape_nblk(c) + (size_t)wind_nblk(c);
   if (c->e_part.n < n_part) { if (c->e_part.alloc(n_part)) return -1; }
   if (c->n_stvk > 0) hipLaunchKernelGGL(k_energy_stvk, dim3(nb1), dim3(256), 0, s, vert_args(c), cloth_args(c), tet_args(c), pos, prev, vel, ref, c->e_part.p, stvk_args(c));
   else hipLaunchKernelGGL(k_energy, dim3(nb1), dim3(256), 0, s, vert_args(c), cloth_args(c), tet_args(c), pos, prev, vel, ref, c->e_part.p);
@@ -375,7 +380,9 @@ static int energy_async(tsl_ctx* c, const double* pos, const double* prev, const
   if (nb5 > 0) hipLaunchKernelGGL(k_tie_energy, dim3(nblk(c->n_tie, 256)), dim3(256), 0, s, tie_args(c), pos, c->e_part.p + nb1 + nb2 + nb3 + nb4);
   // colliders: one partial per workgroup of 256 vertices and kind (planes, balls, rods), behind the tie ones
   const int nb6 = shapes_energy_launch(c, s, pos, prev, c->e_part.p + nb1 + nb2 + nb3 + nb4 + nb5);
-  hipLaunchKernelGGL(k_energy_final, dim3(1), dim3(256), 0, s, nb1 + nb2 + nb3 + nb4 + nb5 + nb6, (const double*)c->e_part.p, &SC(c)->energy);
+  // wind: one partial per workgroup of 256 listed faces, behind the colliders'
+  const int nb7 = wind_energy_launch(c, s, pos, prev, c->e_part.p + nb1 + nb2 + nb3 + nb4 + nb5 + nb6);
+  hipLaunchKernelGGL(k_energy_final, dim3(1), dim3(256), 0, s, nb1 + nb2 + nb3 + nb4 + nb5 + nb6 + nb7, (const double*)c->e_part.p, &SC(c)->energy);
   return 0;
 }
 static int energy_sync(tsl_ctx* c, const double* pos, const double* prev, const double* vel, const double* ref, double* E) {
@@ -452,6 +459,7 @@ static int assemble_enqueue(tsl_ctx* c, const double* pos, const double* prev, c
   hipLaunchKernelGGL(k_vert_hess, dim3(nblk(NV, 256)), dim3(256), 0, s, VA, c->diag_blk.p, c->vals_full.p);      // (the mass diagonal: the first contribution to its blocks)
   handle_assemble_launch(c, s, pos, grad);
   shapes_assemble_launch(c, s, spd, pos, prev, grad);
+  wind_assemble_launch(c, s, pos, prev, grad);
   if (grad) {
     if (c->n_cface) cloth_grad_face_launch(c, s, CA, pos);
     if (c->n_hinge) hipLaunchKernelGGL(k_cloth_grad_hinge, dim3(nblk(c->n_hinge, 256)), dim3(256), 0, s, CA, pos, ref);
@@ -525,6 +533,7 @@ static int assemble_enqueue_early(tsl_ctx* c, const double* pos, const double* p
   hipLaunchKernelGGL(k_vert_hess, dim3(nblk(NV, 256)), dim3(256), 0, s, VA, c->diag_blk.p, c->vals_full.p);   // (the mass diagonal: the first contribution to its blocks)
   handle_assemble_launch(c, s, pos, grad);   // (on the stream of the vertex terms, in front of ev_fork: the gathers and masks of the other streams wait for it as they do for those)
   shapes_assemble_launch(c, s, spd, pos, prev, grad);
+  wind_assemble_launch(c, s, pos, prev, grad);
   HIP_OK(hipEventRecord(c->ev_fork, s));   // normals, vertex gradient and mass diagonal are in place
   if (c->n_cface) {
     const int nq = (int)c->h_cloth.size() * 9;

@@ -197,6 +197,48 @@ def validate_colliders(tot_NV, normals, offsets, mu, vertex_ids=None):
     return unit, o.copy(), m.copy(), _shape_mask("set_colliders", "collider", tot_NV, n, vertex_ids)
 
 
+def validate_wind(n_cloth_faces, tot_NF, c_n, c_t, face_ids=None, weights=None):
+    """The checks of tsl_set_wind and of the keys "wind_cn" / "wind_ct" on the host, with the messages of csrc/wind_host.hpp: returns (c_n, c_t, int32
+    face ids (n), weights (n)) or raises ValueError naming the offender -- a negative or non-finite coefficient, a face outside [0, tot_NF), a
+    surface face of a body (the cloth faces are the first n_cloth_faces of the scene's face table), a face listed twice, a negative or non-finite
+    weight.  face_ids None: every cloth face in ascending order; weights None: 1 each."""
+    cs = []
+    for name, v in (("wind_cn", c_n), ("wind_ct", c_t)):
+        v = float(v)
+        if not (v >= 0.0 and np.isfinite(v)):
+            raise ValueError(f"set_wind: {name} must be finite and >= 0 (got {v:g})")
+        cs.append(v)
+    f = np.arange(n_cloth_faces, dtype=np.int32) if face_ids is None else np.asarray(face_ids, dtype=np.int64).reshape(-1)
+    n = len(f)
+    w = np.ones(n) if weights is None else np.asarray(weights, dtype=np.float64).reshape(-1)
+    if w.shape != (n,):
+        raise ValueError(f"set_wind: {w.size} weights for {n} faces")
+    first = {}
+    for i in range(n):
+        fi = int(f[i])
+        if fi < 0 or fi >= tot_NF:
+            raise ValueError(f"set_wind: face {fi} of entry {i} out of range [0, {tot_NF})")
+        if fi >= n_cloth_faces:
+            raise ValueError(f"set_wind: face {fi} of entry {i} is a surface face of a body, not a cloth face (cloth faces are [0, {n_cloth_faces}))")
+        if fi in first:
+            raise ValueError(f"set_wind: face {fi} is listed twice (entries {first[fi]} and {i})")
+        first[fi] = i
+        if not (w[i] >= 0.0 and np.isfinite(w[i])):
+            raise ValueError(f"set_wind: weight {w[i]:g} of entry {i} (face {fi}) is negative or not finite")
+    return cs[0], cs[1], f.astype(np.int32), w.copy()
+
+
+def validate_wind_velocity(W):
+    """the wind velocity as a (3,) array, or ValueError naming the component that is not finite (the message of csrc/wind_host.hpp)"""
+    W = np.asarray(W, dtype=np.float64).reshape(-1)
+    if W.shape != (3,):
+        raise ValueError(f"set_wind_velocity: {W.size} components, not 3")
+    for a in range(3):
+        if not np.isfinite(W[a]):
+            raise ValueError(f"set_wind_velocity: component {a} of the wind velocity ({W[0]:g}, {W[1]:g}, {W[2]:g}) is not finite")
+    return W.copy()
+
+
 def validate_spheres(tot_NV, centres, radii, mu, vertex_ids=None):
     """The checks of tsl_set_spheres on the host, with the messages of csrc/sphere_host.hpp: returns (centres (n, 3), radii (n), mu (n), uint8 mask
     (tot_NV)) or raises ValueError naming the offender -- more than SHAPE_MAX spheres, a non-finite centre, a radius that is not finite and
@@ -392,6 +434,13 @@ class BaseScene:
         self._box_mu = np.zeros(0)
         self._box_mask = np.zeros(0, np.uint8)
         self.k_box = 0.0
+        # wind (set_wind): the listed cloth faces and their weights, the two drag coefficients and the wind velocity of the next step, kept here and
+        # pushed to the engine context lazily
+        self._wind_f = np.zeros(0, np.int32)
+        self._wind_w = np.zeros(0)
+        self.wind_cn = 0.0
+        self.wind_ct = 0.0
+        self._wind_W = np.zeros(3)
         # rigid frames of the handles (set_handle_frames): frame and local point of every handle, position and unit quaternion of every frame
         self._frame_of = np.zeros(0, np.int32)
         self._frame_local = np.zeros((0, 3))
@@ -677,6 +726,8 @@ class BaseScene:
                 self._push_capsules()
             if self.n_box:
                 self._push_boxes()
+            if self.n_wind:
+                self._push_wind()
             self._dirty.clear()
         if self._dirty:
             if "ties" in self._dirty:
@@ -697,6 +748,10 @@ class BaseScene:
                 self._push_boxes()
             elif "box_poses" in self._dirty:
                 self._ctx.set_box_poses(self._box_c, self._box_q, self._box_cp, self._box_qp)
+            if "wind" in self._dirty:
+                self._push_wind()
+            elif "wind_velocity" in self._dirty:
+                self._ctx.set_wind_velocity(self._wind_W)
             if "handles" in self._dirty:
                 self._push_handles()
             else:
@@ -1068,6 +1123,37 @@ class BaseScene:
             self._box_cp_step, self._box_qp_step = self._box_cp, self._box_qp
             self._box_cp, self._box_qp = self._box_c.copy(), self._box_q.copy()
             self._dirty.add("box_poses")
+
+    # ------------------------------------------------------------------ wind (no counterpart in the reference)
+    @property
+    def n_wind(self):
+        return len(self._wind_f)
+
+    def set_wind(self, c_n, c_t, face_ids=None, weights=None):
+        """Opt-in wind: lagged linear aerodynamic drag on cloth faces.  A listed face f with the start-of-step area vector a (area A0, normal n0) feels
+        the force w_f A0 (c_n n0 n0^T + c_t (I - n0 n0^T)) (W - u), u its centroid velocity over the step and W the wind velocity
+        (set_wind_velocity, one per step and scene); c_n, c_t >= 0 in N s / m^3 are the normal and the tangential drag coefficient.  face_ids None:
+        every cloth face (Cloth.faces() gives one cloth's); else global ids of cloth faces, each once; weights None: 1 each.  An empty list removes
+        the wind; with c_n = c_t = 0 nothing is launched.  Not modelled: drag quadratic in speed, a wind that varies in space (the weights are the
+        only spatial handle), faces of FEM bodies (refused), gradients for the weights.  The lists are checked here, before any library call."""
+        n_cf = sum(c.NF for c in self.cloths)
+        self.wind_cn, self.wind_ct, self._wind_f, self._wind_w = validate_wind(n_cf, self.tot_NF, c_n, c_t, face_ids, weights)
+        self._dirty.add("wind")
+
+    def set_wind_velocity(self, W):
+        """the wind velocity (3,), m / s, of the steps from now on (a Grad tape records it per step)"""
+        self._wind_W = validate_wind_velocity(W)
+        self._dirty.add("wind_velocity")
+
+    def wind_force(self):
+        """(3,): the net force the wind applies to the cloth at the current positions and start-of-step positions"""
+        return self._ensure_ctx().wind_force(self.pos.t, self.prev_pos.t)
+
+    def _push_wind(self):
+        self._ctx.set_wind(self._wind_f, self._wind_w)
+        self._ctx.set_wind_velocity(self._wind_W)
+        self._ctx.set_param("wind_cn", self.wind_cn)
+        self._ctx.set_param("wind_ct", self.wind_ct)
 
     # ------------------------------------------------------------------ rigid frames for the handles (no counterpart in the reference)
     @property

@@ -54,6 +54,18 @@ def handle_tape_init(grad, sys, T):
         grad.box_poses = Field(torch.zeros((T, grad.n_box, 7), dtype=torch.float64))
         grad.box_poses_prev = Field(torch.zeros((T, grad.n_box, 7), dtype=torch.float64))
         grad.box_grad = Field(torch.zeros((T, grad.n_box, 14), dtype=torch.float64))
+    # wind (BaseScene.set_wind): the wind velocity of every step and d(loss)/d(W of the step, c_n, c_t) per reverse step
+    grad.n_wind = getattr(sys, "n_wind", 0)
+    if grad.n_wind:
+        grad.wind_velocity = Field(torch.zeros((T, 3), dtype=torch.float64))
+        grad.wind_grad = Field(torch.zeros((T, 5), dtype=torch.float64))
+
+
+def wind_velocity_grad(grad):
+    """(T, 3) d(loss)/d(wind velocity trajectory): row s is wind_grad[s, 0:3] (the columns 3 and 4 are the step's shares of d(loss)/d(c_n), d(loss)/d(c_t))"""
+    if not grad.n_wind:
+        raise ValueError("wind_velocity_grad: the scene has no wind")
+    return grad.wind_grad.t[:, 0:3].clone()
 
 
 def box_pose_grad(grad):
@@ -100,6 +112,9 @@ def sphere_centre_grad(grad):
 
 
 def handle_tape_reset(grad):
+    if grad.n_wind:
+        grad.wind_velocity.fill(0)
+        grad.wind_grad.fill(0)
     if grad.n_tie:
         grad.tie_grad.fill(0)
     if grad.n_collider:
@@ -135,6 +150,8 @@ def handle_tape_record(grad, sys, step):
         grad.frame_quat.t[step] = torch.as_tensor(sys._frame_quat)
     if grad.n_collider:
         grad.collider_offsets.t[step] = torch.as_tensor(sys._col_o)
+    if grad.n_wind:   # the wind velocity of the step just completed
+        grad.wind_velocity.t[step] = torch.as_tensor(sys._wind_W)
     if grad.n_sphere:   # the step just completed: its centres, and where the balls were when it started
         grad.sphere_centres.t[step] = torch.as_tensor(sys._sph_cp)
         grad.sphere_centres_prev.t[step] = torch.as_tensor(sys._sph_cp_step)
@@ -155,6 +172,8 @@ def handle_tape_push(grad, sys, step):
         sys.set_frame_poses(grad.frame_pos.t[step].numpy(), grad.frame_quat.t[step].numpy())
     if grad.n_collider:   # the offsets of step `step`: the reverse step evaluates d, d0 and the blocks with them
         sys.set_collider_offsets(grad.collider_offsets.t[step].numpy())
+    if grad.n_wind:   # the wind velocity of step `step`: the reverse step evaluates r with it
+        sys.set_wind_velocity(grad.wind_velocity.t[step].numpy())
     if grad.n_sphere:   # the centres and previous centres of step `step`: the reverse step evaluates the contact frame with them
         sys.set_sphere_centres(grad.sphere_centres.t[step].numpy(), grad.sphere_centres_prev.t[step].numpy())
     if grad.n_capsule:   # the endpoints and previous endpoints of step `step`: the reverse step evaluates t0, the contact frame and the slip with them
@@ -175,6 +194,8 @@ def handle_tape_pull(grad, ctx, step):
         grad.tie_grad.t[step] += torch.as_tensor(ctx.tie_grad(grad.pos_buffer.t[step]))
     if grad.n_collider:   # collider_grad[step] += d(loss)/d(offsets of step `step`, mu) of the reverse step just taken, at the tape state (x_step, x_{step-1})
         grad.collider_grad.t[step] += torch.as_tensor(ctx.collider_grad(grad.pos_buffer.t[step], grad.pos_buffer.t[step - 1]))
+    if grad.n_wind:   # wind_grad[step] += d(loss)/d(W of step `step`, c_n, c_t) of the reverse step just taken, at the tape state (x_step, x_{step-1})
+        grad.wind_grad.t[step] += torch.as_tensor(ctx.wind_grad(grad.pos_buffer.t[step], grad.pos_buffer.t[step - 1]))
     if grad.n_sphere:   # sphere_grad[step] += d(loss)/d(c, cp of step `step`, mu, R) of the reverse step just taken, at the tape state (x_step, x_{step-1})
         grad.sphere_grad.t[step] += torch.as_tensor(ctx.sphere_grad(grad.pos_buffer.t[step], grad.pos_buffer.t[step - 1]))
     if grad.n_capsule:   # capsule_grad[step] += d(loss)/d(a, b, ap, bp of step `step`, mu, R) of the reverse step just taken, at the tape state (x_step, x_{step-1})
@@ -223,6 +244,10 @@ class Grad:
 
     def init_mass(self, sys):
         self.mass.copy_from(sys.mass)
+
+    def wind_velocity_grad(self):
+        """(T, 3) d(loss)/d(wind velocity of every step) = wind_grad[:, 0:3]"""
+        return wind_velocity_grad(self)
 
     def sphere_centre_grad(self):
         """(T, n, 3) d(loss)/d(centre trajectory of the spheres); raises if a step's previous centres were not the centres of the step before"""

@@ -13,7 +13,7 @@ Beyond the reference: ``param_keys`` names further scalars, spelled as ``tsl_set
 """
 import torch
 
-from .analytic_grad_single import handle_tape_init, handle_tape_pull, handle_tape_push, handle_tape_record, handle_tape_reset, sphere_centre_grad, capsule_end_grad, box_pose_grad
+from .analytic_grad_single import handle_tape_init, handle_tape_pull, handle_tape_push, handle_tape_record, handle_tape_reset, sphere_centre_grad, capsule_end_grad, box_pose_grad, wind_velocity_grad
 from .field import Field, ScalarField
 
 
@@ -64,6 +64,10 @@ class Grad:
 
     def init_mass(self, sys):  # :41-44
         self.mass.copy_from(sys.mass)
+
+    def wind_velocity_grad(self):
+        """(T, 3) d(loss)/d(wind velocity of every step) = wind_grad[:, 0:3]"""
+        return wind_velocity_grad(self)
 
     def sphere_centre_grad(self):
         """(T, n, 3) d(loss)/d(centre trajectory of the spheres); raises if a step's previous centres were not the centres of the step before"""

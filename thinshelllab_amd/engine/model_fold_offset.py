@@ -107,6 +107,10 @@ class Cloth:
         b = np.clip(np.array(b, dtype=np.float64), 0.0, 1.0)
         return self.offset_faces + f, b
 
+    def faces(self):
+        """the global ids of this cloth's faces in the scene's face table (BaseScene.faces), ascending: what BaseScene.set_wind takes"""
+        return np.arange(self.offset_faces, self.offset_faces + self.NF, dtype=np.int32)
+
     def _stvk_params(self):
         """(key suffix, value) of the membrane settings that differ from the defaults (pushed by BaseScene when it creates the engine context)"""
         return [(k, f.value) for k, f in (("stvk_mu", self.stvk_mu), ("stvk_lam", self.stvk_lam), ("membrane", self.membrane)) if f.value != 0.0]
