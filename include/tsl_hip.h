@@ -103,7 +103,7 @@ int tsl_ctx_create(const tsl_scene_desc* desc, tsl_ctx** out);
 void tsl_ctx_destroy(tsl_ctx* ctx);
 int tsl_set_stream(tsl_ctx* ctx, void* hip_stream);
 
-/* 0-d field writes of the reference and the engine's own switches (48 keys + three patterns; an unknown key is an error).
+/* 0-d field writes of the reference and the engine's own switches (49 keys + three patterns; an unknown key is an error).
  *  Scene (trajopt_folding.py:50,66; Scene_folding.py:30-31; geometry.py:8-19; geometry_self.py:166-230):
  *   "cloth<i>.Kb|Kl|Ka|k_angle", "elastic<i>.mu|lam|alpha", "mu_cloth_elastic", "mu_cloth_cloth", "k_contact", "eps_contact", "eps_v", "damping",
  *   "k_handle" (0 default: stiffness in N/m of the soft handles of tsl_set_handles; negative fails; with 0, or with no handles, no handle kernel is launched),
@@ -116,6 +116,8 @@ int tsl_set_stream(tsl_ctx* ctx, void* hip_stream);
  *   capsules, no capsule kernel is launched),
  *   "k_box" (0 default: stiffness in N/m shared by the rounded-box colliders of tsl_set_boxes; negative or non-finite fails; with 0, or with no
  *   boxes, no box kernel is launched),
+ *   "k_sdf" (0 default: stiffness in N/m shared by the sampled distance-field colliders of tsl_set_sdfs; negative or non-finite fails; with 0, or
+ *   with no fields, no field kernel is launched),
  *   "cloth<i>.membrane" (0 default: edge springs Kl + area term Ka, as the reference; 1: a St. Venant-Kirchhoff membrane per face, A0 Psi(F) with
  *   F = [x1 - x0, x2 - x0] Dm^-1, Dm the rest triangle rebuilt from the face's rest lengths (fails naming a face whose lengths violate the triangle
  *   inequality), Psi = mu |E|^2 + lam/2 tr(E)^2, E = (F^T F - I) / 2, A0 the rest area; it replaces the springs and the area term of the cloth's
@@ -477,6 +479,67 @@ int tsl_set_wind_velocity(tsl_ctx* ctx, const double* W_host);
 int tsl_wind_count(tsl_ctx* ctx, int32_t* out_host);
 int tsl_wind_force(tsl_ctx* ctx, const double* pos_dev, const double* prev_pos_dev, double* out_host);
 int tsl_wind_grad(tsl_ctx* ctx, const double* pos_dev, const double* prev_pos_dev, const double* p_dev, double* out_host);
+
+/* Sampled distance-field colliders (no reference counterpart: its moulds are meshed bodies with every vertex frozen): up to TSL_MAX_SDFS solids
+ * {phi < r} with the cloth outside, phi sampled on a grid -- a mould a sheet is formed into, a bowl, a ring, a shoulder, a jaw with a groove: any
+ * solid, concave ones included.  Field j has dimensions (n0, n1, n2), each in [4, 512], one isotropic spacing h > 0, an origin o (the local position
+ * of sample (0, 0, 0)) and n0 n1 n2 doubles in C order, at most 2^26 over the list, all fixed once the list is set; an offset r (any finite value),
+ * a friction coefficient mu >= 0, and a pose (centre c, quaternion (s, x, y, z), normalised by the library) that may be set before every step, with
+ * the previous pose cp, R0.  The stiffness "k_sdf" of tsl_set_param is shared (0 by default: off), the thickness of the shell is eps_contact, the
+ * friction regularisation eh = eps_v dt.  A per-vertex 8-bit mask of its own says which fields act on a vertex.  phi is the tensor-product uniform
+ * cubic B-spline over the samples (C2; its gradient is C1 everywhere, so the reverse step's operator is the exact second derivative of the energy):
+ *   t = (y - o) / h,  i_a = floor(t_a),  f_a = t_a - i_a,   valid  <=>  1 <= t_a < n_a - 2 for a = 0, 1, 2   (in double; NaN is not valid)
+ *   phi(y) = sum_{a,b,c in 0..3} B_a(f_0) B_b(f_1) B_c(f_2) s[i_0-1+a, i_1-1+b, i_2-1+c]
+ *   B_0 = (1-f)^3/6,  B_1 = (3f^3 - 6f^2 + 4)/6,  B_2 = (-3f^3 + 3f^2 + 3f + 1)/6,  B_3 = f^3/6;  grad phi: one factor B' and 1/h;  Hess phi: B'' or
+ *   B'B' and 1/h^2.
+ * The samples are the control values: a sampled linear field is reproduced exactly, a constant added to the samples is added to phi, a curved field
+ * is smoothed by about h^2/6 times its Laplacian.  For vertex v and field j, with x_prev the start-of-step positions:
+ *   y  = R^T (x - c),        d  = phi(y) - r,    m  = R grad phi(y)   (not normalised: the energy is a function of phi itself)
+ *   y0 = R0^T (x_prev - cp), d0 = phi(y0) - r,   s0 = |grad phi(y0)|,  n0 = R0 grad phi(y0) / s0
+ *   lam = [y0 valid][s0 >= 1e-12] mu k max(0, eps - d0),  D = (x - c) - R y0 = (x - x_prev) - dc,  dc = (c - cp) + (R - R0) y0,
+ *   P0 = I - n0 n0^T,  w = P0 D,  r_w = |w|,  a1 = f1(r_w),  M = a1 P0 + [r_w > 1e-9] (f2 / r_w) w w^T
+ *   E = [y valid][d < eps] 1/2 k (d - eps)^2 + lam f0(r_w),  g = [y valid][d < eps] k (d - eps) m + lam a1 w,
+ *   H = H_n + lam M on the vertex's own diagonal block,  H_n = [y valid][d < eps] k (m m^T + (d - eps) R Hess phi(y) R^T).
+ * tsl_assemble with spd = 0 (the reverse step's operator) adds H_n exact; every other mode, with and without "spd_literal", adds
+ * [y valid][d < eps] k m m^T, the Gauss-Newton part: positive semi-definite, but not the eigen-clamp of H_n (a general field has no closed-form clamp
+ * worth its cost in a 3 x 3 block).  Outside the valid region a pair contributes nothing -- at x no normal term, at x_prev no friction --: a solid
+ * that reaches the border of its grid ends there, and keeping it inside is the caller's business.  No constraint slot, no row list: the plans of
+ * the factorisation and tsl_contact_counts do not depend on fields.  Nothing is stored per step.  Frozen dofs follow the mask rule.  One lane per
+ * vertex, no atomics: the same bits run to run.  With no fields or k_sdf = 0 every launch is the one it was.  Not modelled: gradients for the
+ * samples, a prefilter that makes the spline interpolate, anisotropic spacing, more than TSL_MAX_SDFS fields, any check that a solid stays inside its
+ * grid.
+ *   tsl_set_sdfs: samples_host (the fields' samples one after the other), dims_host (n x 3 int32), origins_host (n x 3), spacings_host (n),
+ *     centres_host (n x 3), quats_host (n x 4), offsets_host (n), mu_host (n), vertex_mask_host (tot_NV bytes, bit j: field j acts on the vertex; NULL:
+ *     every field on every vertex); host pointers, copied; the previous poses := the poses; the stream is synchronised; n = 0 removes the fields and
+ *     frees the samples.  Fails, naming the offender, and leaves the previous list AND the previous samples in place for n < 0 or more than
+ *     TSL_MAX_SDFS fields, a null array, a dimension below 4 or above 512, more than 2^26 samples in total, a spacing that is not finite and
+ *     positive, a non-finite origin, offset, centre or sample (named by the field and its three indices), a zero or non-finite quaternion, a negative
+ *     or non-finite mu, a mask byte that names a field at or above n.
+ *   tsl_set_sdf_poses: centres_host, quats_host and prev_centres_host, prev_quats_host (both NULL: the previous poses := the poses; exactly one NULL
+ *     fails) for the next energy, assemble, step or adjoint step; set those of step s before the reverse step s and before tsl_sdf_grad.  A
+ *     non-finite centre or a zero or non-finite quaternion fails, naming the field, and leaves all four in place.
+ *   tsl_sdf_count: n.
+ *   tsl_sdf_force: out_host (n x 6) at the state (pos, prev_pos): [0:3] -sum_v g_v of field j, the net force the solid applies to the cloth;
+ *     [3:6] -sum_v (x_v - c) x g_v, its torque about the field's centre in the same sign; frozen dofs are NOT masked; k_sdf = 0: zeros.
+ *   tsl_sdf_grad: out_host (n x 14) at the tape state (pos = x_s, prev_pos = x_{s-1}), sign of tsl_box_grad, p the adjoint solution on its free
+ *     dofs (p_dev == NULL: the solution of the last tsl_adjoint_step): the share of one reverse step in
+ *       [0:3]  d(loss)/d(c_j)       = sum_v H_n p_v + lam M p_v   (H_n exact),
+ *       [3:6]  d(loss)/d(theta_j)   = sum_v (x - c) x (H_n p_v) + p_v x g_n + (R y0) x (lam M p_v),   g_n = [y valid][d < eps] k (d - eps) m,
+ *       [6:9]  d(loss)/d(cp_j)      = -sum_v X,
+ *       [9:12] d(loss)/d(theta_p_j) = sum_v -(x_prev - cp) x X - lam n0 x z,
+ *       [12]   d(loss)/d(mu_j)      = -sum_v p_v . k max(0, eps - d0) a1 w,
+ *       [13]   d(loss)/d(r_j)       = -sum_v p_v . (-[d < eps] k m + [d0 < eps] mu k a1 w),
+ *     with theta, theta_p world-frame rotation vectors applied on the left (R <- exp([theta]x) R, as tsl_box_grad), B = a1 I + [r_w > 1e-9]
+ *     (f2 / r_w) w w^T, z = -((n0 . D) B p_v + D (n0 . B p_v)) and
+ *       X = lam (R0 R^T M p_v - R0 Hess phi(y0) R0^T P0 z / s0) + [d0 < eps] mu k s0 n0 (a1 w . p_v) = -(dg/dx_prev)^T p_v,
+ *     which the reverse step itself adds to the free dofs of the vertex's row of pos_grad[s-1].  There is no gradient for the samples. */
+#define TSL_MAX_SDFS 8
+int tsl_set_sdfs(tsl_ctx* ctx, const double* samples_host, const int32_t* dims_host, const double* origins_host, const double* spacings_host, const double* centres_host,
+                 const double* quats_host, const double* offsets_host, const double* mu_host, int32_t n, const uint8_t* vertex_mask_host);
+int tsl_set_sdf_poses(tsl_ctx* ctx, const double* centres_host, const double* quats_host, const double* prev_centres_host, const double* prev_quats_host);
+int tsl_sdf_count(tsl_ctx* ctx, int32_t* out_host);
+int tsl_sdf_force(tsl_ctx* ctx, const double* pos_dev, const double* prev_pos_dev, double* out_host);
+int tsl_sdf_grad(tsl_ctx* ctx, const double* pos_dev, const double* prev_pos_dev, const double* p_dev, double* out_host);
 
 /* BaseScene.compute_energy (BaseScene.py:427-451) at the given state, constraints as last detected. */
 int tsl_energy(tsl_ctx* ctx, const double* pos_dev, const double* prev_pos_dev, const double* vel_dev,

@@ -78,6 +78,7 @@ EXPORTS = [
     "tsl_set_colliders", "tsl_set_collider_offsets", "tsl_collider_count", "tsl_collider_force", "tsl_collider_grad",
     "tsl_set_spheres", "tsl_set_sphere_centres", "tsl_sphere_count", "tsl_sphere_force", "tsl_sphere_grad",
     "tsl_set_capsules", "tsl_set_capsule_ends", "tsl_capsule_count", "tsl_capsule_force", "tsl_capsule_grad", "tsl_set_boxes", "tsl_set_box_poses", "tsl_box_count", "tsl_box_force", "tsl_box_grad",
+    "tsl_set_sdfs", "tsl_set_sdf_poses", "tsl_sdf_count", "tsl_sdf_force", "tsl_sdf_grad",
     "tsl_set_wind", "tsl_set_wind_velocity", "tsl_wind_count", "tsl_wind_force", "tsl_wind_grad", "tsl_energy", "tsl_assemble", "tsl_solve", "tsl_step", "tsl_contact_detect",
     "tsl_contact_reset", "tsl_contact_counts", "tsl_update_ref_angle", "tsl_adjoint_step", "tsl_param_grad", "tsl_param_grad_keys", "tsl_friction_grad", "tsl_elastic_force", "tsl_matrix_nnzb", "tsl_matrix_export", "tsl_matrix_import",
     "tsl_constraints_export", "tsl_contact_blocks_export", "tsl_proj_export", "tsl_proj_import", "tsl_set_border", "tsl_spd_project", "tsl_profile_reset", "tsl_profile_read", "tsl_profile_read_events",
@@ -151,6 +152,11 @@ def load():
     L.tsl_box_count.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
     L.tsl_box_force.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.tsl_box_grad.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.tsl_set_sdfs.argtypes = [C.c_void_p] + [C.c_void_p] * 8 + [C.c_int32, C.c_void_p]
+    L.tsl_set_sdf_poses.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.tsl_sdf_count.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
+    L.tsl_sdf_force.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.tsl_sdf_grad.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.tsl_set_wind.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]
     L.tsl_set_wind_velocity.argtypes = [C.c_void_p, C.c_void_p]
     L.tsl_wind_count.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]

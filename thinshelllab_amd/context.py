@@ -421,6 +421,55 @@ class TslContext:
         adjoint_step, else a 3 * tot_NV device vector"""
         return self._shape_grad("box", 14, pos, prev_pos, p)
 
+    # ---- sampled distance-field colliders (tsl_set_sdfs; stiffness: set_param("k_sdf", k))
+    def set_sdfs(self, grids, origins, spacings, centres, quats, offsets, mu, vertex_mask=None):
+        """n solids {phi < offset} with the cloth outside, phi the cubic B-spline over grids[j] (a 3-d array of samples, every dimension in [4, 512], C
+        order) with spacing spacings[j] and origins[j] the local position of sample (0, 0, 0); centre c_j, quaternion (s, x, y, z), friction mu_j;
+        vertex_mask (tot_NV,) uint8, bit j: field j acts on the vertex, None: all on all; an empty list removes them and frees the samples.  The
+        quaternions are normalised by the library; the previous poses are set to the poses; samples, spacings, origins and offsets stay fixed."""
+        g = [np.ascontiguousarray(_np(a, np.float64)) for a in grids]
+        n = len(g)
+        assert all(a.ndim == 3 for a in g), [a.shape for a in g]
+        dims = np.array([a.shape for a in g], np.int32).reshape(-1, 3)
+        smp = np.concatenate([a.reshape(-1) for a in g]) if n else np.zeros(0)
+        o = _np(origins, np.float64).reshape(-1, 3)
+        h = _np(spacings, np.float64).reshape(-1)
+        ce = _np(centres, np.float64).reshape(-1, 3)
+        qu = _np(quats, np.float64).reshape(-1, 4)
+        r = _np(offsets, np.float64).reshape(-1)
+        m = _np(mu, np.float64).reshape(-1)
+        assert o.shape == (n, 3) and h.shape == (n,) and ce.shape == (n, 3) and qu.shape == (n, 4) and r.shape == (n,) and m.shape == (n,), (n, o.shape, h.shape, ce.shape, qu.shape, r.shape, m.shape)
+        vm = None if vertex_mask is None else _np(vertex_mask, np.uint8).reshape(-1)
+        assert vm is None or vm.shape == (self.tot_NV,), vm.shape
+        ptr = lambda a: a.ctypes.data if n else None
+        check(self.L.tsl_set_sdfs(self.h, ptr(smp), ptr(dims), ptr(o), ptr(h), ptr(ce), ptr(qu), ptr(r), ptr(m), n, None if vm is None else vm.ctypes.data), "tsl_set_sdfs")
+
+    def set_sdf_poses(self, centres, quats, prev_centres=None, prev_quats=None):
+        """the poses of the next energy / assembly / step / reverse step and where the fields were at the start of that step (both None: the poses)"""
+        n = self.sdf_count()
+        ce = _np(centres, np.float64).reshape(-1, 3)
+        qu = _np(quats, np.float64).reshape(-1, 4)
+        pc = None if prev_centres is None else _np(prev_centres, np.float64).reshape(-1, 3)
+        pq = None if prev_quats is None else _np(prev_quats, np.float64).reshape(-1, 4)
+        assert ce.shape == (n, 3) and qu.shape == (n, 4) and (pc is None or pc.shape == (n, 3)) and (pq is None or pq.shape == (n, 4)), (ce.shape, qu.shape, n)
+        if n:
+            check(self.L.tsl_set_sdf_poses(self.h, ce.ctypes.data, qu.ctypes.data, None if pc is None else pc.ctypes.data, None if pq is None else pq.ctypes.data),
+                  "tsl_set_sdf_poses")
+
+    def sdf_count(self):
+        return self._shape_count("sdf")
+
+    def sdf_force(self, pos, prev_pos):
+        """(n, 6): [0:3] -sum_v g_v, the net force every field's solid applies to the cloth at the state (pos, prev_pos), [3:6] -sum_v (x_v - c) x g_v, its
+        torque about the field's centre (frozen dofs not masked)"""
+        return self._shape_force("sdf", 6, pos, prev_pos)
+
+    def sdf_grad(self, pos, prev_pos, p=None):
+        """(n, 14) contribution of one reverse step to d(loss)/d(c (3), theta (3), previous c (3), previous theta (3), mu, offset) of every field at the tape
+        state (x_s, x_{s-1}) with the poses of step s in place (theta: world-frame rotation vectors applied on the left); p None: the solution of the
+        last adjoint_step, else a 3 * tot_NV device vector"""
+        return self._shape_grad("sdf", 14, pos, prev_pos, p)
+
     # ---- wind (tsl_set_wind; coefficients: set_param("wind_cn", c_n), set_param("wind_ct", c_t))
     def set_wind(self, faces=None, weights=None):
         """lagged aerodynamic drag on the cloth faces `faces` (global face ids, each once) with the weights `weights` (None: 1 each); faces None: every

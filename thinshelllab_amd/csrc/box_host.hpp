@@ -14,14 +14,15 @@
 using BoxTable = ShapeTable<29>;
 enum { BOX_C = 0, BOX_R = 3, BOX_CP = 12, BOX_R0 = 15, BOX_H = 24, BOX_RAD = 27, BOX_MU = 28 };
 
-// one pose (what = "" or "previous "): empty and out = (c (3), R (9)), or the message that names the offender
-static inline std::string box_pose_check(const char* what, const double* c, const double* q, int j, double* out) {
+// one pose (what = "" or "previous "): empty and out = (c (3), R (9)), or the message that names the offender (noun: what carries the pose; the
+// sampled fields of sdf_host.hpp take the same rule)
+static inline std::string box_pose_check(const char* what, const double* c, const double* q, int j, double* out, const char* noun = "box") {
 #pragma clang fp contract(off)
   char buf[256];
-  if (!finite3(c)) { snprintf(buf, sizeof(buf), "%scentre (%g, %g, %g) of box %d is not finite", what, c[0], c[1], c[2], j); return buf; }
+  if (!finite3(c)) { snprintf(buf, sizeof(buf), "%scentre (%g, %g, %g) of %s %d is not finite", what, c[0], c[1], c[2], noun, j); return buf; }
   const double n = std::sqrt(((q[0] * q[0] + q[1] * q[1]) + q[2] * q[2]) + q[3] * q[3]);
   if (!(n > 0.0) || !std::isfinite(n)) {
-    snprintf(buf, sizeof(buf), "%squaternion (%g, %g, %g, %g) of box %d is zero or not finite", what, q[0], q[1], q[2], q[3], j); return buf;
+    snprintf(buf, sizeof(buf), "%squaternion (%g, %g, %g, %g) of %s %d is zero or not finite", what, q[0], q[1], q[2], q[3], noun, j); return buf;
   }
   const double s = q[0] / n, x = q[1] / n, y = q[2] / n, z = q[3] / n;
   for (int a = 0; a < 3; a++) out[a] = c[a];

@@ -1,13 +1,14 @@
-// Host side of the four collider kinds inside libtsl_hip.so -- planes (k_collider.hpp), balls (k_sphere.hpp; 2.9), rods (k_capsule.hpp;
-// 2.10), rounded boxes (k_box.hpp; 2.12): the entry points tsl_set_colliders .. tsl_box_grad of include/tsl_hip.h and, for the launch sites of tsl_hip.hip and adjoint_api.hpp,
+// Host side of the five collider kinds inside libtsl_hip.so -- planes (k_collider.hpp), balls (k_sphere.hpp; 2.9), rods (k_capsule.hpp;
+// 2.10), rounded boxes (k_box.hpp; 2.12), sampled distance fields (k_sdf.hpp; 2.14): the entry points tsl_set_colliders .. tsl_sdf_grad of include/tsl_hip.h and, for the launch sites of tsl_hip.hip and adjoint_api.hpp,
 // the launches of an assembly, an energy and a reverse step.  One set of helpers, templates on the kind's Shape (k_shape.hpp);
-// an entry point checks what is particular to its kind (collider_host.hpp, sphere_host.hpp, capsule_host.hpp, box_host.hpp) and hands on.  Included by
+// an entry point checks what is particular to its kind (collider_host.hpp, sphere_host.hpp, capsule_host.hpp, box_host.hpp, sdf_host.hpp) and hands on.  Included by
 // tsl_hip.hip behind its helpers (tsl_fail, TSL_TRY, HIP_OK, Scope, nblk), the way handle_api.hpp is.
 #pragma once
 #include <type_traits>
 #include "k_box.hpp"
 #include "k_capsule.hpp"
 #include "k_collider.hpp"
+#include "k_sdf.hpp"
 #include "k_sphere.hpp"
 #include "tsl_ctx.hpp"
 
@@ -16,7 +17,8 @@ static auto& shape_set(tsl_ctx* c) {
   if constexpr (std::is_same_v<Shape, PlaneShape>) return c->col;
   else if constexpr (std::is_same_v<Shape, SphereShape>) return c->sph;
   else if constexpr (std::is_same_v<Shape, CapsuleShape>) return c->cap;
-  else return c->box;
+  else if constexpr (std::is_same_v<Shape, BoxShape>) return c->box;
+  else return c->sdf;
 }
 // the kernels of a kind in an energy / assembly / reverse step run only while this holds: without it the launches are the ones they were
 template <class Shape>
@@ -32,7 +34,7 @@ template <class Shape>
 static ShapeArgs shape_args(tsl_ctx* c) { return ShapeArgs{c->NV, shape_set<Shape>(c).mask.p}; }
 static int shape_nblk(const tsl_ctx* c) { return nblk(c->NV, 256); }
 // how many kinds hold shapes, on or not (they size the energy partials)
-static int shapes_present(tsl_ctx* c) { return (c->col.tab.n > 0) + (c->sph.tab.n > 0) + (c->cap.tab.n > 0) + (c->box.tab.n > 0); }
+static int shapes_present(tsl_ctx* c) { return (c->col.tab.n > 0) + (c->sph.tab.n > 0) + (c->cap.tab.n > 0) + (c->box.tab.n > 0) + (c->sdf.tab.n > 0); }
 
 template <class Shape>
 static void shape_assemble_launch(tsl_ctx* c, hipStream_t s, int spd, const double* pos, const double* prev, double* grad) {
@@ -52,13 +54,14 @@ static void shape_backprop_launch(tsl_ctx* c, hipStream_t s, const double* x_s, 
   hipLaunchKernelGGL(k_shape_backprop<Shape>, dim3(shape_nblk(c)), dim3(256), 0, s, shape_table<Shape>(c), shape_args<Shape>(c), (const int*)c->frozen.p, x_s, x_prev, p, pg_prev);
 }
 
-// The colliders in an assembly: gradient rows and diagonal blocks behind the vertex terms on the same stream -- planes, then balls, then rods, then boxes; a
+// The colliders in an assembly: gradient rows and diagonal blocks behind the vertex terms on the same stream -- planes, then balls, then rods, then boxes, then fields; a
 // kind that is not on launches nothing.  spd 0: the exact block of the reverse step's operator; every other mode: the projected one
 static void shapes_assemble_launch(tsl_ctx* c, hipStream_t s, int spd, const double* pos, const double* prev, double* grad) {
   shape_assemble_launch<PlaneShape>(c, s, spd, pos, prev, grad);
   shape_assemble_launch<SphereShape>(c, s, spd, pos, prev, grad);
   shape_assemble_launch<CapsuleShape>(c, s, spd, pos, prev, grad);
   shape_assemble_launch<BoxShape>(c, s, spd, pos, prev, grad);
+  shape_assemble_launch<SdfShape>(c, s, spd, pos, prev, grad);
 }
 // Their energy partials from e_part on, one per workgroup of 256 vertices and kind that is on, in the same order; returns how many
 static int shapes_energy_launch(tsl_ctx* c, hipStream_t s, const double* pos, const double* prev, double* e_part) {
@@ -67,15 +70,17 @@ static int shapes_energy_launch(tsl_ctx* c, hipStream_t s, const double* pos, co
   shape_energy_launch<SphereShape>(c, s, pos, prev, e_part, nb);
   shape_energy_launch<CapsuleShape>(c, s, pos, prev, e_part, nb);
   shape_energy_launch<BoxShape>(c, s, pos, prev, e_part, nb);
+  shape_energy_launch<SdfShape>(c, s, pos, prev, e_part, nb);
   return nb;
 }
 // Their share of a reverse step that goes into pos_grad[s-1] (x_s, x_{s-1}, the adjoint solution p), in the same order: the planes' lagged
-// friction; the balls' lagged friction and lagged contact frame; the rods' lagged friction, lagged contact frame and lagged rod parameter; the boxes' lagged friction, lagged contact frame and lagged material point
+// friction; the balls' lagged friction and lagged contact frame; the rods' lagged friction, lagged contact frame and lagged rod parameter; the boxes' lagged friction, lagged contact frame and lagged material point; the fields' likewise
 static void shapes_backprop_launch(tsl_ctx* c, hipStream_t s, const double* x_s, const double* x_prev, const double* p, double* pg_prev) {
   shape_backprop_launch<PlaneShape>(c, s, x_s, x_prev, p, pg_prev);
   shape_backprop_launch<SphereShape>(c, s, x_s, x_prev, p, pg_prev);
   shape_backprop_launch<CapsuleShape>(c, s, x_s, x_prev, p, pg_prev);
   shape_backprop_launch<BoxShape>(c, s, x_s, x_prev, p, pg_prev);
+  shape_backprop_launch<SdfShape>(c, s, x_s, x_prev, p, pg_prev);
 }
 
 // The tail of tsl_set_*: T is the checked list of n shapes (the kind's host header); the mask is checked here and becomes a device buffer of NV
@@ -241,4 +246,43 @@ extern "C" int tsl_box_force(tsl_ctx* c, const double* pos, const double* prev, 
 }
 extern "C" int tsl_box_grad(tsl_ctx* c, const double* pos, const double* prev, const double* p_dev, double* out_host) {
   return shape_grad<BoxShape>(c, "tsl_box_grad", pos, prev, p_dev, out_host);
+}
+
+// ---- sampled distance fields.  The previous poses of a new list are its poses.  The samples of all fields go into one device buffer: a new list is
+// checked, uploaded into a NEW buffer and swapped in once everything succeeded, so that a refusal leaves the previous list and the previous samples in
+// place; n = 0 (and the context's destruction) frees the buffer.  Force: n x 6, the net force -sum_v g_v of every field and its torque
+// -sum_v (x_v - c) x g_v about the field's centre.  Grad: n x 14, d(loss)/d(c_j, theta_j, cp_j, theta_p_j, mu_j, r_j), the poses and previous poses of
+// step s in place
+extern "C" int tsl_set_sdfs(tsl_ctx* c, const double* samples, const int32_t* dims, const double* origins, const double* spacings, const double* centres, const double* quats,
+                            const double* offsets, const double* mu, int32_t n, const uint8_t* vertex_mask) {
+  Scope scope(c);
+  (void)hipStreamSynchronize(c->stream);
+  std::string err;
+  SdfTable S = c->sdf.tab;
+  size_t total = 0;
+  if (sdf_validate(samples, dims, origins, spacings, centres, quats, offsets, mu, n, S, total, err)) return tsl_fail("tsl_set_sdfs: %s", err.c_str());
+  DevBuf<double> fresh;
+  if (n > 0) {
+    TSL_TRY(fresh.alloc(total));
+    HIP_OK(hipMemcpy(fresh.p, samples, total * sizeof(double), hipMemcpyHostToDevice));
+  }
+  S.smp = fresh.p;
+  TSL_TRY(shape_commit<SdfShape>(c, "tsl_set_sdfs", "field", S, n, vertex_mask));
+  c->sdf_smp.swap(fresh);   // (the previous buffer leaves with `fresh`)
+  return 0;
+}
+extern "C" int tsl_set_sdf_poses(tsl_ctx* c, const double* centres, const double* quats, const double* prev_centres, const double* prev_quats) {
+  Scope scope(c);
+  (void)hipStreamSynchronize(c->stream);
+  if (c->sdf.tab.n == 0) return 0;
+  std::string err;
+  if (sdf_poses_validate(centres, quats, prev_centres, prev_quats, c->sdf.tab, err)) return tsl_fail("tsl_set_sdf_poses: %s", err.c_str());
+  return 0;
+}
+extern "C" int tsl_sdf_count(tsl_ctx* c, int32_t* out) { return shape_count<SdfShape>(c, "tsl_sdf_count", out); }
+extern "C" int tsl_sdf_force(tsl_ctx* c, const double* pos, const double* prev, double* out_host) {
+  return shape_force<SdfShape>(c, "tsl_sdf_force", pos, prev, out_host);
+}
+extern "C" int tsl_sdf_grad(tsl_ctx* c, const double* pos, const double* prev, const double* p_dev, double* out_host) {
+  return shape_grad<SdfShape>(c, "tsl_sdf_grad", pos, prev, p_dev, out_host);
 }

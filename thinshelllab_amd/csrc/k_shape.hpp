@@ -1,6 +1,6 @@
 // The collider layer that the kinds share: everything of a collider kernel that is not geometry.  A kind -- planes (k_collider.hpp),
-// balls (k_sphere.hpp), rods (k_capsule.hpp), rounded boxes (k_box.hpp) -- is a struct Shape of static device functions and constants:
-//   Table              its ShapeTable (shape_host.hpp), by value in the kernel arguments
+// balls (k_sphere.hpp), rods (k_capsule.hpp), rounded boxes (k_box.hpp), sampled distance fields (k_sdf.hpp) -- is a struct Shape of static device functions and constants:
+//   Table              its ShapeTable (shape_host.hpp) or a type derived from it (SdfTable), by value in the kernel arguments
 //   stride             slots of one shape in the partial buffer of the read-outs (>= n_force, n_grad)
 //   n_force, n_grad    values per shape of the two read-outs
 //   assemble(T, j, x, xp, exact, g, H)   g += the pair's gradient, H += its 3 x 3 block

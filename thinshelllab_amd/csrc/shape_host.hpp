@@ -1,6 +1,6 @@
-// Host side that the four collider kinds share: the table a kind's kernels take, the per-vertex mask and the checks that differ
-// between the kinds only in a noun ("collider", "sphere", "capsule", "box").  What is particular to a kind -- its rows and their checks -- is in
-// collider_host.hpp, sphere_host.hpp, capsule_host.hpp and box_host.hpp.  Plain C++ with no device code, so that it can also be compiled into a stand-alone
+// Host side that the five collider kinds share: the table a kind's kernels take, the per-vertex mask and the checks that differ
+// between the kinds only in a noun ("collider", "sphere", "capsule", "box", "field").  What is particular to a kind -- its rows and their checks -- is in
+// collider_host.hpp, sphere_host.hpp, capsule_host.hpp, box_host.hpp and sdf_host.hpp.  Plain C++ with no device code, so that it can also be compiled into a stand-alone
 // program (a CPU build under a sanitizer) without the rest of the library, as tie_host.hpp.
 #pragma once
 #include <climits>

@@ -16,6 +16,7 @@
 #include "collider_host.hpp"
 #include "sphere_host.hpp"
 #include "box_host.hpp"
+#include "sdf_host.hpp"
 #include "capsule_host.hpp"
 #include "k_body.hpp"
 #include "direct_plan.hpp"
@@ -425,11 +426,14 @@ struct tsl_ctx {
   DevBuf<double> ti_b, ti_w, ti_out;   // n x 3, n, n x 3 (read-outs of tsl_tie_force / tsl_tie_residuals / tsl_tie_grad)
   // ---- colliders (collider_api.hpp; k_shape.hpp): one set per kind -- planes (tsl_set_colliders, k_collider.hpp), balls (tsl_set_spheres,
   // k_sphere.hpp: centres and previous centres), rods (tsl_set_capsules, k_capsule.hpp: endpoints and previous endpoints), rounded boxes
-  // (tsl_set_boxes, k_box.hpp: poses and previous poses).  A kind's kernels run while tab.n > 0 and k != 0
+  // (tsl_set_boxes, k_box.hpp: poses and previous poses), sampled distance fields (tsl_set_sdfs, k_sdf.hpp: poses and previous poses; sdf_smp: the
+  // samples of all fields, which sdf.tab.smp points to).  A kind's kernels run while tab.n > 0 and k != 0
   ShapeSet<ColliderPlanes> col;
   ShapeSet<SphereTable> sph;
   ShapeSet<CapsuleTable> cap;
   ShapeSet<BoxTable> box;
+  ShapeSet<SdfTable> sdf;
+  DevBuf<double> sdf_smp;
   // ---- wind (tsl_set_wind, "wind_cn" / "wind_ct"; wind_api.hpp): lagged drag on a list of cloth faces
   WindSet wind;
 

@@ -284,9 +284,9 @@ extern "C" int tsl_set_param(tsl_ctx* c, const char* key, double v) {
     c->k_tie = v;
     TSL_TRY(tie_slots_refresh(c));   // (the tie slots exist while k_tie != 0)
   }
-  else if (k == "k_collider" || k == "k_sphere" || k == "k_capsule" || k == "k_box") {
+  else if (k == "k_collider" || k == "k_sphere" || k == "k_capsule" || k == "k_box" || k == "k_sdf") {
     if (!(v >= 0.0) || !std::isfinite(v)) return tsl_fail("tsl_set_param: %s must be finite and >= 0 (got %g)", key, v);
-    (k == "k_collider" ? c->col.k : k == "k_sphere" ? c->sph.k : k == "k_capsule" ? c->cap.k : c->box.k) = v;
+    (k == "k_collider" ? c->col.k : k == "k_sphere" ? c->sph.k : k == "k_capsule" ? c->cap.k : k == "k_box" ? c->box.k : c->sdf.k) = v;
   }
   else if (k == "wind_cn" || k == "wind_ct") {
     if (!(v >= 0.0) || !std::isfinite(v)) return tsl_fail("tsl_set_param: %s must be finite and >= 0 (got %g)", key, v);

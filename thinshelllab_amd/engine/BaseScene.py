@@ -129,7 +129,8 @@ def validate_ties(tot_NV, faces_tab, vertex_ids, face_ids, bary, weights=None):
 
 
 SHAPE_MAX = 8   # colliders of one kind: one bit each in a vertex's mask byte (csrc/shape_host.hpp)
-TSL_MAX_COLLIDERS = TSL_MAX_SPHERES = TSL_MAX_CAPSULES = TSL_MAX_BOXES = SHAPE_MAX
+TSL_MAX_COLLIDERS = TSL_MAX_SPHERES = TSL_MAX_CAPSULES = TSL_MAX_BOXES = TSL_MAX_SDFS = SHAPE_MAX
+SDF_DIM_MIN, SDF_DIM_MAX, SDF_SAMPLES_MAX = 4, 512, 1 << 26   # (csrc/sdf_host.hpp)
 
 
 def _check_shape(who, noun, j, mu, radius=None):
@@ -293,13 +294,14 @@ def validate_capsules(tot_NV, ends_a, ends_b, radii, mu, vertex_ids=None):
     return a.copy(), b.copy(), r.copy(), m.copy(), _shape_mask("set_capsules", "capsule", tot_NV, n, vertex_ids)
 
 
-def _box_pose_check(who, what, c, q, j):
-    """the message of csrc/box_host.hpp for the pose of box j (what: "" or "previous "), or None"""
+def _box_pose_check(who, what, c, q, j, noun="box"):
+    """the message of csrc/box_host.hpp's box_pose_check for the pose of box j (what: "" or "previous "; noun: what carries the pose -- the sampled
+    fields take the same rule), or None"""
     if not np.isfinite(c).all():
-        return f"{who}: {what}centre ({c[0]:g}, {c[1]:g}, {c[2]:g}) of box {j} is not finite"
+        return f"{who}: {what}centre ({c[0]:g}, {c[1]:g}, {c[2]:g}) of {noun} {j} is not finite"
     n = math.sqrt(((q[0] * q[0] + q[1] * q[1]) + q[2] * q[2]) + q[3] * q[3]) if np.isfinite(q).all() else float("nan")
     if not (n > 0.0 and math.isfinite(n)):
-        return f"{who}: {what}quaternion ({q[0]:g}, {q[1]:g}, {q[2]:g}, {q[3]:g}) of box {j} is zero or not finite"
+        return f"{who}: {what}quaternion ({q[0]:g}, {q[1]:g}, {q[2]:g}, {q[3]:g}) of {noun} {j} is zero or not finite"
     return None
 
 
@@ -330,6 +332,54 @@ def validate_boxes(tot_NV, centres, quats, half_extents, radii, mu, vertex_ids=N
     if vertex_ids is not None and len(vertex_ids) != n:
         raise ValueError(f"set_boxes: {len(vertex_ids)} vertex lists for {n} boxes")
     return c.copy(), q, h.copy(), r.copy(), m.copy(), _shape_mask("set_boxes", "box", tot_NV, n, vertex_ids)
+
+
+def validate_sdfs(tot_NV, grids, origins, spacings, centres, quats, offsets, mu, vertex_ids=None):
+    """The checks of tsl_set_sdfs on the host, with the messages of csrc/sdf_host.hpp: returns (grids (list of C-ordered float64 arrays), origins (n, 3),
+    spacings (n), centres (n, 3), unit quaternions (n, 4), offsets (n), mu (n), uint8 mask (tot_NV)) or raises ValueError naming the offender -- more
+    than SHAPE_MAX fields, a grid that is not 3-d, a dimension below 4 or above 512, more than 2^26 samples in total, a spacing that is not finite and
+    positive, a non-finite origin, offset, centre or sample, a zero or non-finite quaternion, a negative or non-finite friction coefficient, a vertex
+    id out of range.  vertex_ids None: every field acts on every vertex; else one entry per field, None (all vertices) or a list of global vertex ids."""
+    g = [np.array(a, dtype=np.float64, order="C") for a in grids]
+    n = len(g)
+    o = np.asarray(origins, dtype=np.float64).reshape(-1, 3) if n else np.zeros((0, 3))
+    h = np.asarray(spacings, dtype=np.float64).reshape(-1)
+    c = np.asarray(centres, dtype=np.float64).reshape(-1, 3) if n else np.zeros((0, 3))
+    q = np.array(quats, dtype=np.float64).reshape(-1, 4) if n else np.zeros((0, 4))
+    r = np.asarray(offsets, dtype=np.float64).reshape(-1)
+    m = np.asarray(mu, dtype=np.float64).reshape(-1)
+    if o.shape != (n, 3) or h.shape != (n,) or c.shape != (n, 3) or q.shape != (n, 4) or r.shape != (n,) or m.shape != (n,):
+        raise ValueError(f"set_sdfs: {len(o)} origins, {h.size} spacings, {len(c)} centres, {len(q)} quaternions, {r.size} offsets and {m.size} friction coefficients for {n} grids")
+    if n > SHAPE_MAX:
+        raise ValueError(f"set_sdfs: {n} fields: at most {SHAPE_MAX}")
+    tot = 0
+    for j in range(n):
+        if g[j].ndim != 3:
+            raise ValueError(f"set_sdfs: the grid of field {j} has {g[j].ndim} axes, not 3")
+        for a in range(3):
+            if not SDF_DIM_MIN <= g[j].shape[a] <= SDF_DIM_MAX:
+                raise ValueError(f"set_sdfs: dimension {g[j].shape[a]} of axis {a} of field {j} is below {SDF_DIM_MIN} or above {SDF_DIM_MAX}")
+        tot += g[j].size
+        if tot > SDF_SAMPLES_MAX:
+            raise ValueError(f"set_sdfs: {tot} samples up to field {j}: at most {SDF_SAMPLES_MAX} in total")
+        if not (h[j] > 0.0 and np.isfinite(h[j])):
+            raise ValueError(f"set_sdfs: spacing {h[j]:g} of field {j} is not finite and positive")
+        if not np.isfinite(o[j]).all():
+            raise ValueError(f"set_sdfs: origin ({o[j, 0]:g}, {o[j, 1]:g}, {o[j, 2]:g}) of field {j} is not finite")
+        if not np.isfinite(r[j]):
+            raise ValueError(f"set_sdfs: offset {r[j]:g} of field {j} is not finite")
+        bad = _box_pose_check("set_sdfs", "", c[j], q[j], j, "field")
+        if bad:
+            raise ValueError(bad)
+        _check_shape("set_sdfs", "field", j, m[j])
+        q[j] = quat_normalize(q[j])
+    for j in range(n):
+        if not np.isfinite(g[j]).all():
+            i0, i1, i2 = (int(e) for e in np.argwhere(~np.isfinite(g[j]))[0])
+            raise ValueError(f"set_sdfs: sample ({i0}, {i1}, {i2}) of field {j} is not finite ({g[j][i0, i1, i2]:g})")
+    if vertex_ids is not None and len(vertex_ids) != n:
+        raise ValueError(f"set_sdfs: {len(vertex_ids)} vertex lists for {n} fields")
+    return g, o.copy(), h.copy(), c.copy(), q, r.copy(), m.copy(), _shape_mask("set_sdfs", "field", tot_NV, n, vertex_ids)
 
 
 class _SystemMatrix:
@@ -434,6 +484,18 @@ class BaseScene:
         self._box_mu = np.zeros(0)
         self._box_mask = np.zeros(0, np.uint8)
         self.k_box = 0.0
+        # sampled distance-field colliders (set_sdfs): the poses as for the boxes (_sdf_c, _sdf_q for the next step, _sdf_cp, _sdf_qp of the last completed
+        # step, _sdf_cp_step, _sdf_qp_step the previous poses that the last completed step used); grids, origins, spacings, offsets, friction
+        # coefficients, the per-vertex mask and the stiffness k_sdf, kept here and pushed to the engine context lazily
+        self._sdf_c = self._sdf_cp = self._sdf_cp_step = np.zeros((0, 3))
+        self._sdf_q = self._sdf_qp = self._sdf_qp_step = np.zeros((0, 4))
+        self._sdf_grids = []
+        self._sdf_o = np.zeros((0, 3))
+        self._sdf_h = np.zeros(0)
+        self._sdf_r = np.zeros(0)
+        self._sdf_mu = np.zeros(0)
+        self._sdf_mask = np.zeros(0, np.uint8)
+        self.k_sdf = 0.0
         # wind (set_wind): the listed cloth faces and their weights, the two drag coefficients and the wind velocity of the next step, kept here and
         # pushed to the engine context lazily
         self._wind_f = np.zeros(0, np.int32)
@@ -726,6 +788,8 @@ class BaseScene:
                 self._push_capsules()
             if self.n_box:
                 self._push_boxes()
+            if self.n_sdf:
+                self._push_sdfs()
             if self.n_wind:
                 self._push_wind()
             self._dirty.clear()
@@ -748,6 +812,10 @@ class BaseScene:
                 self._push_boxes()
             elif "box_poses" in self._dirty:
                 self._ctx.set_box_poses(self._box_c, self._box_q, self._box_cp, self._box_qp)
+            if "sdfs" in self._dirty:
+                self._push_sdfs()
+            elif "sdf_poses" in self._dirty:
+                self._ctx.set_sdf_poses(self._sdf_c, self._sdf_q, self._sdf_cp, self._sdf_qp)
             if "wind" in self._dirty:
                 self._push_wind()
             elif "wind_velocity" in self._dirty:
@@ -1124,6 +1192,78 @@ class BaseScene:
             self._box_cp, self._box_qp = self._box_c.copy(), self._box_q.copy()
             self._dirty.add("box_poses")
 
+    # ------------------------------------------------------------------ sampled distance-field colliders (no counterpart in the reference)
+    @property
+    def n_sdf(self):
+        return len(self._sdf_r)
+
+    def set_sdfs(self, grids, origins, spacings, centres, quats, offsets, mu, k, vertex_ids=None):
+        """Up to 8 solids given as sampled distance fields, with the cloth outside and one stiffness k >= 0 in N/m: a mould a sheet is formed into, a bowl,
+        a ring, a shoulder -- any solid, concave ones included (engine/sdf.py samples analytic fields).  grids[j]: a 3-d array of samples in C order,
+        every dimension in [4, 512]; origins[j]: the local position of sample (0, 0, 0); spacings[j] > 0; the solid is {phi < offsets[j]} with phi the
+        cubic B-spline over the samples (the samples are its control values: a curved field is smoothed by about h^2/6 times its Laplacian).  Poses:
+        centre and quaternion (s, x, y, z) (set_sdf_poses or move_sdfs before every step); friction mu_j >= 0 acts on the slip relative to the field's
+        material point under the vertex.  Outside 1 <= t < n - 2 grid cells a vertex feels nothing: keep the solid inside (sdf.border_clear).
+        vertex_ids None: every field acts on every vertex; else one entry per field, None or a list of global vertex ids.  The fields start at rest
+        (previous poses = poses); an empty list removes them.  The lists are checked here, before any library call."""
+        g, o, h, c, q, r, m, mask = validate_sdfs(self.tot_NV, grids, origins, spacings, centres, quats, offsets, mu, vertex_ids)
+        k = _check_k("set_sdfs", "k_sdf", k)
+        self._sdf_c, self._sdf_cp, self._sdf_cp_step = c, c.copy(), c.copy()
+        self._sdf_q, self._sdf_qp, self._sdf_qp_step = q, q.copy(), q.copy()
+        self._sdf_grids, self._sdf_o, self._sdf_h, self._sdf_r, self._sdf_mu, self._sdf_mask, self.k_sdf = g, o, h, r, m, mask, k
+        self._dirty.add("sdfs")
+
+    def _check_sdf_poses(self, what, centres, quats):
+        c = np.asarray(centres, dtype=np.float64).reshape(-1, 3)
+        q = np.array(quats, dtype=np.float64).reshape(-1, 4)
+        if c.shape != (self.n_sdf, 3) or q.shape != (self.n_sdf, 4):
+            raise ValueError(f"set_sdf_poses: {len(c)} {what}centres and {len(q)} {what}quaternions for {self.n_sdf} fields")
+        for j in range(len(c)):
+            bad = _box_pose_check("set_sdf_poses", what, c[j], q[j], j, "field")
+            if bad:
+                raise ValueError(bad)
+            q[j] = quat_normalize(q[j])
+        return c.copy(), q
+
+    def set_sdf_poses(self, centres, quats, prev_centres=None, prev_quats=None):
+        """the poses of the next step (or energy, assembly, reverse step).  Where the fields were at the start of that step is kept by the scene: the
+        poses of the last completed step.  prev_centres and prev_quats together override it (a tape puts a recorded step back; a caller restarts a
+        rollout); one without the other is refused."""
+        if (prev_centres is None) != (prev_quats is None):
+            raise ValueError("set_sdf_poses: previous " + ("centres without previous quaternions" if prev_quats is None else "quaternions without previous centres"))
+        c, q = self._check_sdf_poses("", centres, quats)
+        if prev_centres is not None:
+            self._sdf_cp, self._sdf_qp = self._check_sdf_poses("previous ", prev_centres, prev_quats)
+        self._sdf_c, self._sdf_q = c, q
+        self._dirty.add("sdf_poses")
+
+    def move_sdfs(self, delta_pos, delta_theta):
+        """the poses of the next step from those in place: c += delta_pos, R <- exp([delta_theta]x) R per field (frames.compose: world-frame rotation
+        vectors applied on the left, the convention of sdf_pose_grad)"""
+        dp = np.asarray(delta_pos, dtype=np.float64).reshape(-1, 3)
+        dth = np.asarray(delta_theta, dtype=np.float64).reshape(-1, 3)
+        if dp.shape != (self.n_sdf, 3) or dth.shape != (self.n_sdf, 3):
+            raise ValueError(f"move_sdfs: {len(dp)} translations and {len(dth)} rotation vectors for {self.n_sdf} fields")
+        if self.n_sdf:
+            self.set_sdf_poses(*compose(self._sdf_c, self._sdf_q, dp, dth))
+
+    def sdf_force(self):
+        """(n, 6): the net force every field's solid applies to the cloth at the current positions and start-of-step positions, and its torque about
+        the field's centre"""
+        return self._ensure_ctx().sdf_force(self.pos.t, self.prev_pos.t)
+
+    def _push_sdfs(self):
+        self._ctx.set_sdfs(self._sdf_grids, self._sdf_o, self._sdf_h, self._sdf_c, self._sdf_q, self._sdf_r, self._sdf_mu, self._sdf_mask if self.n_sdf else None)
+        self._ctx.set_sdf_poses(self._sdf_c, self._sdf_q, self._sdf_cp, self._sdf_qp)
+        self._ctx.set_param("k_sdf", self.k_sdf)
+
+    def _sdfs_step_done(self):
+        """a step is complete: its poses are where the fields are at the start of the next one"""
+        if self.n_sdf:
+            self._sdf_cp_step, self._sdf_qp_step = self._sdf_cp, self._sdf_qp
+            self._sdf_cp, self._sdf_qp = self._sdf_c.copy(), self._sdf_q.copy()
+            self._dirty.add("sdf_poses")
+
     # ------------------------------------------------------------------ wind (no counterpart in the reference)
     @property
     def n_wind(self):
@@ -1285,6 +1425,7 @@ class BaseScene:
         self._spheres_step_done()
         self._capsules_step_done()
         self._boxes_step_done()
+        self._sdfs_step_done()
         self.last_stats = st
         self.nc[None] = st["nc"]
         self.E[None] = st["energy"]

@@ -54,6 +54,13 @@ def handle_tape_init(grad, sys, T):
         grad.box_poses = Field(torch.zeros((T, grad.n_box, 7), dtype=torch.float64))
         grad.box_poses_prev = Field(torch.zeros((T, grad.n_box, 7), dtype=torch.float64))
         grad.box_grad = Field(torch.zeros((T, grad.n_box, 14), dtype=torch.float64))
+    # sampled distance-field colliders (BaseScene.set_sdfs): the poses (centre (3), unit quaternion (4)) and previous poses of every step and
+    # d(loss)/d(c, theta, cp, theta_p, mu, offset) per reverse step
+    grad.n_sdf = getattr(sys, "n_sdf", 0)
+    if grad.n_sdf:
+        grad.sdf_poses = Field(torch.zeros((T, grad.n_sdf, 7), dtype=torch.float64))
+        grad.sdf_poses_prev = Field(torch.zeros((T, grad.n_sdf, 7), dtype=torch.float64))
+        grad.sdf_grad = Field(torch.zeros((T, grad.n_sdf, 14), dtype=torch.float64))
     # wind (BaseScene.set_wind): the wind velocity of every step and d(loss)/d(W of the step, c_n, c_t) per reverse step
     grad.n_wind = getattr(sys, "n_wind", 0)
     if grad.n_wind:
@@ -66,6 +73,21 @@ def wind_velocity_grad(grad):
     if not grad.n_wind:
         raise ValueError("wind_velocity_grad: the scene has no wind")
     return grad.wind_grad.t[:, 0:3].clone()
+
+
+def sdf_pose_grad(grad):
+    """(T, n, 6) d(loss)/d(pose trajectory of the sampled fields) -- [0:3] the centre, [3:6] a world-frame rotation vector applied on the left of the
+    step's orientation -- when each step's previous pose was the pose of the step before: row s is sdf_grad[s, :, 0:6] + sdf_grad[s + 1, :, 6:12].
+    Raises if the tape shows another trajectory."""
+    if not grad.n_sdf:
+        raise ValueError("sdf_pose_grad: the scene has no fields")
+    e, ep, g = grad.sdf_poses.t, grad.sdf_poses_prev.t, grad.sdf_grad.t
+    if not torch.equal(ep[1:], e[:-1]):
+        s = int((ep[1:] != e[:-1]).reshape(len(e) - 1, -1).any(dim=1).nonzero()[0, 0]) + 1
+        raise ValueError(f"sdf_pose_grad: the previous poses of step {s} are not the poses of step {s - 1}")
+    out = g[:, :, 0:6].clone()
+    out[:-1] += g[1:, :, 6:12]
+    return out
 
 
 def box_pose_grad(grad):
@@ -132,6 +154,10 @@ def handle_tape_reset(grad):
         grad.box_poses.fill(0)
         grad.box_poses_prev.fill(0)
         grad.box_grad.fill(0)
+    if grad.n_sdf:
+        grad.sdf_poses.fill(0)
+        grad.sdf_poses_prev.fill(0)
+        grad.sdf_grad.fill(0)
     if grad.n_handle:
         grad.handle_targets.fill(0)
         grad.handle_grad.fill(0)
@@ -161,6 +187,9 @@ def handle_tape_record(grad, sys, step):
     if grad.n_box:   # likewise: the poses of the step just completed, and where the boxes were when it started
         grad.box_poses.t[step] = torch.as_tensor(np.concatenate([sys._box_cp, sys._box_qp], axis=1))
         grad.box_poses_prev.t[step] = torch.as_tensor(np.concatenate([sys._box_cp_step, sys._box_qp_step], axis=1))
+    if grad.n_sdf:   # likewise for the sampled fields
+        grad.sdf_poses.t[step] = torch.as_tensor(np.concatenate([sys._sdf_cp, sys._sdf_qp], axis=1))
+        grad.sdf_poses_prev.t[step] = torch.as_tensor(np.concatenate([sys._sdf_cp_step, sys._sdf_qp_step], axis=1))
 
 
 def handle_tape_push(grad, sys, step):
@@ -182,6 +211,9 @@ def handle_tape_push(grad, sys, step):
     if grad.n_box:   # the poses and previous poses of step `step`: the reverse step evaluates b0, the contact frame and the slip with them
         e, ep = grad.box_poses.t[step].numpy(), grad.box_poses_prev.t[step].numpy()
         sys.set_box_poses(e[:, 0:3], e[:, 3:7], ep[:, 0:3], ep[:, 3:7])
+    if grad.n_sdf:   # the poses and previous poses of step `step`: the reverse step evaluates y0, the contact frame and the slip with them
+        e, ep = grad.sdf_poses.t[step].numpy(), grad.sdf_poses_prev.t[step].numpy()
+        sys.set_sdf_poses(e[:, 0:3], e[:, 3:7], ep[:, 0:3], ep[:, 3:7])
 
 
 def handle_tape_pull(grad, ctx, step):
@@ -202,6 +234,8 @@ def handle_tape_pull(grad, ctx, step):
         grad.capsule_grad.t[step] += torch.as_tensor(ctx.capsule_grad(grad.pos_buffer.t[step], grad.pos_buffer.t[step - 1]))
     if grad.n_box:   # box_grad[step] += d(loss)/d(c, theta, cp, theta_p of step `step`, mu, r) of the reverse step just taken, at the tape state (x_step, x_{step-1})
         grad.box_grad.t[step] += torch.as_tensor(ctx.box_grad(grad.pos_buffer.t[step], grad.pos_buffer.t[step - 1]))
+    if grad.n_sdf:   # sdf_grad[step] += d(loss)/d(c, theta, cp, theta_p of step `step`, mu, offset) of the reverse step just taken, at the tape state (x_step, x_{step-1})
+        grad.sdf_grad.t[step] += torch.as_tensor(ctx.sdf_grad(grad.pos_buffer.t[step], grad.pos_buffer.t[step - 1]))
 
 
 class Grad:
@@ -261,6 +295,11 @@ class Grad:
         """(T, n, 6) d(loss)/d(pose trajectory of the boxes: centre, world-frame rotation vector); raises if a step's previous poses were not the poses of
         the step before"""
         return box_pose_grad(self)
+
+    def sdf_pose_grad(self):
+        """(T, n, 6) d(loss)/d(pose trajectory of the sampled fields: centre, world-frame rotation vector); raises if a step's previous poses were not
+        the poses of the step before"""
+        return sdf_pose_grad(self)
 
     # :37-51
     def copy_pos(self, sys, step):

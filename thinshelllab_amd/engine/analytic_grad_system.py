@@ -13,7 +13,7 @@ Beyond the reference: ``param_keys`` names further scalars, spelled as ``tsl_set
 """
 import torch
 
-from .analytic_grad_single import handle_tape_init, handle_tape_pull, handle_tape_push, handle_tape_record, handle_tape_reset, sphere_centre_grad, capsule_end_grad, box_pose_grad, wind_velocity_grad
+from .analytic_grad_single import handle_tape_init, handle_tape_pull, handle_tape_push, handle_tape_record, handle_tape_reset, sphere_centre_grad, capsule_end_grad, box_pose_grad, sdf_pose_grad, wind_velocity_grad
 from .field import Field, ScalarField
 
 
@@ -81,6 +81,11 @@ class Grad:
         """(T, n, 6) d(loss)/d(pose trajectory of the boxes: centre, world-frame rotation vector); raises if a step's previous poses were not the poses of
         the step before"""
         return box_pose_grad(self)
+
+    def sdf_pose_grad(self):
+        """(T, n, 6) d(loss)/d(pose trajectory of the sampled fields: centre, world-frame rotation vector); raises if a step's previous poses were not
+        the poses of the step before"""
+        return sdf_pose_grad(self)
 
     def copy_pos(self, sys, step):  # :46-59
         self.pos_buffer.t[step].copy_(sys.pos.t)

@@ -66,6 +66,7 @@ class SceneGroup:
             s._spheres_step_done()
             s._capsules_step_done()
             s._boxes_step_done()
+            s._sdfs_step_done()
             s.last_stats = d
             s.nc[None] = d["nc"]
             s.E[None] = d["energy"]
