@@ -700,6 +700,29 @@ int tsl_mg_export(tsl_ctx* ctx, int32_t hierarchy, int32_t level, int32_t what, 
 int tsl_mg_apply(tsl_ctx* ctx, const double* r_dev, double* z_dev);
 int tsl_solve_with(tsl_ctx* ctx, int32_t method, int32_t cap, const double* rhs_dev, double* x_dev, tsl_solve_stats* stats_host);
 
+/* ---- the operator of the Krylov solvers taken apart (tests/ only; csrc/op_test_api.hpp).  Like the hooks above they call the solver's own functions
+ * and kernels and add no launch to any existing path.
+ *   tsl_op_export: array `what` to the host as the next solve reads it; cap = room in elements; returns the number of elements (0 where a scene
+ *                  without constraints has no such array).  int32: SLICE_OFF[n_slices + 1], SLICE_LEN[n_slices], COLIDX[n_slots], PERM, ROWPOS,
+ *                  DIAG_PERM[tot_NV], CR_PTR[tot_NV + 1], CR_ENT[4 nc] ((constraint << 2) | slot), CR_ROWS[16 nc]; uint8: FZMASK[tot_NV]
+ *                  (bit k: component k frozen, solver order); double: VALS / VALS_FULL[9 n_slots] (masked / unmasked, padded slots included),
+ *                  MDT2[tot_NV], DINV / CDIAG[9 tot_NV] (solver order; formed first only if the context holds them to be stale).
+ *   tsl_op_apply:  y = H x by one kernel, x and y 3 * tot_NV device vectors in the caller's vertex order.  kernel 0: k_spmv with the dot into slot 0 of
+ *                  the scalar record (returned in *dot_host) plus k_contact_matvec; 1..7: variants 1..7 of tsl_bench_spmv (static matrix only, their
+ *                  per-workgroup partials of x . y in part_host); 8: the plain product of the solvers (launch_spmv, contact rows folded in); 9: the
+ *                  same kernel with partials, as MINRES launches it.  Returns the number of partials.
+ *   tsl_pcg_trace: the start of a PCG run as the solver launches it and n_iter iterations with a threshold nothing meets, the ones behind the
+ *                  first launched one by one (use_graph 0) or as replays of the captured chunk (1: n_iter - 1 must be a multiple of the chunk).
+ *                  out_vec: x, r, z, p, the previous p, Ap (6 x 3 tot_NV, solver order); out_part: the partials of p.Ap, r.z, r.r (3 x cap_part,
+ *                  counts in n_part[3]); out_scal[11]: rzh[0], rzh[1], thresh2, bb, rr_last, rz_last, pAp_last, flag, iters, n_part1, n_part2.
+ *                  Returns the chunk. */
+enum { TSL_OP_SLICE_OFF = 0, TSL_OP_SLICE_LEN = 1, TSL_OP_COLIDX = 2, TSL_OP_PERM = 3, TSL_OP_ROWPOS = 4, TSL_OP_DIAG_PERM = 5, TSL_OP_VALS = 6, TSL_OP_VALS_FULL = 7,
+       TSL_OP_FZMASK = 8, TSL_OP_MDT2 = 9, TSL_OP_DINV = 10, TSL_OP_CDIAG = 11, TSL_OP_CR_PTR = 12, TSL_OP_CR_ENT = 13, TSL_OP_CR_ROWS = 14 };
+int tsl_op_export(tsl_ctx* ctx, int32_t what, void* host, int64_t cap);
+int tsl_op_apply(tsl_ctx* ctx, int32_t kernel, const double* x_dev, double* y_dev, double* dot_host, double* part_host, int32_t cap);
+int tsl_pcg_trace(tsl_ctx* ctx, const double* rhs_dev, int32_t n_iter, int32_t use_graph, double* out_vec_host, double* out_part_host, int32_t cap_part, int32_t* n_part_host,
+                  double* out_scal_host);
+
 /* ---- scene groups: several scenes of ONE device whose sparse direct solves share their launches --------------------------------------------
  * The reference's trajectory-optimisation drivers roll out independent copies of one scene (training/trajopt_*.py, one rollout per candidate
  * trajectory); a single 100k-triangle scene leaves most of the chip idle during the latency-bound parts of its factorisation.  A group takes the

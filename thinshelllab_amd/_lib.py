@@ -84,6 +84,7 @@ EXPORTS = [
     "tsl_constraints_export", "tsl_contact_blocks_export", "tsl_proj_export", "tsl_proj_import", "tsl_set_border", "tsl_spd_project", "tsl_profile_reset", "tsl_profile_read", "tsl_profile_read_events",
     "tsl_bench_spmv", "tsl_bench_direct", "tsl_direct_info", "tsl_direct_counters",
     "tsl_mg_info", "tsl_mg_export", "tsl_mg_apply", "tsl_solve_with",
+    "tsl_op_export", "tsl_op_apply", "tsl_pcg_trace",
     "tsl_group_create", "tsl_group_destroy", "tsl_group_step", "tsl_group_adjoint_step", "tsl_group_info",
 ]
 
@@ -192,6 +193,9 @@ def load():
     L.tsl_mg_export.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64]
     L.tsl_mg_apply.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     L.tsl_solve_with.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(SolveStats)]
+    L.tsl_op_export.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64]
+    L.tsl_op_apply.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(C.c_double), C.c_void_p, C.c_int32]
+    L.tsl_pcg_trace.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
     L.tsl_param_grad.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]
     L.tsl_friction_grad.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]
     L.tsl_param_grad_keys.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_char_p), C.c_int32, C.POINTER(C.c_double)]

@@ -657,6 +657,51 @@ class TslContext:
         check(self.L.tsl_solve_with(self.h, int(method), int(cap), _ptr(rhs), _ptr(x), C.byref(st)), "tsl_solve_with")
         return x, st.as_dict()
 
+    # ---- the operator of the Krylov solvers taken apart (tests): tsl_op_export / tsl_op_apply / tsl_pcg_trace
+    OP_ARRAYS = dict(slice_off=(0, np.int32), slice_len=(1, np.int32), colidx=(2, np.int32), perm=(3, np.int32), rowpos=(4, np.int32), diag_perm=(5, np.int32),
+                     vals=(6, np.float64), vals_full=(7, np.float64), fzmask=(8, np.uint8), mdt2=(9, np.float64), Dinv=(10, np.float64), c_diag=(11, np.float64),
+                     cr_ptr=(12, np.int32), cr_ent=(13, np.int32), cr_rows=(14, np.int32))
+
+    def op_export(self, what):
+        """array `what` (a key of OP_ARRAYS) as the next solve reads it, flat, in the solver's row order; empty where a scene without constraints has none"""
+        self.refresh_stream()
+        code, dt = self.OP_ARRAYS[what]
+        if what in ("vals", "vals_full", "colidx"):
+            so = self.op_export("slice_off")
+            cap = int(so[-1]) * (1 if what == "colidx" else 9)
+        elif what in ("cr_ent", "cr_rows"):
+            cap = 16 * (self.max_n_constraints + self.tie_count())
+        else:
+            cap = 9 * self.tot_NV + 64
+        out = np.zeros(max(cap, 1), dt)
+        n = check(self.L.tsl_op_export(self.h, code, out.ctypes.data, cap), f"tsl_op_export({what})")
+        return out[:n].copy()
+
+    def op_apply(self, kernel, x, y=None):
+        """(y, dot, partials) of y = H x by product kernel `kernel` (0..9, tsl_hip.h); x, y device vectors in the caller's vertex order"""
+        self.refresh_stream()
+        if y is None:
+            y = torch.empty_like(x)
+        part = np.zeros(self.tot_NV + 64)
+        dot = C.c_double(0)
+        n = check(self.L.tsl_op_apply(self.h, int(kernel), _ptr(x), _ptr(y), C.byref(dot), part.ctypes.data, len(part)), "tsl_op_apply")
+        return y, dot.value, part[:n].copy()
+
+    def pcg_trace(self, rhs, n_iter, use_graph=False):
+        """the state of a PCG run on rhs after n_iter iterations that nothing stops: dict of x, r, z, p, p_prev, Ap (solver order), part_pAp, part_rz,
+        part_rr, the scalar record and the chunk of the captured graph"""
+        self.refresh_stream()
+        n3 = 3 * self.tot_NV
+        cap = self.tot_NV + 2048
+        vec = np.zeros((6, n3)); part = np.zeros((3, cap)); npart = np.zeros(3, np.int32); sc = np.zeros(11)
+        chunk = check(self.L.tsl_pcg_trace(self.h, _ptr(rhs), int(n_iter), int(bool(use_graph)), vec.ctypes.data, part.ctypes.data, cap, npart.ctypes.data, sc.ctypes.data),
+                      "tsl_pcg_trace")
+        out = dict(zip(("x", "r", "z", "p", "p_prev", "Ap"), vec))
+        out.update(part_pAp=part[0, :npart[0]].copy(), part_rz=part[1, :npart[1]].copy(), part_rr=part[2, :npart[2]].copy(), chunk=chunk)
+        out.update(zip(("rzh0", "rzh1", "thresh2", "bb", "rr_last", "rz_last", "pAp_last"), sc[:7]))
+        out.update(flag=int(sc[7]), iters=int(sc[8]), n_part1=int(sc[9]), n_part2=int(sc[10]))
+        return out
+
     def constraints(self):
         m = self.max_n_constraints + self.tie_count()   # (the tie slots lie behind the detected ones)
         idx = np.zeros((m, 4), np.int32); w = np.zeros((m, 3)); k = np.zeros(m); dx0 = np.zeros((m, 3)); T = np.zeros((m, 6)); n = np.zeros((m, 3)); mu = np.zeros(m)

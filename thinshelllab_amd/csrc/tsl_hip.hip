@@ -652,6 +652,26 @@ static void launch_spmv(tsl_ctx* c, const double* vals, const double* x, double*
                        check_flag);
 }
 
+// The product kernels that tsl_bench_spmv times (variants 0..7: k_spmv with the fused dot into pAp[0], six instantiations of k_spmv_mw on the static
+// matrix with their per-workgroup dot partials), launched once: one place for the timing and for tsl_op_apply (op_test_api.hpp), which checks what they
+// return.  Returns the number of partials the launch writes (its grid; 0: the dot goes to pAp[0]), -1 for another variant.
+static int spmv_variant_launch(tsl_ctx* c, int variant, const double* x, double* y, double* part) {
+  hipStream_t s = c->stream;
+  const int ns = c->n_slices;
+  switch (variant) {
+    case 0: hipLaunchKernelGGL(k_spmv, dim3(nblk((long)ns * 64, 256)), dim3(256), 0, s, c->NV, ns, c->slice_off.p, c->slice_len.p, c->colidx.p, c->vals.p, x, y, SC(c), 0, 0, (unsigned long long*)nullptr); break;
+    case 1: hipLaunchKernelGGL((k_spmv_mw<1, 4, false>), dim3(nblk(ns, 4)), dim3(256), 0, s, c->NV, ns, c->slice_off.p, c->slice_len.p, c->colidx.p, c->vals.p, x, y, part, (const int*)nullptr, ContactRows{}); break;
+    case 2: hipLaunchKernelGGL((k_spmv_mw<4, 1, false>), dim3(ns), dim3(256), 0, s, c->NV, ns, c->slice_off.p, c->slice_len.p, c->colidx.p, c->vals.p, x, y, part, (const int*)nullptr, ContactRows{}); break;
+    case 3: hipLaunchKernelGGL((k_spmv_mw<4, 1, true>), dim3(ns), dim3(256), 0, s, c->NV, ns, c->slice_off.p, c->slice_len.p, c->colidx.p, c->vals.p, x, y, part, (const int*)nullptr, ContactRows{}); break;
+    case 4: hipLaunchKernelGGL((k_spmv_mw<2, 2, false>), dim3(nblk(ns, 2)), dim3(256), 0, s, c->NV, ns, c->slice_off.p, c->slice_len.p, c->colidx.p, c->vals.p, x, y, part, (const int*)nullptr, ContactRows{}); break;
+    case 5: hipLaunchKernelGGL((k_spmv_mw<8, 1, false>), dim3(ns), dim3(512), 0, s, c->NV, ns, c->slice_off.p, c->slice_len.p, c->colidx.p, c->vals.p, x, y, part, (const int*)nullptr, ContactRows{}); break;
+    case 6: hipLaunchKernelGGL((k_spmv_mw<4, 2, false>), dim3(nblk(ns, 2)), dim3(512), 0, s, c->NV, ns, c->slice_off.p, c->slice_len.p, c->colidx.p, c->vals.p, x, y, part, (const int*)nullptr, ContactRows{}); break;
+    case 7: hipLaunchKernelGGL((k_spmv_mw<2, 2, true>), dim3(nblk(ns, 2)), dim3(256), 0, s, c->NV, ns, c->slice_off.p, c->slice_len.p, c->colidx.p, c->vals.p, x, y, part, (const int*)nullptr, ContactRows{}); break;
+    default: return -1;
+  }
+  return variant == 0 ? 0 : variant == 1 ? nblk(ns, 4) : (variant == 4 || variant == 6 || variant == 7) ? nblk(ns, 2) : ns;
+}
+
 static void prof_collect(tsl_ctx* c) {
   for (size_t i = 0; i < c->ev_used; i++) {
     float ms = 0;
@@ -1572,11 +1592,12 @@ struct PcgOutcome { bool need_fallback = false, indefinite = false; };
 
 // Multigrid- or block-Jacobi-preconditioned CG, restarted from the true residual (at most 20 times); st->iters counts at most `cap` iterations
 // (to the chunk).  out->need_fallback: not converged; out->indefinite: the recurrence met a direction of non-positive curvature.
-static int pcg_restarts(tsl_ctx* c, tsl_solve_stats* st, int cap, PcgOutcome* out) {
+// The start of a PCG run in three parts, shared by pcg_restarts and tsl_pcg_trace (op_test_api.hpp), so that the traced iterations start exactly
+// where the solver's do.  pcg_begin: x = 0, |b|^2 (returned; 0: nothing to solve), the set-up of the preconditioners.
+static int pcg_begin(tsl_ctx* c, double* bb_out) {
   hipStream_t s = c->stream;
-  const int NV = c->NV;
-  const size_t n3 = 3 * (size_t)NV;
-  const int gb = nblk(NV, 256);
+  const size_t n3 = 3 * (size_t)c->NV;
+  *bb_out = 0;
   TSL_TRY(block_jacobi_ensure(c));   // (skipped by an assembly that expected the factorisation to take this solve)
   HIP_OK(hipMemsetAsync(c->v_x.p, 0, n3 * sizeof(double), s));
   HIP_OK(hipMemsetAsync(c->scal.p, 0, sizeof(SolverScalars), s));
@@ -1584,23 +1605,52 @@ static int pcg_restarts(tsl_ctx* c, tsl_solve_stats* st, int cap, PcgOutcome* ou
   TSL_TRY(read_scal(c));
   const double bb = HSC(c)->bb;
   if (!(bb > 0)) return 0;  // zero rhs -> x = 0
+  if (body_active(c) && !c->bd_valid) TSL_TRY(body_build_inverse(c));
+  *bb_out = bb;
+  return 0;
+}
+static int pcg_n_rz(tsl_ctx* c) { return nblk(c->NV, 256) + ((body_active(c) && c->bd_valid) ? c->bd_wg : 0); }
+// pcg_start_residual: the scalar record of a (re)start, the true residual r = b - H x (restart: x is not zero), z = Dinv r, the partials of r.r and their sum
+static int pcg_start_residual(tsl_ctx* c, double bb, double thresh2, bool restart) {
+  hipStream_t s = c->stream;
+  const int NV = c->NV, gb = nblk(NV, 256);
+  PcgScal hs;
+  memset(&hs, 0, sizeof(hs));
+  hs.bb = bb; hs.thresh2 = thresh2; hs.n_part1 = c->n_slices; hs.n_part2 = pcg_n_rz(c);
+  HIP_OK(hipMemcpyAsync(c->scal.p, &hs, sizeof(PcgScal), hipMemcpyHostToDevice, s));
+  if (restart) launch_spmv(c, c->vals.p, c->v_x.p, c->v_Ap.p, -1, 0);
+  // true residual, z = M^-1 r, partial r.z / r.r
+  hipLaunchKernelGGL(k_pcg_update, dim3(gb + (pcg_fold(c) ? c->bd_wg : 0)), dim3(256), 0, s, NV, (const double*)nullptr, (const double*)nullptr, c->Dinv.p, c->v_x.p, c->v_r.p,
+                     c->v_z.p, c->part_pAp.p, c->part_rz.p, c->part_rr.p, PSC(c), 0, c->v_b.p, restart ? c->v_Ap.p : (const double*)nullptr, mg_active(c) ? 0 : 1,
+                     (const double*)nullptr, gb, c->bd_args, c->bd_Binv.p, pcg_fold(c) ? c->bd_rb.p : (double*)nullptr, c->bd_scr_n);
+  hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(256), 0, s, c->part_rr.p, gb, &PSC(c)->rr_last);
+  return 0;
+}
+// pcg_start_precond: the rest of z = M^-1 r behind it (the cycle, or the dense body blocks), the sum of the r.z partials
+static int pcg_start_precond(tsl_ctx* c) {
+  hipStream_t s = c->stream;
+  const int gb = nblk(c->NV, 256);
+  if (mg_active(c)) {
+    if (!c->mg_ops_valid) TSL_TRY(mg_setup_operators(c));
+    mg_vcycle(c, c->v_r.p, c->v_z.p, c->part_rz.p);
+  } else if (body_active(c) && c->bd_valid) body_apply(c, 0, c->v_r.p, nullptr, c->v_z.p, c->v_r.p, c->part_rz.p + gb);
+  hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(256), 0, s, c->part_rz.p, pcg_n_rz(c), &PSC(c)->rz_last);
+  return 0;
+}
+// iterations per graph replay / host convergence read.  With multigrid: eight on long solves (the previous time step needed more than 150 per
+// solve: cfg4 1.56 -> 1.53 s per step), four otherwise (the idle launches after convergence cost drape 4 % with eight).  Block-Jacobi PCG: 32.
+static int pcg_chunk(tsl_ctx* c) { return mg_active(c) ? (c->last_step_iters_per_solve > 150.0 ? 8 : 4) : 32; }
+
+static int pcg_restarts(tsl_ctx* c, tsl_solve_stats* st, int cap, PcgOutcome* out) {
+  hipStream_t s = c->stream;
+  double bb = 0;
+  TSL_TRY(pcg_begin(c, &bb));
+  if (!(bb > 0)) return 0;  // zero rhs -> x = 0
   const double tol2 = c->cg_tol * c->cg_tol * bb;
   int total_it = 0;
-  if (body_active(c) && !c->bd_valid) TSL_TRY(body_build_inverse(c));
-  const bool bd = body_active(c) && c->bd_valid;
-  const int n_rz = gb + (bd ? c->bd_wg : 0);
   double rr_prev_outer = 1e300;
   for (int outer = 0; outer < 20; outer++) {
-    PcgScal hs;
-    memset(&hs, 0, sizeof(hs));
-    hs.bb = bb; hs.thresh2 = 0.25 * tol2; hs.n_part1 = c->n_slices; hs.n_part2 = n_rz;
-    HIP_OK(hipMemcpyAsync(c->scal.p, &hs, sizeof(PcgScal), hipMemcpyHostToDevice, s));
-    if (outer > 0) launch_spmv(c, c->vals.p, c->v_x.p, c->v_Ap.p, -1, 0);
-    // true residual, z = M^-1 r, partial r.z / r.r
-    hipLaunchKernelGGL(k_pcg_update, dim3(gb + (pcg_fold(c) ? c->bd_wg : 0)), dim3(256), 0, s, NV, (const double*)nullptr, (const double*)nullptr, c->Dinv.p, c->v_x.p, c->v_r.p,
-                       c->v_z.p, c->part_pAp.p, c->part_rz.p, c->part_rr.p, PSC(c), 0, c->v_b.p, outer > 0 ? c->v_Ap.p : (const double*)nullptr, mg_active(c) ? 0 : 1,
-                       (const double*)nullptr, gb, c->bd_args, c->bd_Binv.p, pcg_fold(c) ? c->bd_rb.p : (double*)nullptr, c->bd_scr_n);
-    hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(256), 0, s, c->part_rr.p, gb, &PSC(c)->rr_last);
+    TSL_TRY(pcg_start_residual(c, bb, 0.25 * tol2, outer > 0));
     if (outer > 0) {  // verification of a converged recurrence: the true residual decides before a V-cycle is spent on it
       TSL_TRY(read_scal(c));
       const double rr1 = HPSC(c)->rr_last;
@@ -1610,11 +1660,7 @@ static int pcg_restarts(tsl_ctx* c, tsl_solve_stats* st, int cap, PcgOutcome* ou
       // this conditioning (a direct solver has the same backward error); accept if within 1e2 of the requested tolerance (reported: attained)
       if (rr1 > 0.25 * rr_prev_outer && rr1 <= 1e4 * tol2) { out->need_fallback = false; st->attained = 1; break; }
     }
-    if (mg_active(c)) {
-      if (!c->mg_ops_valid) TSL_TRY(mg_setup_operators(c));
-      mg_vcycle(c, c->v_r.p, c->v_z.p, c->part_rz.p);
-    } else if (bd) body_apply(c, 0, c->v_r.p, nullptr, c->v_z.p, c->v_r.p, c->part_rz.p + gb);
-    hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(256), 0, s, c->part_rz.p, n_rz, &PSC(c)->rz_last);
+    TSL_TRY(pcg_start_precond(c));
     TSL_TRY(read_scal(c));
     const double rr0 = HPSC(c)->rr_last;
     st->rel_residual = sqrt(rr0 / bb);
@@ -1628,9 +1674,7 @@ static int pcg_restarts(tsl_ctx* c, tsl_solve_stats* st, int cap, PcgOutcome* ou
     // iteration 0 (beta = 0) eagerly, then graph replays of `chunk` iterations (parities 1,0,...)
     launch_pcg_iteration(c, 0, 1, nullptr);
     it++; total_it++; c->prof_launches++;
-    // iterations per graph replay / host convergence read.  With multigrid: eight on long solves (the previous time step needed more than 150 per
-    // solve: cfg4 1.56 -> 1.53 s per step), four otherwise (the idle launches after convergence cost drape 4 % with eight).  Block-Jacobi PCG: 32.
-    const int chunk = mg_active(c) ? (c->last_step_iters_per_solve > 150.0 ? 8 : 4) : 32;
+    const int chunk = pcg_chunk(c);
     TSL_TRY(pcg_chunk_graph(c, chunk));
     int n_chunks = 0;
     // (a second chunk kept in flight behind the one whose convergence record the host waits for was measured and dropped: the time per iteration
@@ -1870,6 +1914,7 @@ extern "C" int tsl_solve(tsl_ctx* c, const double* rhs, double* x, tsl_solve_sta
 
 #include "param_api.hpp"
 #include "mg_test_api.hpp"
+#include "op_test_api.hpp"
 
 // ------------------------------------------------------------------------------------------------
 extern "C" int tsl_update_ref_angle(tsl_ctx* c, const double* pos, double* ref) {
@@ -2256,6 +2301,7 @@ extern "C" int tsl_matrix_import(tsl_ctx* c, const double* vals) {
   c->ds.numeric_valid = false; c->ds.anorm_valid = false;
   c->mg_ops_valid = false; c->pc_separate = false;
   c->bd_valid = false; c->mg_omega_valid = false;
+  c->dinv_valid = false;   // the block-Jacobi inverse too: block_jacobi_ensure kept the one of the values before (c_diag holds contact blocks only: it stays)
   return 0;
 }
 
@@ -2316,14 +2362,7 @@ extern "C" int tsl_bench_spmv(tsl_ctx* c, int variant, int reps, double* us_per_
   const int variant30_grid = std::min<long>(std::max<long>((long)c->v_t4.n, 1), 2048);
   auto launch = [&]() {
     switch (variant) {
-      case 0: hipLaunchKernelGGL(k_spmv, dim3(nblk((long)ns * 64, 256)), dim3(256), 0, s, c->NV, ns, c->slice_off.p, c->slice_len.p, c->colidx.p, c->vals.p, c->v_p.p, c->v_Ap.p, SC(c), 0, 0, (unsigned long long*)nullptr); break;
-      case 1: hipLaunchKernelGGL((k_spmv_mw<1, 4, false>), dim3(nblk(ns, 4)), dim3(256), 0, s, c->NV, ns, c->slice_off.p, c->slice_len.p, c->colidx.p, c->vals.p, c->v_p.p, c->v_Ap.p, c->v_t4.p, (const int*)nullptr, ContactRows{}); break;
-      case 2: hipLaunchKernelGGL((k_spmv_mw<4, 1, false>), dim3(ns), dim3(256), 0, s, c->NV, ns, c->slice_off.p, c->slice_len.p, c->colidx.p, c->vals.p, c->v_p.p, c->v_Ap.p, c->v_t4.p, (const int*)nullptr, ContactRows{}); break;
-      case 3: hipLaunchKernelGGL((k_spmv_mw<4, 1, true>), dim3(ns), dim3(256), 0, s, c->NV, ns, c->slice_off.p, c->slice_len.p, c->colidx.p, c->vals.p, c->v_p.p, c->v_Ap.p, c->v_t4.p, (const int*)nullptr, ContactRows{}); break;
-      case 4: hipLaunchKernelGGL((k_spmv_mw<2, 2, false>), dim3(nblk(ns, 2)), dim3(256), 0, s, c->NV, ns, c->slice_off.p, c->slice_len.p, c->colidx.p, c->vals.p, c->v_p.p, c->v_Ap.p, c->v_t4.p, (const int*)nullptr, ContactRows{}); break;
-      case 5: hipLaunchKernelGGL((k_spmv_mw<8, 1, false>), dim3(ns), dim3(512), 0, s, c->NV, ns, c->slice_off.p, c->slice_len.p, c->colidx.p, c->vals.p, c->v_p.p, c->v_Ap.p, c->v_t4.p, (const int*)nullptr, ContactRows{}); break;
-      case 6: hipLaunchKernelGGL((k_spmv_mw<4, 2, false>), dim3(nblk(ns, 2)), dim3(512), 0, s, c->NV, ns, c->slice_off.p, c->slice_len.p, c->colidx.p, c->vals.p, c->v_p.p, c->v_Ap.p, c->v_t4.p, (const int*)nullptr, ContactRows{}); break;
-      case 7: hipLaunchKernelGGL((k_spmv_mw<2, 2, true>), dim3(nblk(ns, 2)), dim3(256), 0, s, c->NV, ns, c->slice_off.p, c->slice_len.p, c->colidx.p, c->vals.p, c->v_p.p, c->v_Ap.p, c->v_t4.p, (const int*)nullptr, ContactRows{}); break;
+      case 0: case 1: case 2: case 3: case 4: case 5: case 6: case 7: spmv_variant_launch(c, variant, c->v_p.p, c->v_Ap.p, c->v_t4.p); break;
       case 10: hipLaunchKernelGGL(k_spmv, dim3(nblk((long)ns * 64, 256)), dim3(256), 0, s, c->NV, ns, c->slice_off.p, c->slice_len.p, c->colidx.p, c->vals.p, c->v_p.p, c->v_Ap.p, SC(c), 0, 1, (unsigned long long*)nullptr); break;
       case 11: hipLaunchKernelGGL(k_spmv, dim3(nblk((long)ns * 64, 256)), dim3(256), 0, s, c->NV, ns, c->slice_off.p, c->slice_len.p, c->colidx.p, c->vals.p, c->v_p.p, c->v_Ap.p, SC(c), -1, 0, (unsigned long long*)nullptr); break;
       case 12: {  // one full PCG iteration body (never converges: thresh2 = 0)
